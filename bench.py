@@ -226,6 +226,24 @@ def cputopo_ranges(cpus):
     return ",".join(out)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, logits, loss):
+    """What a caller of the timed step receives, as float32 .npy files: logits.npy [B, K], loss.npy [] and grad.<parameter name>.npy for
+    every trainable parameter (its .grad, the shard-mean at N > 1).  The inputs, weights and dropout seed are fixed by the arguments."""
+    arrays = {"logits": logits, "loss": loss}
+    arrays.update((f"grad.{k}", p.grad) for k, p in model.named_parameters() if p.requires_grad and p.grad is not None)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    print(f"bench.py: {len(arrays)} arrays ({total} bytes) written to {out_dir}", file=sys.stderr, flush=True)
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` with no launcher: start the N ranks as FRESH child processes (never a re-exec) -- this parent has not
     touched the GPU (importing torch does not initialise HIP) and never will.  Every child gets RANK / LOCAL_RANK / WORLD_SIZE /
@@ -300,11 +318,16 @@ def main():
     ap.add_argument("--dump-gemm-shapes", default=None, metavar="FILE",
                     help="write {workload, classes: {GEMM class: [M, N, K]}} of this run's instrumented pass to FILE (tools/pmc_traffic.py attaches "
                          "the shapes to the traffic clusters of a PMC pass of the same command)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned -- logits, loss and every trainable gradient -- as "
+                         "DIR/<name>.npy (rank 0), to compare two builds output for output")
     ap.add_argument("--launch-check", action="store_true", help="every rank reports its launcher environment and exits before any GPU call (tests)")
     ap.add_argument("--allow-diag", "--allow-ablate", dest="allow_diag", action="store_true",
                     help="diagnostics only: run on the measurement build (GAVIKO_HIP_DIAG=1: A/B switches and timing ablations live there); the "
                          "output line is marked INVALID")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch is None:
         args.batch = DEFAULT_BATCH[args.method]
     if args.precision is None:
@@ -357,6 +380,8 @@ def main():
 
     from gaviko_amd import engine as eng_mod
     from gaviko_amd.utils import synth
+    # the device-side dropout draws start from torch's base seed (engine._seed_base): fixed, so that the same arguments compute the same step
+    torch.manual_seed(0)
     model = build(args.backbone, dev, args.method, args.precision)
     if world > 1:
         model.make_reducer()
@@ -383,9 +408,10 @@ def main():
 
     def step():
         optimizer.zero_grad(set_to_none=to_none)
-        loss = criterion(model(x), y)
+        logits = model(x)
+        loss = criterion(logits, y)
         loss.backward()
-        return loss
+        return logits, loss
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -398,7 +424,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -406,6 +432,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     vps = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:               # before the passes below overwrite the logits buffer and the gradients
+        dump_outputs(args.dump_outputs, model, *last)
 
     bbname = {"vit-b16": "ViT-B/16", "vit-l16": "ViT-L/16", "vit-t16": "ViT-T/16"}.get(args.backbone, args.backbone)
     eng0 = model._engine()
