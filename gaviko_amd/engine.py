@@ -328,15 +328,17 @@ class Engine(GavikoPaths, PeftPaths):
         if names is None or any(n in self._fold_names for n in names):
             self._fold_version = None
 
-    def workspace(self, B: int, device, train: bool):
-        key = (B, train, str(device))
+    def workspace(self, B: int, device, train: bool, keep_attn: bool = False):
+        """keep_attn (inference only, gaviko_amd.explain): a workspace of its own whose forward keeps every layer's qkv / lse (and every
+        other per-layer slot) as a training forward does, for the attention-map kernels."""
+        key = (B, train, str(device)) + (("attn",) if keep_attn else ())
         if key in self._wss:
             self._ws = self._wss[key]
             return self._ws
         C, T, N, M = self.C, self.T, self.N, B * self.T
         z = lambda r, c, dt: ops.act_zeros(r, c, dt, device)
         f32, bf16 = torch.float32, self.adt                # "bf16" below = the GEMM-operand dtype (fp32 on the fp32 path)
-        nsave = self.depth if train else 1
+        nsave = self.depth if (train or keep_attn) else 1
         ws = {"key": key, "B": B, "M": M}
         ws["img"] = torch.zeros((B, 1) + tuple(g * p for g, p in zip(self.grid, self.patch)), device=device)
         ws["logits"] = torch.zeros((B, self.K), device=device)
@@ -569,7 +571,7 @@ class Engine(GavikoPaths, PeftPaths):
         return
 
     # ------------------------------------------------------------------ forward
-    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None) -> torch.Tensor:
+    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None, keep_attn: bool = False) -> torch.Tensor:
         L.require_device()
         if not img.is_cuda:
             raise L.GavikoHipError("input volume must be on the HIP device: gaviko_amd has no CPU path")
@@ -578,14 +580,14 @@ class Engine(GavikoPaths, PeftPaths):
                                    f"{self.grid[2] * self.patch[2]}], got {tuple(img.shape)}")
         B = img.shape[0]
         drop = drop or {}
-        sv = {"B": B, "train": train, "attn_drop": float(drop.get("attn_drop", 0.0)), "proj_drop": float(drop.get("proj_drop", 0.0))}
+        sv = {"B": B, "train": train, "keep": train or keep_attn, "attn_drop": float(drop.get("attn_drop", 0.0)), "proj_drop": float(drop.get("proj_drop", 0.0))}
         # nn.Dropout of the backbone itself (vision_transformer.py:33-34,52-54,157; vpt.py:129,148): live for the classes without a
         # train() override (linear / bitfit / fft, melo) and for VPT's prompt_dropout.  bf16 path only.
         sv["bdrop"], sv["edrop"], sv["pdrop"] = (float(drop.get(k, 0.0)) for k in ("dropout", "emb_dropout", "prompt_dropout"))
         if (sv["bdrop"] > 0 or sv["edrop"] > 0 or sv["pdrop"] > 0) and self.kind not in ("vit", "melo", "vpt", "adaptformer", "gaviko", "dvpt", "evp", "ssf"):
             raise L.GavikoHipError(f"backbone dropout > 0 in training mode: unknown kind {self.kind!r}")
         self.refresh_weights(need_dgrad=train)
-        ws = self.workspace(B, img.device, train)
+        ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train)
         if img.data_ptr() != ws["img"].data_ptr():           # a caller that fills input_buffer() itself skips the copy-in launch
             ws["img"].copy_(img.detach())                   # static input buffer (the only per-step host-visible copy-in)
         # unfrozen backbone tensors (`fft` / `bitfit`, train.py:123-137): which ones train, and whether GEMM inputs must be kept
@@ -599,6 +601,8 @@ class Engine(GavikoPaths, PeftPaths):
         if bb:
             self._bb_buffers(ws, B, img.device, sv["wgrad"])
         key = (B, train, sv["attn_drop"], sv["proj_drop"], len(bb), sv["wgrad"], sv["bdrop"], sv["edrop"], sv["pdrop"])
+        if keep_attn and not train:
+            key += ("attn",)                                 # its own workspace: its own launch plan
         self._keep_inputs = bool(sv["wgrad"])
         sv["pre_is_grad"] = self._pre_is_grad = bool(train and self._gelu_grad and not self._keep_inputs and sv["bdrop"] <= 0 and not bb)
         self._fold_on = (not self._keep_inputs) and self._ensure_fold()      # ONE place decides: operands are current whenever the fold is taken
@@ -608,6 +612,20 @@ class Engine(GavikoPaths, PeftPaths):
         if train:
             self._fwd_gen += 1
         return ws["logits"] if self.static_io else ws["logits"].clone()
+
+    def attention_forward(self, img: torch.Tensor):
+        """The deterministic inference forward (no dropout) in a workspace of its own that keeps every layer's qkv / lse -> (logits, ws).
+        The state a pending backward reads (saved activations, their workspace and the per-step decisions of forward()) is put back, so a
+        call between a training forward and its backward leaves that backward's gradients bit-identical."""
+        keep = {k: getattr(self, k) for k in ("_ws", "_saved", "_saved_key", "_keep_inputs", "_pre_is_grad", "_fold_on", "_last_run")
+                if hasattr(self, k)}
+        try:
+            logits = self.forward(img, train=False, drop=None, keep_attn=True)
+            ws = self._ws
+        finally:
+            for k, v in keep.items():
+                setattr(self, k, v)
+        return logits, ws
 
     def input_buffer(self, B: int, device, train: bool = True) -> torch.Tensor:
         """The static [B,1,D,H,W] input slot of the (B, train) workspace: a data pipeline that writes its batch here (and passes this very
@@ -679,7 +697,7 @@ class Engine(GavikoPaths, PeftPaths):
         pending_fix = None
         folded_in = False                                            # this layer's first LayerNorm rides its qkv GEMM (self._fold_ln1)
         for i in range(self.depth):
-            si = i if train else 0
+            si = i if sv["keep"] else 0
             gi, go = (i, i + 1) if train else (i & 1, (i + 1) & 1)
             Mi = B * self.Ts[i]
             repack = self.kind == "vpt" and self.deep
@@ -742,7 +760,7 @@ class Engine(GavikoPaths, PeftPaths):
                 pending_fix = dict(enh=g["enh"], lat=g["xl"], wup=d(pre + ".proj_up.weight"))
                 if fold_next:
                     self._wait(None, "gpa")                          # enh ready
-                    sn = ws["stat"][si + 1 if train else 0]
+                    sn = ws["stat"][si + 1 if sv["keep"] else 0]
                     ops.prompt_up_fix_stats(pending_fix["enh"], pending_fix["lat"], pending_fix["wup"], ws["G"][go], ws["xg16"], ws["spart"],
                                             sn[0], sn[1], B, self.T, self.P, C, self.Lat, pivot=ws["stat"][si][2])
                     pending_fix = None

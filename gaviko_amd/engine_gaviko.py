@@ -40,7 +40,7 @@ class GavikoPaths:
             second = dict(w2=d(gpre + ".proj_down.0.weight"), bias2=d(gpre + ".proj_down.0.bias"), z2=g["zl"], y2=g["ll"], L2=Lt, act2=1)
         if chained and i + 1 < self.depth:                  # layer i+1's norm + proj_down + qkv of the same rows
             nx = f"transformer.local_attns.{(i + 1) // self.share}"
-            mn = ws["mw"][si + 1 if sv["train"] else 0]
+            mn = ws["mw"][si + 1 if sv["keep"] else 0]
             second.update(nx_w=d(nx + ".proj_down.weight"), nx_bias=d(nx + ".proj_down.bias"), nx_ln_gamma=d(nx + ".norm.weight"),
                           nx_ln_beta=d(nx + ".norm.bias"), nx_mean=mn["mean"], nx_rstd=mn["rstd"], nx_lat=mn["lat"], nx_w2=d(nx + ".qkv.weight"),
                           nx_y2=mn["qkv"], nx_L2=3 * Lt, nx_eps=1e-5)

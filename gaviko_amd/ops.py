@@ -413,6 +413,31 @@ def attention_fwd(qkv, out, lse, B, T, H, scale, drop_p=0.0, seed=0, seed_ptr=No
             "gvk_attention_fwd_bf16")
 
 
+def attention_colsum(qkv, lse, w, out, B, T, H, q0=0, q1=None):
+    """out f32 [B,H,T] = sum_{q0 <= i < q1} w[b,i] * P[b,h,i,:] -- the weighted rows of the attention probabilities, recomputed from the
+    bf16 forward's qkv (q block pre-scaled, gvk_attention_fwd_bf16's layout) and lse f32 [B,H,T].  w f32 [B, >= T] (row stride = its last dim)."""
+    q1 = T if q1 is None else q1
+    _chk(qkv, torch.bfloat16, "colsum qkv", pad_rows(B * T) * 3 * H * 64)
+    _chk(lse, torch.float32, "colsum lse", B * H * T)
+    _chk(out, torch.float32, "colsum out", B * H * T)
+    _chk(w, torch.float32, "colsum w", B * T)
+    ld_w = w.shape[-1] if w.dim() == 2 else T
+    if ld_w < T or w.numel() < B * ld_w:
+        raise L.GavikoHipError(f"colsum w: expected [B, >= T] = [{B}, >= {T}], got {tuple(w.shape)}")
+    if not 0 <= q0 < q1 <= T:
+        raise L.GavikoHipError(f"colsum: query rows [{q0}, {q1}) outside [0, {T})")
+    L.check(L.load().gvk_attention_colsum_bf16(L.ptr(qkv), L.ptr(lse), L.ptr(w), ld_w, L.ptr(out), B, T, H, 3 * H * 64, int(q0), int(q1),
+                                               L.stream_ptr()), "gvk_attention_colsum_bf16")
+
+
+def rollout_step(r_in, colsum, r_out, B, T, H):
+    """r_out f32 [B,T] = 0.5 r_in + (0.5 / H) sum_h colsum[:, h] (r_out may be r_in)."""
+    _chk(r_in, torch.float32, "rollout r_in", B * T)
+    _chk(r_out, torch.float32, "rollout r_out", B * T)
+    _chk(colsum, torch.float32, "rollout colsum", B * H * T)
+    L.check(L.load().gvk_rollout_step(L.ptr(r_in), L.ptr(colsum), L.ptr(r_out), B, T, H, L.stream_ptr()), "gvk_rollout_step")
+
+
 def _desc(cls, what, **kw):
     """Fill a descriptor struct: tensors -> device pointers (validated fp32, contiguous, on device), None -> NULL."""
     d = cls()

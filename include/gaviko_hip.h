@@ -256,6 +256,16 @@ size_t gvk_attention_bwd_ws_bytes(int B, int T, int H);
 size_t gvk_attention_bwd_status_offset(size_t ws_bytes);
 int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, void* ws,
                                  size_t ws_bytes, int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream);
+/* attention maps for explanations (csrc/attention_map.hip; what a forward hook on the reference's `attend` softmax sees,
+ * vision_transformer.py:50,67): the probabilities P = softmax(scale q.k^T) of qkv / lse in the layout above, row-weighted and summed --
+ *   out f32 [B][H][T]  out[b][h][j] = sum_{q0 <= i < q1} w[b][i] * P[b][h][i][j]   for j < T (nothing else is written)
+ * w f32 [B][ld_w] (rows outside [q0, q1) are not read), 0 <= q0 < q1 <= T.  P is recomputed against lse, as the backward does.
+ * Deterministic (no atomics).
+ * gvk_rollout_step: one step of attention rollout with mean head fusion and residual weight 0.5 --
+ *   r_out[b][j] = 0.5 * r_in[b][j] + (0.5 / H) * sum_h out[b][h][j]   (heads summed in order; r_out may alias r_in), r f32 [B][T]. */
+int gvk_attention_colsum_bf16(const void* qkv, const float* lse, const float* w, int ld_w, float* out, int B, int T, int H, int ld_qkv,
+                              int q0, int q1, void* stream);
+int gvk_rollout_step(const float* r_in, const float* colsum, float* r_out, int B, int T, int H, void* stream);
 /* gvk_attention_bwd_bf16 when only the FIRST need_rows tokens of every sample carry a consumer (the bottom layer of a frozen backbone: of its
  * input only the prompt rows hold a trainable tensor, gaviko.py:540-548): dq, dk, dv of tokens < need_rows (rounded up to 128) are written --
  * the very bits the full call writes there -- the other rows of dqkv are left untouched; delta is complete. */
