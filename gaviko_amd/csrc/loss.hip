@@ -111,7 +111,8 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs p) {
   if (tid == 0) {
     if (p.reduction != 2) p.loss[0] = loss;
     if (p.meter != nullptr) {                              // train.py:327-328: running_loss += loss * B; num_acc += correct
-      p.meter[0] += loss * (float)p.B;
+      // 'none': loss is already the batch sum (den = 1), so the meter takes it as is -- the mean's loss * B of an unweighted batch
+      p.meter[0] += p.reduction == 2 ? red[0][0] : loss * (float)p.B;
       p.meter[1] += red[2][0];
       p.meter[2] += (float)p.B;
     }

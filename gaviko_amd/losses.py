@@ -19,7 +19,11 @@ from . import ops
 
 
 class StepMeter:
-    """Device-side running sums of an epoch: loss * batch, correct argmax predictions, samples."""
+    """Device-side running sums of an epoch: loss * batch, correct argmax predictions, samples.
+
+    buf[0] gains, per step of B samples: 'mean' -> the reduced loss * B (train.py:327); 'sum' -> the summed loss * B, as train.py's
+    formula does with whatever the criterion returns; 'none' -> the sum of the B per-sample losses, i.e. what 'mean' adds for an
+    unweighted batch with no ignored rows.  read() divides by the samples seen, so under 'mean' and 'none' it gives the mean loss."""
 
     def __init__(self, device):
         self.buf = torch.zeros(3, dtype=torch.float32, device=device)

@@ -868,7 +868,8 @@ LOSS_CE, LOSS_FOCAL = 0, 1
 
 
 def loss_fwd_bwd(logits, target, loss, dlogits, kind, gamma=0.0, eps=1e-16, ignore_index=-100, weights=None, meter=None, reduction="mean"):
-    """loss[0] = criterion(logits, target), dlogits = its gradient, meter += (loss*B, #correct, B): one launch, no host read."""
+    """loss[0] = criterion(logits, target), dlogits = its gradient, meter += (loss*B, #correct, B): one launch, no host read.
+    reduction='none': loss receives the B per-sample values and meter[0] their sum (losses.StepMeter)."""
     _chk(logits, torch.float32, "loss logits")
     B, K = logits.shape
     if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != B:

@@ -1,0 +1,165 @@
+"""CPU: a static ledger of which exported kernel entry points a test calls directly.
+
+The whole-model golden tests run every kernel, but only at a handful of shapes and within loose bf16 bounds; a kernel that is
+subtly wrong can hide there.  This file parses the C ABI (include/gaviko_hip.h), maps every ops.py wrapper -- and every name of the
+thin host modules below -- to the gvk_* symbols it reaches, and collects what the test files call.  The symbols no test reaches
+must equal UNCOVERED exactly: a new kernel without a direct test fails here, and so does a kernel that gained one but is still listed.
+"""
+import ast
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "gaviko_hip.h")
+PKG = os.path.join(ROOT, "gaviko_amd")
+TESTS = os.path.join(ROOT, "tests")
+
+# host modules whose names count as a direct call of the kernels they launch (each is a thin layer over ops / the library)
+HOST_MODULES = ("losses", "metrics", "data", "optim", "explain")
+
+# entry points that are not kernels: runtime, plan recording, queries of sizes and constants
+EXCLUDED = {
+    "gvk_last_error": "error message of the last failed call (read by lib.check)",
+    "gvk_device_check": "device presence probe (lib.require_device)",
+    "gvk_abi_version": "ABI version constant (test_abi)",
+    "gvk_plan_begin": "launch-plan recording (runtime, exercised by the engine's replay tests)",
+    "gvk_plan_end": "launch-plan recording",
+    "gvk_plan_abort": "launch-plan recording",
+    "gvk_plan_size": "launch-plan bookkeeping",
+    "gvk_plan_replay": "launch-plan replay",
+    "gvk_plan_free": "launch-plan bookkeeping",
+    "gvk_plan_event_record": "launch-plan stream events",
+    "gvk_plan_event_record_fenced": "launch-plan stream events",
+    "gvk_plan_event_wait": "launch-plan stream events",
+    "gvk_plan_event_stream_wait": "launch-plan stream events",
+    "gvk_plan_set_timing": "launch-plan timing switch (bench.py)",
+    "gvk_plan_event_elapsed": "launch-plan timing query (bench.py)",
+    "gvk_memset_async": "hipMemsetAsync through the library",
+    "gvk_copy_async": "hipMemcpyAsync through the library",
+    "gvk_gemm_stat_parts": "size query",
+    "gvk_attention_bwd_ws_bytes": "size query",
+    "gvk_attention_bwd_status_offset": "size query",
+    "gvk_param_grads_scratch": "size query",
+    "gvk_gpa_gate_param_count": "size query",
+    "gvk_minmax_partials": "size query",
+}
+
+# kernels that no test calls directly, each with the reason it is left out
+UNCOVERED = {
+    "gvk_attention_fwd_f32": "superseded by gvk_attention_fwd_f32_dropout (drop_p = 0 runs the same kernel); no wrapper calls it",
+    "gvk_attention_bwd_f32": "superseded by gvk_attention_bwd_f32_dropout (drop_p = 0 runs the same kernel); no wrapper calls it",
+}
+
+
+def header_symbols():
+    src = open(HEADER).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    # function declarations only: a return type, the name, an opening parenthesis (struct typedef names never precede "(")
+    return set(re.findall(r"^\s*(?:const\s+)?(?:int|int64_t|size_t|void|char)\s*\*?\s*(gvk_\w+)\s*\(", src, flags=re.M))
+
+
+def _module_reach(path, ops_reach=None):
+    """{top-level name: gvk_* symbols it reaches}: .gvk_* attributes in its body, ops.<wrapper> calls (when ops_reach is given) and the
+    other top-level names of the same module it refers to, closed transitively."""
+    tree = ast.parse(open(path).read())
+    tops = {n.name: n for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
+    direct, refs = {}, {}
+    for name, node in tops.items():
+        syms, r = set(), set()
+        for sub in ast.walk(node):
+            if isinstance(sub, ast.Attribute):
+                if sub.attr.startswith("gvk_"):
+                    syms.add(sub.attr)
+                elif ops_reach is not None and isinstance(sub.value, ast.Name) and sub.value.id == "ops":
+                    syms |= ops_reach.get(sub.attr, set())
+            elif isinstance(sub, ast.Name) and sub.id in tops and sub.id != name:
+                r.add(sub.id)
+        direct[name], refs[name] = syms, r
+    reach = {}
+    for name in tops:
+        seen, todo, syms = {name}, [name], set()
+        while todo:
+            n = todo.pop()
+            syms |= direct[n]
+            for m in refs[n] - seen:
+                seen.add(m)
+                todo.append(m)
+        reach[name] = syms
+    return reach
+
+
+def _test_references(path):
+    """(module, name) pairs a test file uses: `mod.name` with mod imported from gaviko_amd, `from gaviko_amd.mod import name`,
+    and ('lib', gvk_*) for direct library calls."""
+    tree = ast.parse(open(path).read())
+    aliases, used = {}, set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and node.module == "gaviko_amd":
+            for a in node.names:
+                aliases[a.asname or a.name] = a.name
+        elif isinstance(node, ast.ImportFrom) and node.module and node.module.startswith("gaviko_amd."):
+            mod = node.module.split(".", 1)[1]
+            for a in node.names:
+                used.add((mod, a.name))
+        elif isinstance(node, ast.Import):
+            for a in node.names:
+                if a.name.startswith("gaviko_amd.") and a.asname:
+                    aliases[a.asname] = a.name.split(".", 1)[1]
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Attribute):
+            if node.attr.startswith("gvk_"):
+                used.add(("lib", node.attr))
+            elif isinstance(node.value, ast.Name) and node.value.id in aliases:
+                used.add((aliases[node.value.id], node.attr))
+    return used
+
+
+def coverage():
+    ops_reach = _module_reach(os.path.join(PKG, "ops.py"))
+    reach = {"ops": ops_reach}
+    for m in HOST_MODULES:
+        reach[m] = _module_reach(os.path.join(PKG, m + ".py"), ops_reach)
+    covered = set()
+    for f in sorted(os.listdir(TESTS)):
+        if f.startswith("test_") and f.endswith(".py"):
+            for mod, name in _test_references(os.path.join(TESTS, f)):
+                if mod == "lib":
+                    covered.add(name)
+                elif mod in reach:
+                    covered |= reach[mod].get(name, set())
+    return covered
+
+
+def test_header_parse_is_sane():
+    syms = header_symbols()
+    assert len(syms) > 100
+    for s in ("gvk_gemm_nt_bf16", "gvk_ssf_colgrad", "gvk_loss_fwd_bwd", "gvk_plan_replay", "gvk_attention_bwd_ws_bytes"):
+        assert s in syms
+    assert not any(s.endswith("_desc") or s.endswith("_job") or s.endswith("_outer") for s in syms)
+
+
+def test_every_listed_symbol_exists():
+    syms = header_symbols()
+    assert not set(EXCLUDED) - syms, f"exclusions that are not exported: {sorted(set(EXCLUDED) - syms)}"
+    assert not set(UNCOVERED) - syms, f"allow-list entries that are not exported: {sorted(set(UNCOVERED) - syms)}"
+    assert not set(EXCLUDED) & set(UNCOVERED)
+
+
+def test_wrappers_reach_the_library():
+    ops_reach = _module_reach(os.path.join(PKG, "ops.py"))
+    assert ops_reach["colsum_any"] == {"gvk_ssf_colgrad"}
+    assert ops_reach["transpose_any"] == {"gvk_transpose_f32", "gvk_transpose_bf16"}
+    assert ops_reach["to_operand"] >= {"gvk_cast_f32_bf16", "gvk_copy_async"}
+    syms = header_symbols()
+    for name, s in ops_reach.items():
+        assert s <= syms, f"ops.{name} calls symbols the header does not export: {sorted(s - syms)}"
+
+
+def test_uncovered_kernels_match_the_allow_list():
+    kernels = header_symbols() - set(EXCLUDED)
+    untested = kernels - coverage()
+    new = sorted(untested - set(UNCOVERED))
+    stale = sorted(set(UNCOVERED) - untested)
+    assert not new, f"kernels with no direct test (add one, or list them in UNCOVERED with a reason): {new}"
+    assert not stale, f"kernels listed in UNCOVERED that a test now calls (remove them from the list): {stale}"
