@@ -17,30 +17,22 @@ Reference call structure mirrored here: gaviko.py:291-306 (layer loop), 531-552 
 """
 from __future__ import annotations
 
-import math
+import os
 from typing import Dict, List, Optional
 
 import torch
 
 from . import lib as L
 from . import ops
-
-import os
-
-from .engine_common import (SEED_EMB, SEED_LAYER, SEED_PROMPT, GRAPH_WARMUP, Names, PLAN_TIMING, SIDE_STREAM_PRIORITY, STEP_MODE, USE_GRAPHS, _ABLATE, _EPI_NAMES, _FIX_IN_LN, _LOC_SHIFT, _MODE, _SIDE_STREAMS, _on, evp_highpass_operator)  # noqa: F401
+from .engine_common import (GRAPH_WARMUP, PLAN_TIMING, SEED_EMB, SEED_LAYER, SEED_PROMPT, USE_GRAPHS, _ABLATE, _EPI_NAMES, _SIDE_STREAMS, Names,
+                            _on)
+from .engine_common import evp_highpass_operator  # noqa: F401  (re-exported: tests import it from here)
 from .engine_gaviko import GavikoPaths
 from .engine_peft import PeftPaths
 
-# bench.py instrumentation: when a dict, every GEMM launch is bracketed by HIP events recorded on the launch stream
 # bench.py instrumentation: when set to a dict, plans recorded from then on bracket every GEMM launch (and the patch-embed
 # stage) with timestamped plan events, so the kernels are timed inside the real three-stream schedule of a replayed step.
 GEMM_MARKS = None
-# the bf16 attention backward as ONE pass (csrc/attention_bwd.hip::attn_bwd_fused_kernel, round 5): built, bit-compatible, and 5 % slower
-# than the two passes at T = 1033 -- the two-pass kernels stay the path; GAVIKO_HIP_ATTN_BWD=fused (measurement build) is the A/B
-_ATTN_FUSED = L.diag_env("GAVIKO_HIP_ATTN_BWD", "2pass") == "fused"
-# the K loops of the strided-panel GEMMs (dead-row pruning) cut into pieces over idle CUs (gvk_gemm_desc.splitk_ws): +0.4 % on the step, but the
-# sum of partial sums is no longer the bit pattern the full-size GEMM produces -- off, so that pruning stays bit-identical (measurement build: =1)
-_PANEL_SPLITK = L.diag_env("GAVIKO_HIP_PANEL_SPLITK", "0") == "1"
 
 
 # classes whose backbone tensors can train (engine_peft.py `_bb_*`): the plain ViT (`fft` / `bitfit`); every class that freezes by default, with freeze_vit=False
@@ -136,9 +128,8 @@ class Engine(GavikoPaths, PeftPaths):
         # GPA projections of backbone rows ride along in the backbone's LayerNorm kernels (gvk_layernorm_*_proj)
         self._fuse_proj = (kind == "gaviko" and not self.fp32 and ops.rowproj_supported(self.Lat, dim)
                            and L.diag_env("GAVIKO_HIP_FUSE_PROJ", "1") != "0")
-        # backward only: dcomb = dG . W_up inside the LayerNorm-1 backward on the main stream ("main"), or by the GPA stream's own projection
-        # kernel in front of its backward core ("gpa": one more 12.7 MB read there, a plain LayerNorm backward here)
-        self._proj_bwd_main = self._fuse_proj and L.diag_env("GAVIKO_HIP_PROJ_BWD", "main") != "gpa"
+        # In the backward, the LayerNorm-1 backward of layer i > 0 also leaves dcomb = dG . W_up for the GPA core of layer i - 1 (computing it
+        # on the GPA stream instead was measured slower and removed: DESIGN.md 7e).
         # Rows nobody consumes are not computed (round 5).  With a frozen backbone the loss reads the LAST layer's output only at the rows
         # the head pools (prompts + CLS, gaviko.py:316), so that layer's MLP -- a row-wise function -- runs on those rows in the forward, and
         # its backward (fc2 / fc1 dgrad, LayerNorm 2) on the same rows: every other row of the incoming gradient is an exact zero.  At the
@@ -415,8 +406,6 @@ class Engine(GavikoPaths, PeftPaths):
             ws["dctx"] = z(M, C, bf16)
             ws["dqkv"] = z(M, 3 * C, bf16)
             ws["delta"] = torch.zeros((B, self.heads, T), device=device)
-            if not self.fp32 and _ATTN_FUSED:                                     # one-pass attention backward: progress words + running dQ sums
-                ws["attn_ws"] = ops.attention_bwd_workspace(B, T, self.heads, device)
             if self.kind == "gaviko":
                 Lt, P, BN = self.Lat, self.P, B * N
                 mk = lambda *s: torch.zeros(s, device=device)
@@ -472,8 +461,7 @@ class Engine(GavikoPaths, PeftPaths):
                 return st
             # (confining the side streams to a CU subset with hipExtStreamCreateWithCUMask was measured: 676 -> 170-260 volumes/s for
             #  every mask shape tried -- masked queues are far slower to dispatch on this runtime)
-            prio = int(L.diag_env(f"GAVIKO_HIP_{name.upper()}_PRIORITY", SIDE_STREAM_PRIORITY))     # per-stream A/B switch (diag)
-            st = self._streams[name] = _SIDE_STREAMS[key] = torch.cuda.Stream(priority=prio)
+            st = self._streams[name] = _SIDE_STREAMS[key] = torch.cuda.Stream()
             if "sidenop" in _ABLATE or f"{name}nop" in _ABLATE:
                 L.load().gvk_plan_nop_stream(st.cuda_stream)
         return st
@@ -694,7 +682,6 @@ class Engine(GavikoPaths, PeftPaths):
                         pre, _ = self._gpa_names(i + 1)
                         ops.pack_split_bf16(d(pre + ".proj_up.weight"), self._w16[f"fc2{i + 1}"], self.mlp, C, b=d(pre + ".proj_up.bias"), weight_side=True)
             side_weights(-1)                                         # (layer 0's operand)
-        pending_fix = None
         folded_in = False                                            # this layer's first LayerNorm rides its qkv GEMM (self._fold_ln1)
         for i in range(self.depth):
             si = i if sv["keep"] else 0
@@ -714,11 +701,7 @@ class Engine(GavikoPaths, PeftPaths):
             self._mark(f"f{i}:start")
             if self.kind == "evp":
                 self._evp_add_prompt(ws, i, si, ws["G"][gi], B)               # x[:, 1:] += prompt_i (evp.py:235-238)
-            if gaviko and pending_fix is not None:
-                self._wait(None, "gpa")                              # the previous layer's enh
-            self._attn_block_fwd(ws, i, si, ws["G"][gi], ws["G1"][si], Mi, sv["bdrop"], fix=pending_fix if gaviko and _on("noside") else None,
-                                 folded=folded_in)
-            pending_fix = None
+            self._attn_block_fwd(ws, i, si, ws["G"][gi], ws["G1"][si], Mi, sv["bdrop"], folded=folded_in)
             self._mark(f"f{i}:attn")
             fused = gaviko and self._fuse_proj
             if gaviko and not fused:
@@ -739,7 +722,7 @@ class Engine(GavikoPaths, PeftPaths):
                     self._gpa_fwd_latents(ws, i, si, ws["G1"][si], ws["Lc"][go], M, B, False)
                 side_weights(i)
             up_in_fc2 = gaviko and fused and fuse_up
-            fold_next = bool(up_in_fc2 and self._fold_on and i + 1 < self.depth and _on("noside") and not _FIX_IN_LN)
+            fold_next = bool(up_in_fc2 and self._fold_on and i + 1 < self.depth and _on("noside"))
             # fc2 carries proj_up of the PLAIN latents of every row (ready right behind the LayerNorm); the GPA has the two GEMMs' time
             # to finish, and only the P prompt rows it replaces are fixed up afterwards
             # the last layer's output is read at the pooled rows only (frozen backbone, no dropout behind fc2): its MLP runs on those rows
@@ -753,22 +736,17 @@ class Engine(GavikoPaths, PeftPaths):
                 self._dvpt_fwd_up(ws, i, si, gout, Mi)
             self._mark(f"f{i}:mlp")
             if gaviko and up_in_fc2:
-                # the P prompt rows still lack (enh - xl) . Wup^T: the next layer's first LayerNorm applies it on the way in (one launch less
-                # on this stream); the last layer has no successor and launches the 128-row fix itself
+                # the P prompt rows still lack (enh - xl) . Wup^T; when the next layer's first LayerNorm is folded into its qkv GEMM, the
+                # fix also turns the fc2 GEMM's row partials into that LayerNorm's mean / rstd
                 pre, _ = self._gpa_names(i)
                 g = ws["gp"][si]
-                pending_fix = dict(enh=g["enh"], lat=g["xl"], wup=d(pre + ".proj_up.weight"))
+                self._wait(None, "gpa")                              # enh ready
                 if fold_next:
-                    self._wait(None, "gpa")                          # enh ready
                     sn = ws["stat"][si + 1 if sv["keep"] else 0]
-                    ops.prompt_up_fix_stats(pending_fix["enh"], pending_fix["lat"], pending_fix["wup"], ws["G"][go], ws["xg16"], ws["spart"],
+                    ops.prompt_up_fix_stats(g["enh"], g["xl"], d(pre + ".proj_up.weight"), ws["G"][go], ws["xg16"], ws["spart"],
                                             sn[0], sn[1], B, self.T, self.P, C, self.Lat, pivot=ws["stat"][si][2])
-                    pending_fix = None
-                elif i + 1 == self.depth or not _FIX_IN_LN:
-                    self._wait(None, "gpa")                          # enh ready
-                    if _on("noside"):
-                        ops.prompt_up_fix(pending_fix["enh"], pending_fix["lat"], pending_fix["wup"], ws["G"][go], B, self.T, self.P, C, self.Lat)
-                    pending_fix = None
+                elif _on("noside"):
+                    ops.prompt_up_fix(g["enh"], g["xl"], d(pre + ".proj_up.weight"), ws["G"][go], B, self.T, self.P, C, self.Lat)
                 folded_in = fold_next
             elif gaviko:
                 self._wait(None, "gpa")                              # enh ready
@@ -814,7 +792,7 @@ class Engine(GavikoPaths, PeftPaths):
         if sv["pdrop"] > 0:
             ops.dropout_rows(g, sv["pdrop"], SEED_PROMPT + i, ws["seed"], out32=g, M=sv["B"] * self.P, N=self.C, rows_in=self.P, rows_out=T, row_off=1)
 
-    def _attn_block_fwd(self, ws, i, si, gin, g1, M, pdrop=0.0, fix=None, folded=False):
+    def _attn_block_fwd(self, ws, i, si, gin, g1, M, pdrop=0.0, folded=False):
         nm, w, d, C = self.names, self._w16, self._d, self.C
         a = nm.attn(i)
         st = ws["stat"][si]
@@ -829,11 +807,7 @@ class Engine(GavikoPaths, PeftPaths):
             self._gemm(ws["ctx"][si], w[f"out{i}"], M, g1, epilogue=ops.EPI_BIAS_RES_F32, bias=d(a + ".to_out.0.bias"), res=gin,
                        drop_p=pdrop, seed=SEED_LAYER + 8 * i + 1, seed_ptr=ws["seed"])
             return
-        if fix is not None:                                  # + the previous layer's GPA prompt fix, applied to gin in place
-            ops.layernorm_fwd_fix(gin, d(a + ".norm.weight"), d(a + ".norm.bias"), M, C, y16=ws["xn"], mean=st[0], rstd=st[1], T=self.T, P=self.P,
-                                  L_=self.Lat, **fix)
-        else:
-            ops.layernorm_fwd(gin, d(a + ".norm.weight"), d(a + ".norm.bias"), M, C, y16=ws["xn"], mean=st[0], rstd=st[1])
+        ops.layernorm_fwd(gin, d(a + ".norm.weight"), d(a + ".norm.bias"), M, C, y16=ws["xn"], mean=st[0], rstd=st[1])
         if self._keep_inputs:
             ops.copy_(ws["sav"]["xn1"][si], ws["xn"])
         # bf16 path: the q block leaves the projection as q * scale * log2(e) (one rounding, in the GEMM epilogue) -- the form the flash
@@ -863,13 +837,7 @@ class Engine(GavikoPaths, PeftPaths):
         """gemm_nt kwargs that restrict a launch to the first `rows` rows of every sample (64-row tiles at stride T), or {}."""
         if not self.prune_dead_rows or rows > 64 or self.T < 64:
             return {}
-        kw = dict(m_panels=B, m_stride=self.T)
-        if _PANEL_SPLITK:
-            ws = self._ws
-            if "gemm_ws" not in ws:                          # 256 ticket words + up to 256 partial tiles of 32 KiB
-                ws["gemm_ws"] = torch.zeros((1024 + 256 * 32768) // 4, dtype=torch.int32, device=ws["logits"].device)
-            kw["splitk_ws"] = ws["gemm_ws"]
-        return kw
+        return dict(m_panels=B, m_stride=self.T)
 
     def _mlp_block_fwd(self, ws, i, si, g1, gout, M, train, pdrop=0.0, up_in_fc2=False, stats_out=False, panels=None):
         nm, w, d, C = self.names, self._w16, self._d, self.C
@@ -1033,8 +1001,8 @@ class Engine(GavikoPaths, PeftPaths):
         the local-stream gradient ping-pongs with the layer parity."""
         if first:
             self._mwsa_pending = None
-        nm, w, d = self.names, self._w16, self._d
-        B, C, T, M = sv["B"], self.C, self.T, sv["B"] * self.T
+        d = self._d
+        B, C, T = sv["B"], self.C, self.T
         gaviko = self.kind == "gaviko"
         if first:
             self._mark("b:begin")
@@ -1049,163 +1017,47 @@ class Engine(GavikoPaths, PeftPaths):
             loc, gpa = self._stream("loc"), self._stream("gpa")
             self._wait("gpa", None)
             self._wait("loc", None)
+        bb = sv.get("bb") or ()
+        # frozen backbone: the fc1 / qkv dgrad GEMMs hand the LayerNorm backward its input gradient in bf16 (self._dy16)
+        dy16 = bool(self._dy16 and not bb and not sv["wgrad"])
+        # Dead rows of a frozen backbone (prune_dead_rows).  Top layer (the first of the sweep): the incoming gradient is an exact zero outside
+        # the rows the head pools, so its MLP backward (row-wise) runs on those rows.  Bottom layer (the last of the sweep): of its INPUT gradient
+        # only the P prompt rows of every sample are read (prompt_embeddings and their position embedding; patch embedding, cls token and
+        # pos_embedding carry none), so its qkv dgrad and LayerNorm-1 backward run on those rows.
+        frozen = gaviko and not bb and sv.get("bdrop", 0.0) <= 0 and not sv["wgrad"]
+        top = self._panels(B, sum(self._pool_rows())) if (frozen and first) else {}
+        bot = self._panels(B, self.P) if (frozen and last and self.P > 0) else {}
         prev_scl = None
         for i in range(hi, lo - 1, -1):
             M = B * self.Ts[i]
             T = self.Ts[i]
             par = (self.depth - 1 - i) & 1
-            m, a = nm.mlp(i), nm.attn(i)
-            st = ws["stat"][i]
             # GPA stream: the critical kernels (-> dzx, dzl) first, then the parameter gradients; the other streams wait only
             # for the event between the two
             if gaviko:
                 with torch.cuda.stream(gpa):
                     # dcomb = dGout . W_up was produced by the LayerNorm backward that wrote dGout, except for the top layer
-                    self._gpa_bwd_core(ws, sv, gv, i, dGout, M, B, par, project=not (self._proj_bwd_main and i < self.depth - 1))
+                    self._gpa_bwd_core(ws, sv, gv, i, dGout, M, B, par, project=not self._fuse_proj or i == self.depth - 1)
                     dz_ready = self._ev_record(gpa)
                     self._gpa_bwd_params(ws, sv, gv, i, dGout, M, B, par)
                     self._bucket_mark("gpa", i)                              # prompt_projs.{i // share} gradients final once the lowest layer using it is done
-            # main stream, MLP block: dG1 = dGout + LN'(fc1^T(GELU'(pre) * fc2^T(dGout)))
             self._mark(f"b{i}:start")
-            bb = sv.get("bb") or ()
-            pd_ = sv.get("bdrop", 0.0)
-            dy_ff = dGout
-            if pd_ > 0:                                                      # gradient of dropout(fc2(.)): the forward's mask on dGout
-                dy_ff = self._masked_grad(ws, dGout, pd_, SEED_LAYER + 8 * i + 3, bool(bb) or self.kind == "ssf", M)
-            if bb:                                                           # fc2: db = colsum(dGout), dW = dGout^T . act
-                self._bb_linear_grads(ws, gv, bb, m + ".net.4", dy_ff, ws["dG16"], ws["sav"]["act"][i] if sv["wgrad"] else None, M, C, self.mlp,
-                                      ldx=self.ldx if self.ldx != self.mlp else None)
-            dvpt = self.kind == "dvpt"
-            if dvpt:
-                self._dvpt_bwd_latents(ws, gv, i, dGout, M, B)
-            ssf = self.kind == "ssf"
-            if ssf:                                                          # fc2 + ssf_2: dy = dGout, y = G[i+1] - G1[i]
-                # (behind a live dropout the stored difference is kept / (1 - p): masked gradient, y_mul = 1 - p)
-                self._ssf_linear_grad(ws, gv, m, 2, dy_ff, ws["G"][i + 1], M, C, y1=ws["G1"][i], y_mul=1.0 - pd_)
-            # top layer, frozen backbone: the incoming gradient is an exact zero outside the rows the head pools -- the MLP's backward (row-wise)
-            # runs on those rows; the rest of dG1 is zeroed in one memset instead of being computed as LN'(0) + 0
-            top = (self._panels(B, self._pool_rows()[0] + self._pool_rows()[1])
-                   if (gaviko and first and i == self.depth - 1 and not bb and pd_ <= 0 and not sv["wgrad"]) else {})
-            self._gemm(ws["dG16"], w[f"fc2{i}_t"], M, ws["dpre"], epilogue=ops.EPI_GELU_BWD_BF16, aux=ws["pre"][i], ldaux=self.ldx,
-                       drop_p=pd_, seed=SEED_LAYER + 8 * i + 2, seed_ptr=ws["seed"], aux_is_grad=int(sv.get("pre_is_grad", False)), **top)
-            if ssf:                                                          # fc1 + ssf_1: dy = d(pre-activation), y = saved pre-activation
-                self._ssf_linear_grad(ws, gv, m, 1, ws["dpre"], ws["pre"][i], M, self.mlp)
-            if bb:                                                           # fc1: db = colsum(dpre), dW = dpre^T . LN2(G1)
-                self._bb_linear_grads(ws, gv, bb, m + ".net.1", ws["dpre"], ws["dpre"], ws["sav"]["xn2"][i] if sv["wgrad"] else None, M, self.mlp, C)
-            self._mark(f"b{i}:fc2d") if False else None
-            fuse_scatter = (gaviko and self._fuse_local and not self.fp32 and "noside" not in _ABLATE
-                            and L.diag_env("GAVIKO_HIP_FUSE_SCATTER", "0") == "1")     # measured: 651 vs 676 volumes/s -- off
-            dy16 = bool(self._dy16 and not bb and not sv["wgrad"] and not fuse_scatter)
-            if dy16:
-                self._gemm(ws["dpre"], w[f"fc1{i}_t"], M, ws["dx16b"], epilogue=ops.EPI_STORE_BF16, **top)
-            else:
-                self._gemm(ws["dpre"], w[f"fc1{i}_t"], M, ws["dx32"], epilogue=ops.EPI_STORE_F32, **top)
-            self._mark(f"b{i}:fc1d")
-            if bb:
-                self._bb_ln_grads(ws, gv, bb, m + ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
-            if ssf:                                                          # LN2 + ssf_0
-                self._ssf_ln_grad(ws, gv, m, ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
-            adapter = self.kind == "adaptformer"
-            if fuse_scatter:
-                # dG1 = dGout + LN'(dx32) + dzx . W_d (+ the bf16 operand of the out-proj dgrad) in ONE pass: the GPA core of this layer
-                # (started at the top of the layer on its own stream) has long finished when the two MLP dgrad GEMMs are through
-                self._ev_wait(torch.cuda.current_stream(), dz_ready)
-                gpre, _ = self._gpa_names(i)
-                ops.layernorm_bwd_up(ws["dx32"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout, dx16=ws["dG16"],
-                                     lat=ws["bw"]["dzx"], w=d(gpre + ".proj_down.0.weight"), L_=self.Lat, w_layout=1)
-            elif top:
-                ops.memset_zero(dGin)
-                if dy16:
-                    ops.layernorm_bwd_dy16(ws["dx16b"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout,
-                                           rows=(B, self._pool_rows()[0] + self._pool_rows()[1], T))
-                else:
-                    ops.layernorm_bwd_rows(ws["dx32"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), B, self._pool_rows()[0] + self._pool_rows()[1],
-                                           T, C, dx=dGin, dres=dGout)
-            elif dy16:
-                ops.layernorm_bwd_dy16(ws["dx16b"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout)
-            else:
-                ops.layernorm_bwd(ws["dx32"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout,
-                                  dx16=None if (gaviko or adapter or dvpt) else ws["dG16"])
-            if dvpt:
-                self._dvpt_bwd_scatter(ws, i, dGin, M)                       # dG1 += (dz . Wd) * QuickGELU'(G1)  (+ operand copy)
-            if adapter:
-                self._adapter_bwd(ws, gv, i, dGout, dGin, M, refresh_operand=pd_ > 0)   # adds LN_a'(...) into dG1 and refreshes dG16
+            self._mlp_block_bwd(ws, sv, gv, i, dGout, dGin, dy16, top if i == self.depth - 1 else {})
             self._mark(f"b{i}:ln2")
             if gaviko:
-                if not fuse_scatter:
-                    self._ev_wait(torch.cuda.current_stream(), dz_ready)
-                    self._gpa_bwd_scatter_g(ws, i, dGin, M)                  # dG1 += dzx.Wd (+ bf16 copy)
+                self._ev_wait(torch.cuda.current_stream(), dz_ready)
+                self._gpa_bwd_scatter_g(ws, i, dGin, M)                      # dG1 += dzx.Wd (+ bf16 copy)
                 self._mark(f"b{i}:scatter")
                 # The MWSA chain of this layer (~170 us of kernels against ~290 us of backbone work per layer) runs beside the attention
-                # backward, which it slows by 21 % (tools/plan_marks.py, locnop ablation); GAVIKO_HIP_LOC_SHIFT=1 holds it back until that
-                # is through (not a gain, see _LOC_SHIFT)
-                shift = _LOC_SHIFT and i > lo
-                if not shift:
-                    self._mwsa_chain_bwd(ws, sv, gv, i, par, B, loc, dz_ready)
-            # main stream, attention block: dG0 = dG1 + LN'(qkv^T(attn'(out^T(dG1))))
-            dy_at = dGin
-            if pd_ > 0:                                                      # gradient of dropout(to_out(.))
-                dy_at = self._masked_grad(ws, dGin, pd_, SEED_LAYER + 8 * i + 1, bool(bb) or ssf, M)
-            if ssf:                                                          # to_out + ssf_2: dy = dG1, y = G1[i] - G[i]
-                self._ssf_linear_grad(ws, gv, a, 2, dy_at, ws["G1"][i], M, C, y1=ws["G"][i], y_mul=1.0 - pd_)
-            if bb:                                                           # to_out: db = colsum(dG1), dW = dG1^T . ctx
-                self._bb_linear_grads(ws, gv, bb, a + ".to_out.0", dy_at, ws["dG16"], ws["ctx"][i], M, C, C)
-            self._gemm(ws["dG16"], w[f"out{i}_t"], M, ws["dctx"], epilogue=ops.EPI_STORE_BF16)
-            self._mark(f"b{i}:outd")
-            # (bottom layer of a frozen backbone: only dq / dk / dv of the prompt rows are read -- by the row-panel qkv dgrad below)
-            rows0 = self.P if (gaviko and last and i == 0 and not bb and pd_ <= 0 and not sv["wgrad"] and self._panels(B, self.P)) else None
-            ops.attention_bwd(ws["qkv"][i], ws["ctx"][i], ws["dctx"], ws["lse"][i], ws["delta"], ws["dqkv"], B, T, self.heads, 64 ** -0.5,
-                              drop_p=pd_, seed=SEED_LAYER + 8 * i, seed_ptr=ws["seed"], q_prescaled=True,
-                              ws=ws.get("attn_ws") if (_ATTN_FUSED and rows0 is None) else None, need_rows=rows0)
-            self._mark(f"b{i}:attnb")
-            if gaviko and shift:
-                self._mwsa_chain_bwd(ws, sv, gv, i, par, B, loc, self._ev_record(torch.cuda.current_stream()))
-            if self.kind == "melo" and i in self.lora_layers:
-                self._melo_bwd(ws, gv, i, M)
-            if ssf:                                                          # to_qkv + ssf_1: dy = dqkv, y = saved qkv
-                uq = {} if self.fp32 else dict(y0_cols=self.heads * 64, y0_mul=1.0 / self.q_scale)     # the saved q block is pre-scaled
-                self._ssf_linear_grad(ws, gv, a, 1, ws["dqkv"], ws["qkv"][i], M, 3 * C, **uq)
-            if bb:                                                           # to_qkv (bias-free): dW = dqkv^T . LN1(G)
-                self._bb_linear_grads(ws, gv, bb, a + ".to_qkv", None, ws["dqkv"], ws["sav"]["xn1"][i] if sv["wgrad"] else None, M, 3 * C, C)
-            # bottom layer, frozen backbone: of this layer's INPUT gradient only the P prompt rows of every sample are read (prompt_embeddings and
-            # their position embedding; patch embedding, cls token and pos_embedding carry none) -- qkv dgrad and LayerNorm 1 on those rows
-            bot = (self._panels(B, self.P) if (gaviko and last and i == 0 and not bb and pd_ <= 0 and not sv["wgrad"] and self.P > 0) else {})
-            if dy16:
-                self._gemm(ws["dqkv"], w[f"qkv{i}_t"], M, ws["dx16b"], epilogue=ops.EPI_STORE_BF16, **bot)
-            else:
-                self._gemm(ws["dqkv"], w[f"qkv{i}_t"], M, ws["dx32"], epilogue=ops.EPI_STORE_F32, **bot)
-            if bb:
-                self._bb_ln_grads(ws, gv, bb, a + ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
-            if ssf:                                                          # LN1 + ssf_0
-                self._ssf_ln_grad(ws, gv, a, ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
-            self._mark(f"b{i}:qkvd")
+                # backward, which it slows by 21 % (tools/plan_marks.py, locnop ablation); holding it back until that is through was
+                # measured slower and removed
+                self._mwsa_chain_bwd(ws, sv, gv, i, par, B, loc, dz_ready)
+            # The new boundary gradient of GAViKO goes to the OTHER parity buffer: the GPA parameter kernels of this layer keep reading
+            # dGout off the critical path.  The buffer being overwritten was last read by layer i+1's parameter kernels, which precede this
+            # layer's dz_ready in the GPA stream -- and the main stream has already waited for that above.
             if gaviko:
-                # The new boundary gradient goes to the OTHER parity buffer: the GPA parameter kernels of this layer keep reading
-                # dGout off the critical path.  The buffer being overwritten was last read by layer i+1's parameter kernels, which
-                # precede this layer's dz_ready in the GPA stream -- and the main stream has already waited for that above.
-                dGnext = ws["dGb"] if dGout is ws["dG"][0] else ws["dG"][0]
-                if dy16:
-                    g1 = d(a + ".norm.weight")
-                    if self._proj_bwd_main and i > 0:
-                        pre_lo, _ = self._gpa_names(i - 1)
-                        ops.layernorm_bwd_dy16(ws["dx16b"], ws["G"][i], st[0], st[1], g1, M, C, dx=dGnext, dres=dGin, dx16=ws["dG16"],
-                                               proj=dict(w=d(pre_lo + ".proj_up.weight"), y=ws["bw"]["dcomb"], w_layout=1, L_=self.Lat))
-                    elif bot:
-                        ops.layernorm_bwd_dy16(ws["dx16b"], ws["G"][i], st[0], st[1], g1, M, C, dx=dGnext, dres=dGin, rows=(B, self.P, T))
-                    else:
-                        ops.layernorm_bwd_dy16(ws["dx16b"], ws["G"][i], st[0], st[1], g1, M, C, dx=dGnext, dres=dGin, dx16=ws["dG16"])
-                elif self._proj_bwd_main and i > 0:
-                    pre_lo, _ = self._gpa_names(i - 1)
-                    ops.layernorm_bwd_proj(ws["dx32"], ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, C, dx=dGnext, dres=dGin,
-                                           dx16=ws["dG16"], w=d(pre_lo + ".proj_up.weight"), y=ws["bw"]["dcomb"], w_layout=1, L_=self.Lat)
-                elif bot:
-                    ops.layernorm_bwd_rows(ws["dx32"], ws["G"][i], st[0], st[1], d(a + ".norm.weight"), B, self.P, T, C, dx=dGnext, dres=dGin)
-                else:
-                    ops.layernorm_bwd(ws["dx32"], ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, C, dx=dGnext, dres=dGin,
-                                      dx16=ws["dG16"])
-                dGout = dGnext
-            else:
-                ops.layernorm_bwd(ws["dx32"], ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, C, dx=dGout, dres=dGin, dx16=ws["dG16"])
+                dGout = ws["dGb"] if dGout is ws["dG"][0] else ws["dG"][0]
+            self._attn_block_bwd(ws, sv, gv, i, dGin, dGout, dy16, bot if i == 0 else {})
             if gaviko:
                 # The MWSA chain never feeds the global stream in the backward, so the main stream does not join it per layer: dzl
                 # is double-buffered by layer parity and the only cross-stream hazard left is layer i-1's GPA rewriting the buffer
@@ -1216,7 +1068,7 @@ class Engine(GavikoPaths, PeftPaths):
                 self._wait("gpa", None)                                      # the next layer's GPA backward needs this dG[i]
             if self.kind == "evp":
                 self._evp_bwd_layer(ws, gv, i, dGout, B)
-            if ssf and bb:
+            if self.kind == "ssf" and bb:
                 self._ssf_unfold(gv, bb, self._ssf_sites()[1 + 6 * i: 7 + 6 * i])     # this layer's six sites, before its bucket is final
             self._mark(f"b{i}:end")
             if not gaviko:
@@ -1269,6 +1121,103 @@ class Engine(GavikoPaths, PeftPaths):
         if last:
             self._bucket_mark("main", -1)                                    # everything else (prompts, head, unindexed tensors): end of the sweep
         self._mark("b:tail")                                                 # side streams joined, embedding-side gradients issued
+
+    def _mlp_block_bwd(self, ws, sv, gv, i, dGout, dGin, dy16, top):
+        """Main stream, MLP block of layer i: dGin = dGout + LN2'(fc1^T(GELU'(pre) * fc2^T(dGout))), with the method's own gradients of the
+        block in launch order.  top: _panels kwargs that restrict the block to the rows the head pools (frozen top layer), or {}."""
+        w, d, C = self._w16, self._d, self.C
+        B, T = sv["B"], self.Ts[i]
+        M, m, st = B * T, self.names.mlp(i), ws["stat"][i]
+        bb, pd_ = sv.get("bb") or (), sv.get("bdrop", 0.0)
+        dvpt, ssf = self.kind == "dvpt", self.kind == "ssf"
+        dy_ff = dGout
+        if pd_ > 0:                                                          # gradient of dropout(fc2(.)): the forward's mask on dGout
+            dy_ff = self._masked_grad(ws, dGout, pd_, SEED_LAYER + 8 * i + 3, bool(bb) or ssf, M)
+        if bb:                                                               # fc2: db = colsum(dGout), dW = dGout^T . act
+            self._bb_linear_grads(ws, gv, bb, m + ".net.4", dy_ff, ws["dG16"], ws["sav"]["act"][i] if sv["wgrad"] else None, M, C, self.mlp,
+                                  ldx=self.ldx if self.ldx != self.mlp else None)
+        if dvpt:
+            self._dvpt_bwd_latents(ws, gv, i, dGout, M, B)
+        if ssf:                                                              # fc2 + ssf_2: dy = dGout, y = G[i+1] - G1[i]
+            # (behind a live dropout the stored difference is kept / (1 - p): masked gradient, y_mul = 1 - p)
+            self._ssf_linear_grad(ws, gv, m, 2, dy_ff, ws["G"][i + 1], M, C, y1=ws["G1"][i], y_mul=1.0 - pd_)
+        self._gemm(ws["dG16"], w[f"fc2{i}_t"], M, ws["dpre"], epilogue=ops.EPI_GELU_BWD_BF16, aux=ws["pre"][i], ldaux=self.ldx,
+                   drop_p=pd_, seed=SEED_LAYER + 8 * i + 2, seed_ptr=ws["seed"], aux_is_grad=int(sv.get("pre_is_grad", False)), **top)
+        if ssf:                                                              # fc1 + ssf_1: dy = d(pre-activation), y = saved pre-activation
+            self._ssf_linear_grad(ws, gv, m, 1, ws["dpre"], ws["pre"][i], M, self.mlp)
+        if bb:                                                               # fc1: db = colsum(dpre), dW = dpre^T . LN2(G1)
+            self._bb_linear_grads(ws, gv, bb, m + ".net.1", ws["dpre"], ws["dpre"], ws["sav"]["xn2"][i] if sv["wgrad"] else None, M, self.mlp, C)
+        self._gemm(ws["dpre"], w[f"fc1{i}_t"], M, ws["dx16b"] if dy16 else ws["dx32"], epilogue=ops.EPI_STORE_BF16 if dy16 else ops.EPI_STORE_F32,
+                   **top)
+        self._mark(f"b{i}:fc1d")
+        if bb:
+            self._bb_ln_grads(ws, gv, bb, m + ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
+        if ssf:                                                              # LN2 + ssf_0
+            self._ssf_ln_grad(ws, gv, m, ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
+        if top:                                                              # the other rows of dG1 are dGout: zero, in one memset
+            ops.memset_zero(dGin)
+        self._ln_bwd(ws, dy16, ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, dx=dGin, dres=dGout,
+                     dx16=None if self.kind in ("gaviko", "adaptformer", "dvpt") else ws["dG16"],
+                     rows=(B, sum(self._pool_rows()), T) if top else None)
+        if dvpt:
+            self._dvpt_bwd_scatter(ws, i, dGin, M)                           # dG1 += (dz . Wd) * QuickGELU'(G1)  (+ operand copy)
+        if self.kind == "adaptformer":
+            self._adapter_bwd(ws, gv, i, dGout, dGin, M, refresh_operand=pd_ > 0)   # adds LN_a'(...) into dG1 and refreshes dG16
+
+    def _attn_block_bwd(self, ws, sv, gv, i, dGin, dx, dy16, bot):
+        """Main stream, attention block of layer i: dx = dGin + LN1'(qkv^T(attn'(out^T(dGin)))), with the method's own gradients of the block
+        in launch order.  bot: _panels kwargs that restrict the qkv dgrad and LayerNorm 1 to the prompt rows (frozen bottom layer), or {}."""
+        w, d, C = self._w16, self._d, self.C
+        B, T = sv["B"], self.Ts[i]
+        M, a, st = B * T, self.names.attn(i), ws["stat"][i]
+        bb, pd_ = sv.get("bb") or (), sv.get("bdrop", 0.0)
+        ssf = self.kind == "ssf"
+        dy_at = dGin
+        if pd_ > 0:                                                          # gradient of dropout(to_out(.))
+            dy_at = self._masked_grad(ws, dGin, pd_, SEED_LAYER + 8 * i + 1, bool(bb) or ssf, M)
+        if ssf:                                                              # to_out + ssf_2: dy = dG1, y = G1[i] - G[i]
+            self._ssf_linear_grad(ws, gv, a, 2, dy_at, ws["G1"][i], M, C, y1=ws["G"][i], y_mul=1.0 - pd_)
+        if bb:                                                               # to_out: db = colsum(dG1), dW = dG1^T . ctx
+            self._bb_linear_grads(ws, gv, bb, a + ".to_out.0", dy_at, ws["dG16"], ws["ctx"][i], M, C, C)
+        self._gemm(ws["dG16"], w[f"out{i}_t"], M, ws["dctx"], epilogue=ops.EPI_STORE_BF16)
+        self._mark(f"b{i}:outd")
+        # (bottom layer of a frozen backbone: only dq / dk / dv of the prompt rows are read -- by the row-panel qkv dgrad below)
+        ops.attention_bwd(ws["qkv"][i], ws["ctx"][i], ws["dctx"], ws["lse"][i], ws["delta"], ws["dqkv"], B, T, self.heads, 64 ** -0.5,
+                          drop_p=pd_, seed=SEED_LAYER + 8 * i, seed_ptr=ws["seed"], q_prescaled=True, need_rows=self.P if bot else None)
+        self._mark(f"b{i}:attnb")
+        if self.kind == "melo" and i in self.lora_layers:
+            self._melo_bwd(ws, gv, i, M)
+        if ssf:                                                              # to_qkv + ssf_1: dy = dqkv, y = saved qkv
+            uq = {} if self.fp32 else dict(y0_cols=self.heads * 64, y0_mul=1.0 / self.q_scale)     # the saved q block is pre-scaled
+            self._ssf_linear_grad(ws, gv, a, 1, ws["dqkv"], ws["qkv"][i], M, 3 * C, **uq)
+        if bb:                                                               # to_qkv (bias-free): dW = dqkv^T . LN1(G)
+            self._bb_linear_grads(ws, gv, bb, a + ".to_qkv", None, ws["dqkv"], ws["sav"]["xn1"][i] if sv["wgrad"] else None, M, 3 * C, C)
+        self._gemm(ws["dqkv"], w[f"qkv{i}_t"], M, ws["dx16b"] if dy16 else ws["dx32"], epilogue=ops.EPI_STORE_BF16 if dy16 else ops.EPI_STORE_F32,
+                   **bot)
+        if bb:
+            self._bb_ln_grads(ws, gv, bb, a + ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
+        if ssf:                                                              # LN1 + ssf_0
+            self._ssf_ln_grad(ws, gv, a, ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
+        self._mark(f"b{i}:qkvd")
+        proj = None
+        if self._fuse_proj and i > 0:                                        # + dcomb = dx . W_up for the GPA core of layer i - 1
+            pre_lo, _ = self._gpa_names(i - 1)
+            proj = dict(w=d(pre_lo + ".proj_up.weight"), y=ws["bw"]["dcomb"], w_layout=1, L_=self.Lat)
+        self._ln_bwd(ws, dy16, ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, dx=dx, dres=dGin, dx16=None if bot else ws["dG16"],
+                     rows=(B, self.P, T) if bot else None, proj=proj)
+
+    def _ln_bwd(self, ws, dy16, x, mean, rstd, gamma, M, *, dx, dres, dx16=None, rows=None, proj=None):
+        """dx = dres + LN'(dy) (+ its GEMM-operand copy dx16) for the dy the dgrad GEMM left: ws['dx16b'] when dy16, else ws['dx32'].
+        rows = (groups, rows per group, group stride): the leading rows of every sample only.  proj = dict(w=, y=, L_=, w_layout=): the
+        rank-L projection of dx rides along."""
+        if dy16:
+            ops.layernorm_bwd_dy16(ws["dx16b"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16, rows=rows, proj=proj)
+        elif rows is not None:
+            ops.layernorm_bwd_rows(ws["dx32"], x, mean, rstd, gamma, *rows, self.C, dx=dx, dres=dres, dx16=dx16)
+        elif proj is not None:
+            ops.layernorm_bwd_proj(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16, **proj)
+        else:
+            ops.layernorm_bwd(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16)
 
     def _grad_supported(self, name: str) -> bool:
         # head: always; backbone tensors: the classes of _BB_KINDS (plain ViT `linear` / `bitfit` / `fft`, AdaptFormer and Gaviko with

@@ -21,7 +21,7 @@ PLAN_TIMING = os.environ.get("GAVIKO_HIP_PLAN_TIMING") is not None
 # Timing ablations (tools/ablate_streams.py) -- the RESULTS ARE WRONG with either switch; they only answer "where does the step go":
 #   nowait: the main stream skips its waits on the side chains;  noside: the MWSA / GPA chains are not launched at all.
 # (measurement build only: L.diag_env reads the environment when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so, else returns the default --
-#  in the product every switch below is a constant and no `_on(...)` branch can be taken the wrong way)
+#  in the product the ablation set is empty and no `_on(...)` branch can be taken the wrong way)
 _ABLATE = set(filter(None, (L.diag_env("GAVIKO_HIP_ABLATE", "") or "").split(",")))
 
 
@@ -32,16 +32,11 @@ def _on(tag: str) -> bool:
 # {+0 attention probabilities, +1 to_out, +2 after GELU, +3 after fc2}.  The MWSA sites use 2*i and 2*i + 1.
 SEED_EMB, SEED_PROMPT, SEED_LAYER = 900, 950, 1000
 
-# Dispatch priority of the side-chain streams (negative = higher).  Measured: -1 drops the step rate from 448 to 274 volumes/s
-# (priority queues serialise against the captured graph's main queue on this runtime), so the default stays 0.
-SIDE_STREAM_PRIORITY = int(L.diag_env("GAVIKO_HIP_SIDE_PRIORITY", "0"))
-# GPA prompt fix inside the next layer's first LayerNorm (gvk_layernorm_fwd_fix) instead of its own 128-row launch: measured 709-711 vs
-# 719-721 volumes/s -- the 128 prompt rows' waves become the tail of a 4132-row kernel; opt-in
-_FIX_IN_LN = L.diag_env("GAVIKO_HIP_FIX_IN_LN", "0") == "1"
 _SIDE_STREAMS = {}                       # (device index, kind) -> the process-wide side stream of that kind
-# MWSA backward chain held behind the layer's attention backward: measured 669 vs 688 volumes/s -- the chain then slows the dgrad GEMMs
-# of the next layer by as much as it slowed the attention kernels before (start->fc1d 82 -> 98 us); opt-in only
-_LOC_SHIFT = L.diag_env("GAVIKO_HIP_LOC_SHIFT", "0") == "1"
+# Measured, lost and removed from the engine: side streams at a higher dispatch priority (-1: 448 -> 274 volumes/s, priority queues
+# serialise against the main queue on this runtime); the GPA prompt fix inside the next layer's first LayerNorm instead of its own 128-row
+# launch (709-711 vs 719-721: the prompt rows' waves become the tail of a 4132-row kernel); the MWSA backward chain held behind the layer's
+# attention backward (669 vs 688: it then slows the next layer's dgrad GEMMs as much as it slowed the attention kernels, start->fc1d 82 -> 98 us).
 _EPI_NAMES = {0: "store_bf16", 1: "bias_res_f32", 2: "bias_gelu_bf16", 3: "patch_f32", 4: "gelu_bwd_bf16", 5: "store_f32", 6: "bias_res_f32_bf16",
               7: "bias_relu_bf16", 8: "relu_bwd_bf16"}
 

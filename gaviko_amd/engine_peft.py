@@ -2,15 +2,10 @@
 (adaptformer.py, melo.py, train.py:123-137, evp.py, dvpt.py, ssf.py).  Mixed into engine.Engine; every method only enqueues C-ABI launches."""
 from __future__ import annotations
 
-import math
-import os
-from typing import Dict, List, Optional
-
 import torch
 
-from . import lib as L
 from . import ops
-from .engine_common import (SEED_EMB, SEED_LAYER, SEED_PROMPT, GRAPH_WARMUP, Names, PLAN_TIMING, SIDE_STREAM_PRIORITY, STEP_MODE, USE_GRAPHS, _ABLATE, _EPI_NAMES, _FIX_IN_LN, _LOC_SHIFT, _MODE, _SIDE_STREAMS, _on, evp_highpass_operator)  # noqa: F401
+from .engine_common import evp_highpass_operator
 
 
 class PeftPaths:
