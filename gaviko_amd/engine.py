@@ -180,6 +180,9 @@ class Engine(GavikoPaths, PeftPaths):
         self.bucket_layers = 4              # layout of the flat gradient buffer: completion groups of this many layers (set_bucket_layers)
         self._saved = None
         self._pre_is_grad = False
+        self._igrad = None                  # the backward being issued also carries the gradient to the input volume: None | "params" | "only"
+        self._ig_scratch = {}               # input-gradient mode -> scratch gradient targets (a recorded plan keeps their addresses)
+        self._conv_t_version = None
 
     def _gemm(self, a, w, M, out0, alg_k=None, **kw):
         """One NT GEMM launch.  alg_k: the ALGORITHMIC contraction length when the operand carries padding columns (fc2 with the
@@ -319,10 +322,11 @@ class Engine(GavikoPaths, PeftPaths):
         if names is None or any(n in self._fold_names for n in names):
             self._fold_version = None
 
-    def workspace(self, B: int, device, train: bool, keep_attn: bool = False):
+    def workspace(self, B: int, device, train: bool, keep_attn: bool = False, tag: Optional[str] = None):
         """keep_attn (inference only, gaviko_amd.explain): a workspace of its own whose forward keeps every layer's qkv / lse (and every
-        other per-layer slot) as a training forward does, for the attention-map kernels."""
-        key = (B, train, str(device)) + (("attn",) if keep_attn else ())
+        other per-layer slot) as a training forward does, for the attention-map kernels.  tag: another workspace of its own for the same
+        (B, mode) -- 'igrad', the input-gradient sweeps of gaviko_amd.explain."""
+        key = (B, train, str(device)) + (("attn",) if keep_attn else ()) + ((tag,) if tag else ())
         if key in self._wss:
             self._ws = self._wss[key]
             return self._ws
@@ -559,7 +563,7 @@ class Engine(GavikoPaths, PeftPaths):
         return
 
     # ------------------------------------------------------------------ forward
-    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None, keep_attn: bool = False) -> torch.Tensor:
+    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None, keep_attn: bool = False, ws_tag: Optional[str] = None) -> torch.Tensor:
         L.require_device()
         if not img.is_cuda:
             raise L.GavikoHipError("input volume must be on the HIP device: gaviko_amd has no CPU path")
@@ -575,7 +579,7 @@ class Engine(GavikoPaths, PeftPaths):
         if (sv["bdrop"] > 0 or sv["edrop"] > 0 or sv["pdrop"] > 0) and self.kind not in ("vit", "melo", "vpt", "adaptformer", "gaviko", "dvpt", "evp", "ssf"):
             raise L.GavikoHipError(f"backbone dropout > 0 in training mode: unknown kind {self.kind!r}")
         self.refresh_weights(need_dgrad=train)
-        ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train)
+        ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train, tag=ws_tag)
         if img.data_ptr() != ws["img"].data_ptr():           # a caller that fills input_buffer() itself skips the copy-in launch
             ws["img"].copy_(img.detach())                   # static input buffer (the only per-step host-visible copy-in)
         # unfrozen backbone tensors (`fft` / `bitfit`, train.py:123-137): which ones train, and whether GEMM inputs must be kept
@@ -591,6 +595,8 @@ class Engine(GavikoPaths, PeftPaths):
         key = (B, train, sv["attn_drop"], sv["proj_drop"], len(bb), sv["wgrad"], sv["bdrop"], sv["edrop"], sv["pdrop"])
         if keep_attn and not train:
             key += ("attn",)                                 # its own workspace: its own launch plan
+        if ws_tag:
+            key += (ws_tag,)
         self._keep_inputs = bool(sv["wgrad"])
         sv["pre_is_grad"] = self._pre_is_grad = bool(train and self._gelu_grad and not self._keep_inputs and sv["bdrop"] <= 0 and not bb)
         self._fold_on = (not self._keep_inputs) and self._ensure_fold()      # ONE place decides: operands are current whenever the fold is taken
@@ -605,14 +611,43 @@ class Engine(GavikoPaths, PeftPaths):
         """The deterministic inference forward (no dropout) in a workspace of its own that keeps every layer's qkv / lse -> (logits, ws).
         The state a pending backward reads (saved activations, their workspace and the per-step decisions of forward()) is put back, so a
         call between a training forward and its backward leaves that backward's gradients bit-identical."""
-        keep = {k: getattr(self, k) for k in ("_ws", "_saved", "_saved_key", "_keep_inputs", "_pre_is_grad", "_fold_on", "_last_run")
-                if hasattr(self, k)}
+        keep = self._pending_state()
         try:
             logits = self.forward(img, train=False, drop=None, keep_attn=True)
             ws = self._ws
         finally:
-            for k, v in keep.items():
-                setattr(self, k, v)
+            self._restore_state(keep)
+        return logits, ws
+
+    def _pending_state(self) -> dict:
+        """What a pending backward reads besides its workspace: the saved activations and the per-step decisions of forward()."""
+        return {k: getattr(self, k) for k in ("_ws", "_saved", "_saved_key", "_keep_inputs", "_pre_is_grad", "_fold_on", "_last_run", "_fwd_gen")
+                if hasattr(self, k)}
+
+    def _restore_state(self, keep: dict) -> None:
+        for k, v in keep.items():
+            setattr(self, k, v)
+
+    def eval_forward(self, img: torch.Tensor) -> torch.Tensor:
+        """A deterministic inference forward (no dropout) that leaves the state of a pending backward as it was."""
+        keep = self._pending_state()
+        try:
+            return self.forward(img, train=False, drop=None)
+        finally:
+            self._restore_state(keep)
+
+    def input_backward(self, img: torch.Tensor, seed):
+        """Gradient of the logits with respect to the input volume, for gaviko_amd.explain: a deterministic training forward (no dropout)
+        and an input-only backward, both in the 'igrad' workspace -> (logits, ws).  `seed(logits)` returns dlogits [B, K] (the logit
+        gradient to start from).  ws['ig']['dcols'] holds the gradient in the patch-embedding's im2col layout, ws['dimg'] the volume.  No
+        parameter gradient is written (the sweep writes into a scratch buffer of its own) and the state of a pending backward is put back."""
+        keep = self._pending_state()
+        try:
+            logits = self.forward(img, train=True, drop=None, ws_tag="igrad")
+            self.backward(seed(logits), input_grad="only")
+            ws = self._ws
+        finally:
+            self._restore_state(keep)
         return logits, ws
 
     def input_buffer(self, B: int, device, train: bool = True) -> torch.Tensor:
@@ -907,26 +942,57 @@ class Engine(GavikoPaths, PeftPaths):
     def flat_grad(self) -> Optional[torch.Tensor]:
         return None if self._flat_grad is None else self._flat_grad["buf"]
 
-    def backward(self, dlogits: torch.Tensor, reducer=None) -> Dict[str, torch.Tensor]:
+    def backward(self, dlogits: torch.Tensor, reducer=None, input_grad: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """Fills and returns {param name: gradient view into the flat fp32 gradient buffer} for every trainable tensor.
         The sweep is cut into segments at the reducer's bucket boundaries (one segment without a reducer); each segment is a
         HIP graph after warm-up.  `reducer` (distributed.GradReducer) is told after every segment which layers are done, so
-        finished buckets of the flat buffer are all-reduced on its side stream while the next segment runs."""
+        finished buckets of the flat buffer are all-reduced on its side stream while the next segment runs.
+        input_grad: the sweep also carries the gradient down to the input volume (ws['dimg'], ws['ig']['dcols']) -- "params": and the
+        parameter gradients as without it (bit-identical); "only": no parameter gradient is written (the kernels that produce them write
+        into a scratch buffer of its own; the flat buffer and every .grad stay untouched) and {} is returned."""
+        if input_grad not in (None, "params", "only"):
+            raise L.GavikoHipError(f"input_grad={input_grad!r}: expected None, 'params' or 'only'")
+        if input_grad is None:
+            return self._backward(dlogits, reducer)
+        self._igrad = input_grad
+        try:
+            return self._backward(dlogits, reducer if input_grad == "params" else None)
+        finally:
+            self._igrad = None
+
+    def _backward(self, dlogits, reducer):
         sv = self._saved
         if sv is None:
             raise L.GavikoHipError("backward() without a preceding training-mode forward()")
         ws = self._ws
-        gv = self._grad_views(dlogits.device)
+        ig = self._igrad
+        gv = self._grad_views(dlogits.device) if ig != "only" else {}
         unsupported = [n for n in gv if not self._grad_supported(n)]
         if unsupported:
             raise NotImplementedError(f"gradients for backbone tensors are not built yet (frozen-backbone PEFT only): {unsupported[:3]}...")
+        real = gv
+        if ig:
+            self._ig_buffers(ws, sv["B"], dlogits.device)
+            gv = dict(real, **self._ig_scratch_views(dlogits.device, real))
         if dlogits.data_ptr() != ws["dlogits"].data_ptr():
             ws["dlogits"].copy_(dlogits.detach())
-        flat = self._flat_grad["buf"]
+        flat = self._flat_grad["buf"] if ig != "only" else None
+        saved_key = self._saved_key + (("ig", ig),) if ig else self._saved_key
+        if ig == "only":
+            keep = self._flat_grad
+            self._flat_grad = self._ig_scratch["only"]        # the kernels that address the flat buffer directly write the scratch
+            try:
+                return self._backward_sweep(ws, sv, gv, real, flat, saved_key, reducer)
+            finally:
+                self._flat_grad = keep
+        return self._backward_sweep(ws, sv, gv, real, flat, saved_key, reducer)
+
+    def _backward_sweep(self, ws, sv, gv, real, flat, saved_key, reducer):
+        ig = self._igrad
         if reducer is not None:
             reducer.begin()
-        if not self._needs_backbone_backward():
-            self._run("bwd_head", self._saved_key, lambda: self._backward_head(ws, sv, gv, False))
+        if not self._needs_backbone_backward() and not ig:
+            self._run("bwd_head", saved_key, lambda: self._backward_head(ws, sv, gv, False))
             if reducer is not None:
                 reducer.finish(flat)
             return gv
@@ -935,7 +1001,7 @@ class Engine(GavikoPaths, PeftPaths):
             self._want_bucket_marks = True
             self._bucket_marks = {}
             try:
-                self._run("bwd0", self._saved_key + ("events",),
+                self._run("bwd0", saved_key + ("events",),
                           lambda: self._backward_segment(ws, sv, gv, self.depth - 1, 0, True, True))
             finally:
                 self._want_bucket_marks = False
@@ -947,20 +1013,20 @@ class Engine(GavikoPaths, PeftPaths):
                 marks = self._bucket_marks
                 waiter = lambda stream, ev: stream.wait_event(ev)
             reducer.reduce_marked(flat, marks, waiter)
-            return gv
+            return real
         cuts = sorted({r for r, _, _ in reducer.ranges if r >= 0}, reverse=True) if reducer is not None else []
         cuts = [c for c in cuts if 0 < c < self.depth]          # segment k ends (inclusive) at layer cuts[k]
         hi = self.depth - 1
         for seg, lo in enumerate(cuts + [0]):
             first, last = seg == 0, lo == 0
-            self._run(f"bwd{seg}", self._saved_key + (tuple(cuts),),
+            self._run(f"bwd{seg}", saved_key + (tuple(cuts),),
                       lambda hi=hi, lo=lo, first=first, last=last: self._backward_segment(ws, sv, gv, hi, lo, first, last))
             if reducer is not None:
                 reducer.layer_done(flat, lo)
             hi = lo - 1
         if reducer is not None:
             reducer.finish(flat)
-        return gv
+        return real
 
     def _backward_head(self, ws, sv, gv, backbone_bwd):
         nm, d = self.names, self._d
@@ -1026,7 +1092,7 @@ class Engine(GavikoPaths, PeftPaths):
         # pos_embedding carry none), so its qkv dgrad and LayerNorm-1 backward run on those rows.
         frozen = gaviko and not bb and sv.get("bdrop", 0.0) <= 0 and not sv["wgrad"]
         top = self._panels(B, sum(self._pool_rows())) if (frozen and first) else {}
-        bot = self._panels(B, self.P) if (frozen and last and self.P > 0) else {}
+        bot = self._panels(B, self.P) if (frozen and last and self.P > 0 and not self._igrad) else {}     # (the input gradient reads every row)
         prev_scl = None
         for i in range(hi, lo - 1, -1):
             M = B * self.Ts[i]
@@ -1086,7 +1152,7 @@ class Engine(GavikoPaths, PeftPaths):
         if gaviko:
             if last:                                                         # (the deferred step crosses segment boundaries like layer boundaries)
                 # frozen embedding: the local stream's INPUT gradient (layer 0's deferred last step) has no reader -- conv / pos_embedding carry none
-                self._mwsa_flush(ws, B, loc, dead=self.prune_dead_rows and lo == 0 and not sv.get("bb"))
+                self._mwsa_flush(ws, B, loc, dead=self.prune_dead_rows and lo == 0 and not sv.get("bb") and not self._igrad)
             self._wait(None, "gpa")
             self._wait(None, "loc")
         if last and sv.get("bb"):
@@ -1118,6 +1184,8 @@ class Engine(GavikoPaths, PeftPaths):
         if last and (gaviko or self.kind == "dvpt"):
             ops.rows_batch_sum(dGout, gv["prompt_embeddings"].view(self.P, C), gv["prompt_positional_embedding"].view(self.P, C), B, T, 0,
                                self.P, C)
+        if last and self._igrad:
+            self._input_grad_tail(ws, sv, dGout, B, lo)
         if last:
             self._bucket_mark("main", -1)                                    # everything else (prompts, head, unindexed tensors): end of the sweep
         self._mark("b:tail")                                                 # side streams joined, embedding-side gradients issued
@@ -1218,6 +1286,106 @@ class Engine(GavikoPaths, PeftPaths):
             ops.layernorm_bwd_proj(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16, **proj)
         else:
             ops.layernorm_bwd(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16)
+
+    # ------------------------------------------------------------------ input gradient (gaviko_amd.explain, img.requires_grad)
+    def _ig_names(self) -> List[str]:
+        """Every tensor whose gradient kernel the sweep may reach: the trainable ones, the method's own and the head.  An input-gradient
+        sweep runs the full backward whatever trains, so the kernels of the tensors that do not train get scratch targets."""
+        head = self.names.head()
+        return [n for n, p in self.p.items() if p.requires_grad or n.startswith(head) or self._own_grad_kernels(n)]
+
+    def _ig_scratch_views(self, device, real) -> Dict[str, torch.Tensor]:
+        """Scratch gradient targets for the names of _ig_names that `real` (the flat buffer's views) lacks: all of them in "only" mode,
+        where the scratch buffer takes the flat buffer's layout (distributed.flat_order: GAViKO's GPA gate tensors are one contiguous slice
+        that one kernel writes) and stands in for it during the sweep (_backward)."""
+        names = [n for n in self._ig_names() if n not in real]
+        if not real:
+            from .distributed import flat_order
+            names = flat_order(tuple(names), self.cfg.get("share_factor", 1) if self.kind == "gaviko" else 1, self.bucket_layers)
+        sig = (tuple((n, tuple(self.p[n].shape)) for n in names), str(device))
+        sc = self._ig_scratch.get(self._igrad)
+        if sc is None or sc["sig"] != sig:
+            if sc is not None:                            # recorded plans hold the old buffer's addresses
+                self._graphs.clear()
+                self._calls.clear()
+            buf = torch.zeros(max(1, sum(self.p[n].numel() for n in names)), device=device)
+            views, off = {}, 0
+            for n in names:
+                k = self.p[n].numel()
+                views[n] = buf[off: off + k].view(self.p[n].shape)
+                off += k
+            sc = self._ig_scratch[self._igrad] = {"sig": sig, "buf": buf, "views": views}
+        return sc["views"]
+
+    def _ig_buffers(self, ws, B, device) -> None:
+        """Buffers of the input-gradient tail (in the workspace: a recorded plan keeps their addresses) and the transposed patch-embedding
+        operand conv^T [Kp][C] (the dgrad GEMM's W), rebuilt in place when the conv weight changed.  SSF folds its scale into the operand
+        inside the step (_input_grad_tail)."""
+        C, BN, Kp = self.C, B * self.N, self.Kp
+        if "ig" not in ws:
+            ig = ws["ig"] = dict(dxc=ops.act_zeros(BN, C, torch.float32, device), dcols=ops.act_zeros(BN, Kp, torch.float32, device))
+            if not self.fp32:
+                ig["dxc16"] = ops.act_zeros(BN, C, self.adt, device)
+            if self.kind == "evp":
+                ig["dhc"] = ops.act_zeros(BN, 64, torch.float32, device)
+                ig["dhcols"] = ops.act_zeros(BN, Kp, torch.float32, device)
+                ig["dhp"] = torch.zeros_like(ws["img"])
+                ig["dhp2"] = torch.zeros_like(ws["img"])
+            ws["dimg"] = torch.zeros_like(ws["img"])
+        w = self._w16
+        if "conv_t" not in w:
+            w["conv_t"] = torch.zeros((Kp, C), dtype=self.adt, device=device)
+        if self.kind == "evp":
+            st = self._evp_state(device)
+            if "hpT" not in st:
+                st["hpT"] = st["hp"].t().contiguous()                   # the adjoint operator of the high-pass's linear part
+                st["WpT"] = torch.zeros((Kp, 64), device=device)
+        if self.kind == "ssf":
+            return
+        cw = self.p[self.names.conv() + ".weight"]
+        version = (cw._version, cw.data_ptr())
+        if version != self._conv_t_version:
+            ops.transpose_operand(self._d(self.names.conv() + ".weight").reshape(C, Kp).contiguous(), w["conv_t"], self.adt)
+            self._conv_t_version = version
+
+    def _input_grad_tail(self, ws, sv, dG0, B, lo):
+        """dG0 (the gradient of the layer-0 input) -> the gradient of the input volume.  The patch rows of dG0 (through emb_dropout) plus
+        whatever else read the raw patch embedding -- GAViKO's local stream (the MWSA chain's input gradient, dL), EVP's
+        embedding_generator (ds . W_e) -- make d xc [B*N][C]; d cols = d xc . W_conv (the dgrad GEMM against conv^T); the stride-equals-
+        kernel convolution makes the volume a permutation of d cols (gvk_unpatchify_f32).  EVP adds its high-pass branch:
+        d hcols = ds . W_p, un-patchified, through the modulus and the adjoint high-pass, back to the im2col layout and into d cols."""
+        C, T, N, Kp, BN = self.C, self.T, self.N, self.Kp, B * self.N
+        ig, w = ws["ig"], self._w16
+        edrop = sv.get("edrop", 0.0)
+        premasked = bool(sv.get("bb"))                    # the trainable-embedding tail above has applied the emb_dropout masks in place
+        src = dG0
+        if edrop > 0 and not premasked:
+            ops.dropout_rows(dG0, edrop, SEED_EMB, ws["seed"], out32=ws["dx32"], M=B * T, N=C)
+            src = ws["dx32"]
+        ops.rows_gather(src, ig["dxc"], B, T, N, C, self.row_off)
+        if self.kind == "gaviko":                          # local stream = conv(img) + pos[1:] (gaviko.py:545-546): its input gradient
+            dlocal = ws["dL"][(self.depth - lo) & 1]        # (what _mwsa_final of the lowest layer wrote)
+            if edrop > 0 and not premasked:
+                ops.dropout_rows(dlocal, edrop, SEED_EMB + 1, ws["seed"], out32=dlocal, M=BN, N=C)
+            ops.add2d(ig["dxc"], C, dlocal, C, ig["dxc"], C, BN, C)
+        if self.kind == "evp":                             # embedding_generator reads the raw conv output (evp.py:347-348)
+            ops.skinny_up(lat=ws["evb"]["ds"], w=self._evp_state(dG0.device)["We"], out=ig["dxc"], M=BN, C=C, L=self.Lp, w_layout=1, accumulate=1)
+        if self.kind == "ssf":                             # y = s o conv(img) + t (ssf.py:229-232): the operand is s o W, as the forward's
+            ops.ssf_fold_weight(self.p[self.names.conv() + ".weight"].detach().reshape(C, Kp), self.p["ssf_scale_1"].detach(), w["conv"], w["conv_t"])
+        a = ig["dxc"] if self.fp32 else ops.to_operand(ig["dxc"], ig["dxc16"], self.adt)
+        ops.gemm_nt(a, w["conv_t"], BN, ig["dcols"], epilogue=ops.EPI_STORE_F32)
+        if self.kind == "evp":
+            st = self._evp_state(dG0.device)
+            # hc = hcols . Wp^T + bp, s = hc[:, :Lp] + e  ->  d hcols = ds . Wp (rows >= r of Wp are zero); fp32 as the forward's GEMM
+            ops.pad2d(ws["evb"]["ds"], BN, self.Lp, ig["dhc"], BN, 64)
+            ops.transpose_any(st["Wp"], st["WpT"], 64, Kp)
+            ops.gemm_nt(ig["dhc"], st["WpT"], BN, ig["dhcols"], epilogue=ops.EPI_STORE_F32)
+            ops.unpatchify(ig["dhcols"], ig["dhp"], self.patch)
+            ops.evp_highpass_sign(ws["img"], st["hp"], st["dmask"], ig["dhp"], ig["dhp2"])
+            ops.evp_highpass_linear(ig["dhp2"], st["hpT"], st["dmask"], ig["dhp"])
+            ops.patchify(ig["dhp"], ig["dhcols"], self.patch)
+            ops.add2d(ig["dcols"], Kp, ig["dhcols"], Kp, ig["dcols"], Kp, BN, Kp)
+        ops.unpatchify(ig["dcols"], ws["dimg"], self.patch)
 
     def _grad_supported(self, name: str) -> bool:
         # head: always; backbone tensors: the classes of _BB_KINDS (plain ViT `linear` / `bitfit` / `fft`, AdaptFormer and Gaviko with

@@ -11,6 +11,15 @@ row-weighted sums of P from them, as the backward recomputes P from lse.
     grid = patch_grid(model, rel)                        # [B, D/pd, H/ph, W/pw]
 
 Only the bf16 path and the global self-attention are covered; the MWSA local attention and the GPA cross-attention are not.
+
+Gradient attributions cover every module of every method, on both precision paths: the gradient of a logit with respect to the input
+volume, from a deterministic (no-dropout) forward and an input-only backward in a workspace of their own (Engine.input_backward; no
+parameter gradient changes), un-patchified by csrc/input_grad.hip with the attribution arithmetic in the same pass.
+
+    logits, g = input_gradient(model, img)                 # g: [B, 1, D, H, W], d logit[b, target[b]] / d img[b]
+    logits, g = smoothgrad(model, img, samples=16)         # mean over noisy copies (Smilkov et al., 2017)
+    logits, attr, delta = integrated_gradients(model, img) # (Sundararajan et al., 2017); delta: the completeness gap
+    grid = patch_saliency(model, g)                        # [B, D/pd, H/ph, W/pw]: sum of |g| per patch (patch_grid's layout)
 """
 from __future__ import annotations
 
@@ -108,3 +117,157 @@ def patch_grid(model, relevance: torch.Tensor) -> torch.Tensor:
         raise L.GavikoHipError(f"patch_grid: expected a last dimension of T = {eng.T} tokens, got {tuple(relevance.shape)}")
     patches = relevance[..., eng.row_off: eng.row_off + eng.N]
     return patches.reshape(*relevance.shape[:-1], *eng.grid)
+
+
+# ---- gradient attributions ----------------------------------------------------------------------------------------------------
+def _volume_check(model, img, what):
+    eng = model._engine()
+    if not isinstance(img, torch.Tensor) or not img.is_cuda:
+        raise L.GavikoHipError(f"{what} runs on the HIP device: move the model and the input there (there is no CPU path)")
+    want = (1,) + tuple(g * p for g, p in zip(eng.grid, eng.patch))
+    if img.dim() != 5 or tuple(img.shape[1:]) != want or img.shape[0] < 1:
+        raise L.GavikoHipError(f"{what}: expected img [B, {', '.join(map(str, want))}], got {tuple(img.shape)}")
+    if img.dtype != torch.float32:
+        raise L.GavikoHipError(f"{what}: expected a float32 volume, got {img.dtype}")
+    return eng, img.detach().contiguous()
+
+
+def _targets(eng, logits, target, B) -> torch.Tensor:
+    """int64 [B] device tensor of the logit to explain per sample: None -> the argmax of `logits`, an int, or a [B] tensor."""
+    dev = logits.device
+    if target is None:
+        return logits.argmax(dim=1)
+    if isinstance(target, bool):
+        raise L.GavikoHipError(f"target={target!r}: expected None, an int or a [B] tensor")
+    if isinstance(target, int):
+        if not 0 <= target < eng.K:
+            raise L.GavikoHipError(f"target={target}: outside [0, {eng.K})")
+        return torch.full((B,), target, dtype=torch.int64, device=dev)
+    if isinstance(target, torch.Tensor):
+        t = target.reshape(-1)
+        if t.numel() != B or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise L.GavikoHipError(f"target: expected an integer tensor of {B} elements, got {tuple(target.shape)} {target.dtype}")
+        t = t.to(device=dev, dtype=torch.int64)
+        if bool(((t < 0) | (t >= eng.K)).any()):
+            raise L.GavikoHipError(f"target: a class index outside [0, {eng.K})")
+        return t
+    raise L.GavikoHipError(f"target={target!r}: expected None, an int or a [B] tensor")
+
+
+def _onehot(tgt, K):
+    return lambda logits: torch.nn.functional.one_hot(tgt, K).to(logits.dtype)
+
+
+def _batch(batch, default):
+    if batch is None:
+        return default
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise L.GavikoHipError(f"batch={batch!r}: expected a positive int")
+    return batch
+
+
+def _accumulate(eng, rows, tgt_rows, out, S, alpha, x=None, x0=None, batch=1):
+    """out[b] = sum_s alpha * g(rows[b*S + s]) (* (x[b] - x0[b])): the input gradients of the logit tgt_rows[r] at every row r, in engine
+    batches of `batch` rows; each output sample's rows are summed in s order by gvk_unpatchify_f32 (one FMA per step), so the result does
+    not depend on how the rows are split into batches beyond the per-row gradients themselves."""
+    n = rows.shape[0]
+    for c0 in range(0, n, batch):
+        c1 = min(n, c0 + batch)
+        _, ws = eng.input_backward(rows[c0:c1], _onehot(tgt_rows[c0:c1], eng.K))
+        dcols = ws["ig"]["dcols"]
+        r = c0
+        while r < c1:                                   # the runs of one output sample inside this batch
+            b, s = divmod(r, S)
+            e = min(c1, (b + 1) * S)
+            ops.unpatchify(dcols[(r - c0) * eng.N:], out[b:b + 1], eng.patch, x=None if x is None else x[b:b + 1],
+                           x0=None if x0 is None else x0[b:b + 1], alpha=alpha, beta=0.0 if s == 0 else 1.0, nsum=e - r)
+            r = e
+
+
+def input_gradient(model, img: torch.Tensor, target=None, *, times_input: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (logits [B, K], grad [B, 1, D, H, W] float32): d logit[b, target[b]] / d img[b] (times img with times_input: gradient x input).
+    target: None (the argmax per sample), an int, or a [B] tensor of class indices."""
+    eng, x = _volume_check(model, img, "input_gradient")
+    B = x.shape[0]
+    box = {}
+
+    def seed(logits):
+        box["t"] = _targets(eng, logits, target, B)
+        return torch.nn.functional.one_hot(box["t"], eng.K).to(logits.dtype)
+
+    if isinstance(target, (int, torch.Tensor)) and not isinstance(target, bool):
+        _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)       # reject a bad target before any launch
+    logits, ws = eng.input_backward(x, seed)
+    out = torch.empty_like(x)
+    ops.unpatchify(ws["ig"]["dcols"], out, eng.patch, x=x if times_input else None)
+    return logits, out
+
+
+def smoothgrad(model, img: torch.Tensor, target=None, *, samples: int = 16, sigma: float = 0.15, generator=None,
+               batch: int = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (logits [B, K] of the clean input, grad [B, 1, D, H, W]): the mean input gradient over `samples` noisy copies x + N(0, s^2) per
+    volume, s = sigma * (max - min) of that volume.  target None: the clean input's argmax.  batch: engine rows per sweep (default B)."""
+    eng, x = _volume_check(model, img, "smoothgrad")
+    B = x.shape[0]
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise L.GavikoHipError(f"samples={samples!r}: expected a positive int")
+    if not sigma >= 0:
+        raise L.GavikoHipError(f"sigma={sigma!r}: expected >= 0")
+    if isinstance(target, (int, torch.Tensor)) and not isinstance(target, bool):
+        _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)
+    bs = _batch(batch, B)
+    with torch.no_grad():
+        logits = eng.eval_forward(x)
+        tgt = _targets(eng, logits, target, B)
+        rows = x.repeat_interleave(samples, dim=0)
+        if sigma > 0:
+            flat = x.reshape(B, -1)
+            scale = (sigma * (flat.amax(1) - flat.amin(1))).repeat_interleave(samples).view(-1, 1, 1, 1, 1)
+            noise = torch.randn(rows.shape, generator=generator, device=x.device if generator is None else generator.device)
+            rows = rows + noise.to(x.device) * scale
+        out = torch.empty_like(x)
+        _accumulate(eng, rows.contiguous(), tgt.repeat_interleave(samples), out, samples, 1.0 / samples, batch=bs)
+    return logits, out
+
+
+def integrated_gradients(model, img: torch.Tensor, target=None, *, baseline: torch.Tensor = None, steps: int = 32,
+                         batch: int = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (logits [B, K], attributions [B, 1, D, H, W], delta [B]): (x - x0) * mean_k grad(x0 + a_k (x - x0)), a_k = (k + 1/2) / steps
+    (the midpoint rule), and the completeness gap delta = sum(attr) - (f(x) - f(x0)) of the explained logit (float64).  baseline: None
+    (zeros) or a volume of img's shape.  batch: engine rows per sweep (default B)."""
+    eng, x = _volume_check(model, img, "integrated_gradients")
+    B = x.shape[0]
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise L.GavikoHipError(f"steps={steps!r}: expected a positive int")
+    if baseline is None:
+        x0 = torch.zeros_like(x)
+    else:
+        _, x0 = _volume_check(model, baseline if baseline.dim() == 5 else baseline[None], "integrated_gradients baseline")
+        x0 = x0.expand_as(x).contiguous()
+    if isinstance(target, (int, torch.Tensor)) and not isinstance(target, bool):
+        _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)
+    bs = _batch(batch, B)
+    with torch.no_grad():
+        logits = eng.eval_forward(x)
+        f0 = eng.eval_forward(x0)
+        tgt = _targets(eng, logits, target, B)
+        a = (torch.arange(steps, device=x.device, dtype=torch.float32) + 0.5) / steps
+        rows = x0.repeat_interleave(steps, dim=0) + a.repeat(B).view(-1, 1, 1, 1, 1) * (x - x0).repeat_interleave(steps, dim=0)
+        out = torch.empty_like(x)
+        _accumulate(eng, rows.contiguous(), tgt.repeat_interleave(steps), out, steps, 1.0 / steps, x=x, x0=x0, batch=bs)
+        grid = torch.empty((B,) + tuple(eng.grid), device=x.device)
+        ops.patch_reduce(out, grid, eng.patch, absval=False)
+        idx = torch.arange(B, device=x.device)
+        delta = grid.double().reshape(B, -1).sum(1) - (logits[idx, tgt].double() - f0[idx, tgt].double())
+    return logits, out, delta
+
+
+def patch_saliency(model, volume_map: torch.Tensor, reduce: str = "abs") -> torch.Tensor:
+    """[B, 1, D, H, W] volume map (a gradient, an attribution) -> [B, D/pd, H/ph, W/pw]: per patch the sum of |map| (reduce='abs') or of
+    the map (reduce='sum'), in the layout of patch_grid."""
+    if reduce not in ("abs", "sum"):
+        raise L.GavikoHipError(f"reduce={reduce!r}: expected 'abs' or 'sum'")
+    eng, v = _volume_check(model, volume_map, "patch_saliency")
+    out = torch.empty((v.shape[0],) + tuple(eng.grid), device=v.device)
+    ops.patch_reduce(v, out, eng.patch, absval=reduce == "abs")
+    return out

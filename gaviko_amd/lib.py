@@ -129,6 +129,10 @@ SIGNATURES = {
     "gvk_attention_bwd_bf16_fused": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _F, _P],
     "gvk_attention_colsum_bf16": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "gvk_rollout_step": [_P, _P, _P, _I, _I, _I, _P],
+    "gvk_unpatchify_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
+    "gvk_patch_reduce_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "gvk_evp_highpass_sign": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "gvk_evp_highpass_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_attention_fwd_f32_dropout": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
     "gvk_attention_bwd_f32_dropout": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
     "gvk_attention_fwd_bf16_dropout": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],

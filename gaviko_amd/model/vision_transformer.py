@@ -67,10 +67,22 @@ class Transformer(_Container):
                                      for _ in range(depth)])
 
 
+def _will_execute(node):
+    """True / False: autograd will / will not run `node` in this backward; None: it is a leaf that torch.autograd.grad captures (the
+    probe refuses to answer for those)."""
+    probe = getattr(torch._C, "_will_engine_execute_node", None)
+    if probe is None or node is None:
+        return True
+    try:
+        return bool(probe(node))
+    except RuntimeError:
+        return None
+
+
 class _HotPathFn(torch.autograd.Function):
     """Bridges torch autograd to the engine: one node for the whole model.  The engine writes parameter gradients
     straight into views of its flat gradient buffer (what the data-parallel all-reduce sends), so the per-parameter
-    results returned to autograd are None."""
+    results returned to autograd are None.  The gradient of `img` (when it requires one) is returned as usual."""
 
     @staticmethod
     def forward(ctx, owner, img, drop, *params):
@@ -85,24 +97,29 @@ class _HotPathFn(torch.autograd.Function):
     def backward(ctx, dlogits):
         owner = ctx.owner
         eng = owner._engine()
-        # The node hands autograd no input gradients (the engine writes every parameter's .grad itself), so torch.autograd.grad(loss, params)
-        # or backward(inputs=...) would come back with None for all of them without a word.  Those calls run the engine with a non-empty
-        # execution plan; a plain loss.backward() runs it with an empty one, for which _will_engine_execute_node answers True for any node.
-        probe = getattr(torch._C, "_will_engine_execute_node", None)
-        node = next((fn for fn, _ in ctx.next_functions if fn is not None), None)
-        if probe is not None and node is not None:
-            try:
-                plain = bool(probe(node))
-            except RuntimeError:
-                plain = False                   # (a leaf that autograd.grad captures: the probe refuses to answer -- same situation)
-            if not plain:
-                raise L.GavikoHipError("gaviko_amd models write parameter gradients into .grad themselves: use loss.backward() "
-                                       "(torch.autograd.grad(loss, params) / backward(inputs=...) would silently receive None for every "
-                                       "parameter); read the gradients from p.grad afterwards")
+        # The node hands autograd no parameter gradients (the engine writes every parameter's .grad itself), so torch.autograd.grad(loss,
+        # params) or backward(inputs=params) would come back with None for all of them without a word.  Those calls run the engine with a
+        # non-empty execution plan; a plain loss.backward() runs it with an empty one, for which _will_engine_execute_node answers True for
+        # any node.  next_functions: the img edge first (None when img needs no gradient), then the anchor parameter's (when one trains).
+        fns = [fn for fn, _ in ctx.next_functions]
+        img_node = fns[0] if ctx.needs_input_grad[1] else None
+        anchor = fns[-1] if ctx.nparams else None
+        params = _will_execute(anchor) if anchor is not None else False
+        want_img = img_node is not None and _will_execute(img_node) is not False
+        if params is None or (not params and not want_img):
+            raise L.GavikoHipError("gaviko_amd models write parameter gradients into .grad themselves: use loss.backward() "
+                                   "(torch.autograd.grad(loss, params) / backward(inputs=...) would silently receive None for every "
+                                   "parameter); read the gradients from p.grad afterwards")
         if eng._fwd_gen != ctx.gen:
             raise L.GavikoHipError("backward() of a forward whose saved activations were overwritten by a later training-mode forward of the "
                                    "same model (e.g. loss = f(model(x1), model(x2))): the engine keeps one forward's state -- concatenate "
                                    "the inputs into one batch, or call backward() before the next forward")
+        if not params:
+            # torch.autograd.grad(out, img) / backward(inputs=[img]), or a model with nothing trainable: the input gradient alone -- no
+            # .grad and no byte of the flat gradient buffer changes
+            eng.backward(dlogits, input_grad="only")
+            return (None, eng._ws["dimg"].clone(), None) + (None,) * ctx.nparams
+        ig = "params" if want_img else None
         named = owner._named_cache()[1]
         token = owner.__dict__.get("_grads_zeroed")
         owner.__dict__["_grads_zeroed"] = None
@@ -113,21 +130,21 @@ class _HotPathFn(torch.autograd.Function):
             # requires_grad flip), and the engine would write into a buffer no .grad points at -- re-check against the state at backward.
             views = eng._grad_views(dlogits.device)              # (re-allocates when the trainable set changed)
             if eng._flat_grad is token and all(named[n].grad is v for n, v in views.items()):
-                eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"))
-                return (None, None, None) + (None,) * ctx.nparams
+                eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"), input_grad=ig)
+                return (None, eng._ws["dimg"].clone() if ig else None, None) + (None,) * ctx.nparams
         had_grads = [n for n in eng.trainable_names() if named[n].grad is not None]
         if not had_grads:
-            gv = eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"))
+            gv = eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"), input_grad=ig)
             for n, g in gv.items():
                 named[n].grad = g
         else:                                   # gradient accumulation: keep what is there, add the new contribution
             old = {n: named[n].grad.clone() for n in had_grads}
-            gv = eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"))
+            gv = eng.backward(dlogits, reducer=owner.__dict__.get("_reducer"), input_grad=ig)
             for n, g in gv.items():
                 if n in old:
                     g.add_(old[n])
                 named[n].grad = g
-        return (None, None, None) + (None,) * ctx.nparams
+        return (None, eng._ws["dimg"].clone() if ig else None, None) + (None,) * ctx.nparams
 
 
 class HotPathModule(nn.Module):
@@ -242,6 +259,8 @@ class HotPathModule(nn.Module):
             anchor = next((p for _, p in self._named_cache()[0] if p.requires_grad), None)
             if anchor is not None:
                 return _HotPathFn.apply(self, img, self._drop_config(), anchor)
+            if img.requires_grad:                                   # nothing trains, but the input wants its gradient (saliency)
+                return _HotPathFn.apply(self, img, self._drop_config())
         # no autograd: nothing is saved for a backward, but modules left in training mode still drop (nn.Dropout follows .training)
         return self._engine().forward(img, train=False, drop=self._drop_config())
 

@@ -229,6 +229,38 @@ def patchify(img: torch.Tensor, out: torch.Tensor, patch) -> None:
     L.check(L.load().gvk_patchify_bf16(L.ptr(img), L.ptr(out), B, D, H, W, pd, ph, pw, L.stream_ptr()), "gvk_patchify_bf16")
 
 
+def unpatchify(dcols: torch.Tensor, out: torch.Tensor, patch, *, x=None, x0=None, alpha=1.0, beta=0.0, nsum=1) -> None:
+    """The inverse index map of patchify with attribution arithmetic: out[b] = beta out[b] + sum_{j<nsum} alpha V(b nsum + j) (x[b] - x0[b]),
+    V(s) the volume of the fp32 im2col rows of sample s (x None: no factor; x0 None: 0).  out / x / x0 f32 [B,1,D,H,W]."""
+    _chk(out, torch.float32, "unpatchify out")
+    B, ch, D, H, W = out.shape
+    if ch != 1:
+        raise L.GavikoHipError("unpatchify: single-channel volumes only (channels=1)")
+    pd, ph, pw = patch
+    _chk(dcols, torch.float32, "unpatchify dcols", B * int(nsum) * D * H * W)
+    if x0 is not None and x is None:
+        raise L.GavikoHipError("unpatchify: x0 without x")
+    for t, n in ((x, "x"), (x0, "x0")):
+        if t is not None:
+            _chk(t, torch.float32, "unpatchify " + n, out.numel())
+            if tuple(t.shape) != tuple(out.shape):
+                raise L.GavikoHipError(f"unpatchify {n}: shape {tuple(t.shape)} != out {tuple(out.shape)}")
+    L.check(L.load().gvk_unpatchify_f32(L.ptr(dcols), L.ptr(out), L.ptr(x), L.ptr(x0), B, D, H, W, pd, ph, pw, int(nsum), float(alpha),
+                                        float(beta), L.stream_ptr()), "gvk_unpatchify_f32")
+
+
+def patch_reduce(vol: torch.Tensor, out: torch.Tensor, patch, absval=True) -> None:
+    """out [B, D/pd, H/ph, W/pw] = per-patch sum of |vol| (absval) or of vol, vol f32 [B,1,D,H,W]."""
+    _chk(vol, torch.float32, "patch_reduce vol")
+    B, ch, D, H, W = vol.shape
+    if ch != 1:
+        raise L.GavikoHipError("patch_reduce: single-channel volumes only (channels=1)")
+    pd, ph, pw = patch
+    _chk(out, torch.float32, "patch_reduce out", B * (D // pd) * (H // ph) * (W // pw))
+    L.check(L.load().gvk_patch_reduce_f32(L.ptr(vol), L.ptr(out), B, D, H, W, pd, ph, pw, int(bool(absval)), L.stream_ptr()),
+            "gvk_patch_reduce_f32")
+
+
 def layernorm_fwd(x, gamma, beta, M, C_, *, y16=None, y32=None, mean=None, rstd=None, eps=1e-5):
     if y16 is not None and y16.dtype == torch.float32:       # fp32 compute path: the "operand" output is fp32
         y16, y32 = None, y16
@@ -822,6 +854,31 @@ def evp_highpass(img, hp, depth_mask, out):
     _chk(depth_mask, torch.int32, "evp_highpass depth_mask", D)
     _chk(out, torch.float32, "evp_highpass out", img.numel())
     L.check(L.load().gvk_evp_highpass(L.ptr(img), L.ptr(hp), L.ptr(depth_mask), L.ptr(out), B * ch, D, H, W, L.stream_ptr()), "gvk_evp_highpass")
+
+
+def evp_highpass_sign(img, hp, depth_mask, dout, out):
+    """out = dout o sign(hp . img) on the filtered slices, dout o sign(img) on the others: the modulus step of evp_highpass's backward."""
+    _chk(img, torch.float32, "evp_highpass_sign img")
+    B, ch, D, H, W = img.shape
+    _chk(hp, torch.float32, "evp_highpass_sign hp", H * H)
+    _chk(depth_mask, torch.int32, "evp_highpass_sign depth_mask", D)
+    _chk(dout, torch.float32, "evp_highpass_sign dout", img.numel())
+    _chk(out, torch.float32, "evp_highpass_sign out", img.numel())
+    L.check(L.load().gvk_evp_highpass_sign(L.ptr(img), L.ptr(hp), L.ptr(depth_mask), L.ptr(dout), L.ptr(out), B * ch, D, H, W, L.stream_ptr()),
+            "gvk_evp_highpass_sign")
+
+
+def evp_highpass_linear(x, op, depth_mask, out, accumulate=False):
+    """out (+)= op . x on the filtered slices, x on the others (op = hp^T: the adjoint of the high-pass's linear part)."""
+    _chk(x, torch.float32, "evp_highpass_linear x")
+    B, ch, D, H, W = x.shape
+    _chk(op, torch.float32, "evp_highpass_linear op", H * H)
+    _chk(depth_mask, torch.int32, "evp_highpass_linear depth_mask", D)
+    _chk(out, torch.float32, "evp_highpass_linear out", x.numel())
+    if out.data_ptr() == x.data_ptr():
+        raise L.GavikoHipError("evp_highpass_linear: out must not alias x")
+    L.check(L.load().gvk_evp_highpass_linear(L.ptr(x), L.ptr(op), L.ptr(depth_mask), L.ptr(out), int(bool(accumulate)), B * ch, D, H, W,
+                                             L.stream_ptr()), "gvk_evp_highpass_linear")
 
 
 def pad2d(src, rows, cols, dst, drows, dcols, *, ld_src=None, ld_dst=None, transpose=False):

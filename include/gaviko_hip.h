@@ -266,6 +266,23 @@ int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, const void* d
 int gvk_attention_colsum_bf16(const void* qkv, const float* lse, const float* w, int ld_w, float* out, int B, int T, int H, int ld_qkv,
                               int q0, int q1, void* stream);
 int gvk_rollout_step(const float* r_in, const float* colsum, float* r_out, int B, int T, int H, void* stream);
+/* input gradients for explanations (csrc/input_grad.hip).  The patch embedding is a Conv3d with stride == kernel, so its input gradient is
+ * the im2col gradient dcols f32 [B*nsum*N][pd*ph*pw] (row b*N + n = patch n of sample b in grid order, column (kd*ph + kh)*pw + kw, the
+ * layout of gvk_patchify_*) put back in place:
+ *   out[b] = beta * out[b] + sum_{j < nsum} alpha * V(b*nsum + j) * (x[b] - x0[b])      out, x, x0 f32 [B][1][D][H][W]
+ * V(s) = the volume of dcols sample s; x == NULL drops the factor, x0 == NULL reads as 0; beta == 0 never reads out.  The sum over j is one
+ * FMA per step in order (splitting it over calls with beta = 1 gives the same bits).  pw % 4 == 0, pointers 16-byte aligned.
+ * gvk_patch_reduce_f32: out f32 [B][D/pd][H/ph][W/pw] = per-patch sum of |vol| (absval) or of vol; deterministic.
+ * gvk_evp_highpass_sign / _linear: the backward of gvk_evp_highpass (out = |hp . X| on the slices depth_mask marks, |X| on the others).
+ *   _sign:   out = dout o sign(hp . img)  (marked slices),  dout o sign(img)  (others)     (sign(0) = 0)
+ *   _linear: out (+)= op . x  (marked slices),  x  (others)   -- with op = hp^T the adjoint of the linear part.  out must not alias x. */
+int gvk_unpatchify_f32(const float* dcols, float* out, const float* x, const float* x0, int B, int D, int H, int W, int pd, int ph, int pw,
+                       int nsum, float alpha, float beta, void* stream);
+int gvk_patch_reduce_f32(const float* vol, float* out, int B, int D, int H, int W, int pd, int ph, int pw, int absval, void* stream);
+int gvk_evp_highpass_sign(const float* img, const float* hp, const int32_t* depth_mask, const float* dout, float* out, int B, int D, int H, int W,
+                          void* stream);
+int gvk_evp_highpass_linear(const float* x, const float* op, const int32_t* depth_mask, float* out, int accumulate, int B, int D, int H, int W,
+                            void* stream);
 /* gvk_attention_bwd_bf16 when only the FIRST need_rows tokens of every sample carry a consumer (the bottom layer of a frozen backbone: of its
  * input only the prompt rows hold a trainable tensor, gaviko.py:540-548): dq, dk, dv of tokens < need_rows (rounded up to 128) are written --
  * the very bits the full call writes there -- the other rows of dqkv are left untouched; delta is complete. */
