@@ -22,15 +22,17 @@ constexpr int kDownRows = 16;      // one 16-row MFMA tile per workgroup; the 16
 // Wave w owns the 16-column "super-steps" s = w, w+16, ... of the reduction: a lane (r = lane&15, kq = lane>>4) loads
 // x[row0+r][16s + 4kq .. +3] as one float4 and uses element e as the A operand of MFMA e (k = kq), against
 // W[j = lane&15][16s + 4kq + e] read as one float4 from the LDS copy of W.  Partial 16x32 tiles of the 16 waves are summed
-// through LDS.  A fused LayerNorm is applied algebraically: y = rstd * (x.(g*W) - mean * sum(g*W)) + (beta.W + bias).
+// through LDS.  A fused LayerNorm centres the rows it holds before the product (two-pass statistics, as the row-per-wave kernels) and
+// applies the rest algebraically: y = rstd * ((x - mean).(g*W)) + (beta.W + bias).  The folded form rstd * (x.(g*W) - mean * sum(g*W))
+// cancels two numbers of size |mean| * |g*W| and loses the result when |mean| >> std.
 template <int L>
 __global__ __launch_bounds__(1024) void skinny_down_kernel(DownArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NT = (L + 15) / 16;            // 16-column output tiles
   if (p.drop_thresh != 0u && p.seed_ptr != nullptr) p.seed += *p.seed_ptr;
   const int C = p.C, Cp = C + 4;               // padded LDS row (keeps the b128 operand reads nearly conflict-free)
-  float* cst = (float*)smem;                   // [2][32]  s1_j = sum_c g_c W_jc, s2_j = sum_c b_c W_jc + bias_j
-  float* stat = cst + 64;                      // [16 waves][16 rows][2] partial sum / sum of squares
+  float* cst = (float*)smem;                   // [32]  beta.W_j + bias_j
+  float* stat = cst + 64;                      // [16 waves][16 rows][2] partial sum / sum of squared deviations
   float* ws = stat + 16 * 16 * 2;              // [L][Cp]  (gamma-folded when LN is fused); reused for the partial tiles
   const int lane = lane_id(), wave = wave_id();
   const int r = lane & 15, kq = lane >> 4;
@@ -57,34 +59,61 @@ __global__ __launch_bounds__(1024) void skinny_down_kernel(DownArgs p) {
     ws[j * Cp + c] = v;
   }
   if (threadIdx.x < 64) cst[threadIdx.x] = 0.f;
-  __syncthreads();
-  // per-output constants (one wave per j): s1_j over the folded LDS copy, s2_j = beta.W_j + bias_j
-  for (int j = wave; j < L; j += 16) {
-    float a1 = 0.f, a2 = 0.f;
-    for (int c = lane; c < C; c += 64) {
-      a1 += ws[j * Cp + c];
-      if (ln) a2 += p.ln_b[c] * (p.w_layout == 0 ? p.w[(size_t)j * C + c] : p.w[(size_t)c * L + j]);
+  // ---- input dropout on the held rows, then the first pass of the row statistics over this wave's column slice
+  float s1 = 0.f;
+#pragma unroll
+  for (int u = 0; u < kMaxSteps; ++u) {
+    const int c = 16 * (wave + 16 * u) + 4 * kq;
+    if (live && c < C) {
+      if (p.drop_thresh != 0u) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xv[u][e] *= drop_scale(p.seed, (unsigned long long)row * C + c + e, p.drop_thresh, p.inv_keep);
+      }
+      s1 += xv[u][0] + xv[u][1] + xv[u][2] + xv[u][3];
     }
-    a1 = wave_sum(a1); a2 = wave_sum(a2);
-    if (lane == 0) { cst[j] = a1; cst[32 + j] = a2 + (p.bias ? p.bias[j] : 0.f); }
   }
-  // ---- MFMA over this wave's super-steps, plus the row statistics of its column slice
+  if (ln) {
+    s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
+    if (kq == 0) stat[(wave * 16 + r) * 2] = s1;
+  }
+  __syncthreads();
+  // ---- second pass: every wave sums the 16 partial sums in the same order (the same mean), centres its slice of the row and sums the
+  // squared deviations; the padding columns (c >= C) stay zero
+  float mean = 0.f;
+  if (ln) {
+#pragma unroll
+    for (int w = 0; w < 16; ++w) mean += stat[(w * 16 + r) * 2];
+    mean /= (float)C;
+    float s2 = 0.f;
+#pragma unroll
+    for (int u = 0; u < kMaxSteps; ++u) {
+      const int c = 16 * (wave + 16 * u) + 4 * kq;
+      if (c < C) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { xv[u][e] -= mean; s2 += xv[u][e] * xv[u][e]; }
+      }
+    }
+    s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
+    if (kq == 0) stat[(wave * 16 + r) * 2 + 1] = s2;
+  }
+  // per-output constants (one wave per j): beta.W_j + bias_j
+  for (int j = wave; j < L; j += 16) {
+    float a2 = 0.f;
+    if (ln)
+      for (int c = lane; c < C; c += 64) a2 += p.ln_b[c] * (p.w_layout == 0 ? p.w[(size_t)j * C + c] : p.w[(size_t)c * L + j]);
+    a2 = wave_sum(a2);
+    if (lane == 0) cst[j] = a2 + (p.bias ? p.bias[j] : 0.f);
+  }
+  // ---- MFMA over this wave's super-steps
   f32x4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int u = 0; u < kMaxSteps; ++u) {
     const int st = wave + 16 * u;
     if (st < nsteps) {
       const int c = 16 * st + 4 * kq;
-      f32x4 x4 = xv[u];
-      if (p.drop_thresh != 0u && live && c < C) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x4[e] *= drop_scale(p.seed, (unsigned long long)row * C + c + e, p.drop_thresh, p.inv_keep);
-      }
-      s1 += x4[0] + x4[1] + x4[2] + x4[3];
-      s2 += x4[0] * x4[0] + x4[1] * x4[1] + x4[2] * x4[2] + x4[3] * x4[3];
+      const f32x4 x4 = xv[u];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int j = min(t * 16 + r, L - 1);                       // columns >= L re-read row L-1; their results are discarded
@@ -93,11 +122,6 @@ __global__ __launch_bounds__(1024) void skinny_down_kernel(DownArgs p) {
         for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x4[e], w4[e], acc[t], 0, 0, 0);
       }
     }
-  }
-  if (ln) {
-    s1 += __shfl_xor(s1, 16, 64); s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
-    if (kq == 0) { stat[(wave * 16 + r) * 2] = s1; stat[(wave * 16 + r) * 2 + 1] = s2; }
   }
   __syncthreads();                              // all waves are done reading ws: reuse it for the partial tiles
   float* part = ws;                             // [16 waves][16 rows][32]
@@ -119,16 +143,14 @@ __global__ __launch_bounds__(1024) void skinny_down_kernel(DownArgs p) {
         float a = 0.f, q = 0.f;
 #pragma unroll
         for (int w = 0; w < 16; ++w) { a += stat[(w * 16 + i) * 2]; q += stat[(w * 16 + i) * 2 + 1]; }
-        const float mean = a / (float)C;
-        const float var = fmaxf(q / (float)C - mean * mean, 0.f);
-        const float rstd = rsqrtf(var + p.eps);
+        const float rstd = rsqrtf(q / (float)C + p.eps);
         if (j == 0) {
-          if (p.mean) p.mean[row0 + i] = mean;
+          if (p.mean) p.mean[row0 + i] = a / (float)C;
           if (p.rstd) p.rstd[row0 + i] = rstd;
         }
-        zz = rstd * (dot - mean * cst[j]) + cst[32 + j];
+        zz = rstd * dot + cst[j];
       } else {
-        zz = dot + cst[32 + j];
+        zz = dot + cst[j];
       }
       yv = p.act == 1 ? quick_gelu(zz) : zz;
       if (p.z) p.z[(size_t)(row0 + i) * L + j] = zz;

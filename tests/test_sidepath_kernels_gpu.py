@@ -225,8 +225,13 @@ def _gpa_params(Lat, P, seed):
 @pytest.mark.parametrize("B,P,N", [(2, 32, 1000), (3, 8, 1000)])
 def test_gpa_core_fwd_bwd(dev, B, P, N):
     """gvk_gpa_fwd/bwd vs the oracle's awakening_prompt internals (latent space part) under float64 autograd."""
+    gpa_core_check(dev, B, P, N, 20)
+
+
+def gpa_core_check(dev, B, P, N, Lat):
+    """The GPA core at latent width Lat, P prompts, N local tokens (T = P + 1 + N global rows): every output and gradient against float64
+    autograd (also run at the other widths by test_rank_l_kernels_gpu.py)."""
     from gaviko_amd import ops
-    Lat = 20
     T = P + 1 + N
     prm = _gpa_params(Lat, P, 200)
     zx = _rand((B, T, Lat), 111, 2.0).requires_grad_(True)
