@@ -180,6 +180,7 @@ class Engine(GavikoPaths, PeftPaths):
         self.bucket_layers = 4              # layout of the flat gradient buffer: completion groups of this many layers (set_bucket_layers)
         self._saved = None
         self._pre_is_grad = False
+        self._relv = None                   # the input-only sweep being issued also feeds the attention-relevance kernels (relevance_backward)
         self._igrad = None                  # the backward being issued also carries the gradient to the input volume: None | "params" | "only"
         self._ig_scratch = {}               # input-gradient mode -> scratch gradient targets (a recorded plan keeps their addresses)
         self._conv_t_version = None
@@ -650,6 +651,83 @@ class Engine(GavikoPaths, PeftPaths):
             self._restore_state(keep)
         return logits, ws
 
+    def relevance_backward(self, img: torch.Tensor, seed, mode: str = "relevance", rows="pool", keep_dctx: bool = False):
+        """Gradient x attention of every global self-attention layer, for gaviko_amd.explain: input_backward's deterministic forward and
+        input-only sweep in the 'igrad' workspace, and after the out-projection dgrad of layer i has written ws['dctx'] (= dO of that
+        layer) one gvk_attention_gradcolsum_bf16 on ws['qkv'][i], ws['lse'][i] and ws['dctx'] -> (logits, ws, rv).  No [T, T] matrix and no
+        per-layer copy of dO exists; the launches are part of the sweep's plan (a plan key of its own).
+          mode='relevance': rv['r'] [B, T] = w_pool propagated from the last layer to the first, r <- r + (1 / H) sum_h r^T max(0, P o dP)
+                            (the order the sweep visits the layers); rv['added'] = r - w_pool, accumulated on its own.  The first step reads the pooled rows only: with dead-row pruning
+                            the other rows of the top layer's dctx are not written.
+          mode='maps':      rv['maps'][i] [B, H, T_i] = sum_r w_r max(0, P o dP)[r, :], w uniform over `rows` ('pool' or one row index).
+        keep_dctx (tests on tiny models): rv['keep'][i] is a copy of layer i's dctx.
+        No parameter gradient is written and the state of a pending backward is put back, as for input_backward."""
+        if self.fp32:
+            raise L.GavikoHipError("relevance_backward is built for the bf16 path (the exact-fp32 path keeps no bf16 qkv / dctx)")
+        if mode not in ("relevance", "maps"):
+            raise L.GavikoHipError(f"mode={mode!r}: expected 'relevance' or 'maps'")
+        if mode == "relevance" and len(set(self.Ts)) != 1:
+            raise L.GavikoHipError("the attention relevance needs one token sequence through all layers (deep VPT rebuilds it before every layer)")
+        keep = self._pending_state()
+        try:
+            logits = self.forward(img, train=True, drop=None, ws_tag="igrad")
+            ws = self._ws
+            self._relv = rv = self._relv_buffers(ws, mode, rows, bool(keep_dctx), img.device)
+            try:
+                self.backward(seed(logits), input_grad="only")
+            finally:
+                self._relv = None
+        finally:
+            self._restore_state(keep)
+        return logits, ws, rv
+
+    def _relv_buffers(self, ws, mode, rows, keep_dctx, device) -> dict:
+        """The relevance buffers of one (mode, rows, keep_dctx), in the workspace: a recorded plan keeps their addresses."""
+        key = (mode, rows, keep_dctx)
+        rv = ws.setdefault("relv", {}).get(key)
+        if rv is not None:
+            return rv
+        B, H, L_ = ws["B"], self.heads, self.depth
+        r0, R = self._pool_rows()
+        rng = [((0, self.Ts[i]) if (self.pool == "mean" and self.kind not in ("gaviko", "dvpt")) else (r0, r0 + R)) if rows == "pool"
+               else (rows, rows + 1) for i in range(L_)]
+        rv = dict(key=key, mode=mode, rows=rng, keep=[torch.zeros_like(ws["dctx"]) for _ in range(L_)] if keep_dctx else None,
+                  allrows=rows != "pool")
+        def uniform(q0, q1, T):
+            w = torch.zeros((B, T), device=device)
+            w[:, q0:q1] = 1.0 / (q1 - q0)
+            return w
+        if mode == "relevance":
+            rv["w0"] = uniform(*rng[-1], self.T)
+            rv["r"] = torch.zeros((B, self.T), device=device)
+            rv["added"] = torch.zeros((B, self.T), device=device)        # r - w_pool, accumulated on its own
+            rv["cs"] = torch.zeros((B, H, self.T), device=device)
+        else:
+            rv["w"] = [uniform(*rng[i], self.Ts[i]) for i in range(L_)]
+            rv["maps"] = [torch.zeros((B, H, self.Ts[i]), device=device) for i in range(L_)]
+        ws["relv"][key] = rv
+        return rv
+
+    def _relv_layer(self, ws, i, B, T):
+        """Main stream, right after the out-projection dgrad of layer i: ws['dctx'] holds dO of this layer."""
+        rv, H = self._relv, self.heads
+        if rv["keep"] is not None:
+            ops.copy_(rv["keep"][i], ws["dctx"])
+        if rv["mode"] == "relevance":
+            q0, q1 = 0, T
+            if i == self.depth - 1:                         # r = w_pool: zero outside the pooled rows, which are all the first step reads
+                ops.copy_(rv["r"], rv["w0"])
+                ops.memset_zero(rv["added"])
+                q0, q1 = rv["rows"][i]
+            ops.attention_gradcolsum(ws["qkv"][i], ws["lse"][i], ws["dctx"], rv["r"], rv["cs"], B, T, H, q0=q0, q1=q1)
+            # The added part is 1e-3 .. 1e-5 of w_pool on the pooled rows: summed into r itself it would lose its low bits to w_pool's
+            # exponent at every layer.  It is accumulated on its own and r = w_pool + added is rounded once per layer.
+            ops.relevance_step(rv["added"], rv["cs"], rv["added"], B, T, H)
+            ops.add2d(rv["w0"], T, rv["added"], T, rv["r"], T, B, T)
+        else:
+            q0, q1 = rv["rows"][i]
+            ops.attention_gradcolsum(ws["qkv"][i], ws["lse"][i], ws["dctx"], rv["w"][i], rv["maps"][i], B, T, H, q0=q0, q1=q1)
+
     def input_buffer(self, B: int, device, train: bool = True) -> torch.Tensor:
         """The static [B,1,D,H,W] input slot of the (B, train) workspace: a data pipeline that writes its batch here (and passes this very
         tensor to the model) saves the per-step device copy."""
@@ -978,6 +1056,8 @@ class Engine(GavikoPaths, PeftPaths):
             ws["dlogits"].copy_(dlogits.detach())
         flat = self._flat_grad["buf"] if ig != "only" else None
         saved_key = self._saved_key + (("ig", ig),) if ig else self._saved_key
+        if self._relv is not None:
+            saved_key += (("relv",) + self._relv["key"],)
         if ig == "only":
             keep = self._flat_grad
             self._flat_grad = self._ig_scratch["only"]        # the kernels that address the flat buffer directly write the scratch
@@ -1092,6 +1172,8 @@ class Engine(GavikoPaths, PeftPaths):
         # pos_embedding carry none), so its qkv dgrad and LayerNorm-1 backward run on those rows.
         frozen = gaviko and not bb and sv.get("bdrop", 0.0) <= 0 and not sv["wgrad"]
         top = self._panels(B, sum(self._pool_rows())) if (frozen and first) else {}
+        if self._relv is not None and self._relv["allrows"]:
+            top = {}                                           # a map of a row the head does not pool reads that row of the top layer's dctx
         bot = self._panels(B, self.P) if (frozen and last and self.P > 0 and not self._igrad) else {}     # (the input gradient reads every row)
         prev_scl = None
         for i in range(hi, lo - 1, -1):
@@ -1249,6 +1331,8 @@ class Engine(GavikoPaths, PeftPaths):
             self._bb_linear_grads(ws, gv, bb, a + ".to_out.0", dy_at, ws["dG16"], ws["ctx"][i], M, C, C)
         self._gemm(ws["dG16"], w[f"out{i}_t"], M, ws["dctx"], epilogue=ops.EPI_STORE_BF16)
         self._mark(f"b{i}:outd")
+        if self._relv is not None:
+            self._relv_layer(ws, i, B, T)
         # (bottom layer of a frozen backbone: only dq / dk / dv of the prompt rows are read -- by the row-panel qkv dgrad below)
         ops.attention_bwd(ws["qkv"][i], ws["ctx"][i], ws["dctx"], ws["lse"][i], ws["delta"], ws["dqkv"], B, T, self.heads, 64 ** -0.5,
                           drop_p=pd_, seed=SEED_LAYER + 8 * i, seed_ptr=ws["seed"], q_prescaled=True, need_rows=self.P if bot else None)

@@ -12,6 +12,16 @@ row-weighted sums of P from them, as the backward recomputes P from lse.
 
 Only the bf16 path and the global self-attention are covered; the MWSA local attention and the GPA cross-attention are not.
 
+The class-specific token-level map is the gradient-weighted attention relevance of Chefer, Gur & Wolf (2021, "Generic Attention-model
+Explainability"): with A_l the attention probabilities of layer l and dA_l = d logit[b, target[b]] / d A_l,
+Abar_l = mean_h max(0, A_l o dA_l) and R = (I + Abar_{L-1}) ... (I + Abar_0); the relevance is the pooled query's row of R.  In the
+reference that is a hook on `attend` with retain_grad(); here dA_l = dO_l . V_l^T is recomputed tile by tile from the dO the input-only
+backward sweep produces anyway (Engine.relevance_backward), layer by layer in the order the sweep visits them, so neither a T x T matrix
+nor a per-layer copy of dO exists (gvk_attention_gradcolsum_bf16, gvk_relevance_step).
+
+    logits, rel = attention_relevance(model, img, target=None)   # rel: [B, T] >= w_pool, not normalised; patch_grid(model, rel)
+    logits, gmaps = attention_gradmaps(model, img)               # gmaps[i]: [B, H, T_i] = sum_r w_r max(0, A_i o dA_i)[b, h, r, :]
+
 Gradient attributions cover every module of every method, on both precision paths: the gradient of a logit with respect to the input
 volume, from a deterministic (no-dropout) forward and an input-only backward in a workspace of their own (Engine.input_backward; no
 parameter gradient changes), un-patchified by csrc/input_grad.hip with the attribution arithmetic in the same pass.
@@ -107,6 +117,57 @@ def attention_rollout(model, img: torch.Tensor) -> Tuple[torch.Tensor, torch.Ten
         ops.rollout_step(r, cs, r, B, T, H)
         q0, q1 = 0, T
     return logits, r
+
+
+def _relevance_checks(model, img, target, what):
+    """Everything attention_relevance / attention_gradmaps reject, before any launch -> (engine, contiguous volume, seed)."""
+    eng = model._engine()
+    if eng.fp32:
+        raise L.GavikoHipError(f"{what} is built for the bf16 path: the exact-fp32 path (set_precision('fp32')) keeps no bf16 qkv / lse / "
+                               "dctx for the map kernels")
+    want = (1,) + tuple(g * p for g, p in zip(eng.grid, eng.patch))
+    if not isinstance(img, torch.Tensor) or img.dim() != 5 or tuple(img.shape[1:]) != want or img.shape[0] < 1:
+        raise L.GavikoHipError(f"{what}: expected img [B, {', '.join(map(str, want))}], got {tuple(getattr(img, 'shape', ()))}")
+    if img.dtype != torch.float32:
+        raise L.GavikoHipError(f"{what}: expected a float32 volume, got {img.dtype}")
+    B = img.shape[0]
+    if target is not None:
+        _targets(eng, torch.zeros((B, eng.K)), target, B)            # a bad target is rejected here (host tensors only)
+    eng, x = _volume_check(model, img, what)                         # (and the device)
+
+    def seed(logits):
+        return torch.nn.functional.one_hot(_targets(eng, logits, target, B), eng.K).to(logits.dtype)
+
+    return eng, x, seed
+
+
+def attention_relevance(model, img: torch.Tensor, target=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (logits [B, K], relevance [B, T] float32): the gradient-weighted attention relevance of the logit target[b] (None: the argmax
+    per sample, an int, or a [B] tensor) --  r = w_pool;  for l = L-1 .. 0:  r <- r + r^T mean_h max(0, A_l o dA_l).  Not normalised;
+    r >= w_pool elementwise (the identity term), so the class-specific part is r - w_pool."""
+    eng = model._engine()
+    if eng.kind == "vpt" and eng.deep:
+        raise L.GavikoHipError("attention relevance needs one token sequence through all layers; deep VPT rebuilds it before every layer "
+                               "(vpt.py:147-153) -- use attention_gradmaps")
+    eng, x, seed = _relevance_checks(model, img, target, "attention_relevance")
+    with torch.no_grad():
+        logits, _, rv = eng.relevance_backward(x, seed, mode="relevance")
+        return logits, rv["r"].clone()
+
+
+def attention_gradmaps(model, img: torch.Tensor, target=None, rows: Union[str, int] = "pool") -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """-> (logits [B, K], maps): maps[i] is a float32 [B, H, T_i] device tensor, maps[i][b, h, j] = sum_r w_r max(0, A_i o dA_i)[b, h, r, j]
+    with w uniform over the selected query rows (attention_maps' `rows`) and dA_i the gradient of the logit target[b] with respect to the
+    probabilities of layer i: per head, not propagated -- the class-specific counterpart of attention_maps."""
+    eng = model._engine()
+    if isinstance(rows, bool) or not (rows == "pool" or isinstance(rows, int)):
+        raise L.GavikoHipError(f"rows={rows!r}: expected 'pool' or a query row index")
+    if isinstance(rows, int) and not 0 <= rows < min(eng.Ts):
+        raise L.GavikoHipError(f"rows={rows}: query row outside [0, {min(eng.Ts)}) (the shortest layer's sequence)")
+    eng, x, seed = _relevance_checks(model, img, target, "attention_gradmaps")
+    with torch.no_grad():
+        logits, _, rv = eng.relevance_backward(x, seed, mode="maps", rows=rows)
+        return logits, [m.clone() for m in rv["maps"]]
 
 
 def patch_grid(model, relevance: torch.Tensor) -> torch.Tensor:

@@ -129,6 +129,8 @@ SIGNATURES = {
     "gvk_attention_bwd_bf16_fused": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _F, _P],
     "gvk_attention_colsum_bf16": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "gvk_rollout_step": [_P, _P, _P, _I, _I, _I, _P],
+    "gvk_attention_gradcolsum_bf16": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
+    "gvk_relevance_step": [_P, _P, _P, _I, _I, _I, _P],
     "gvk_unpatchify_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
     "gvk_patch_reduce_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_evp_highpass_sign": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -470,6 +470,32 @@ def rollout_step(r_in, colsum, r_out, B, T, H):
     L.check(L.load().gvk_rollout_step(L.ptr(r_in), L.ptr(colsum), L.ptr(r_out), B, T, H, L.stream_ptr()), "gvk_rollout_step")
 
 
+def attention_gradcolsum(qkv, lse, dctx, w, out, B, T, H, q0=0, q1=None):
+    """out f32 [B,H,T] = sum_{q0 <= i < q1} w[b,i] * P[b,h,i,:] * max(0, dP[b,h,i,:]), dP = dO . v^T -- gradient x attention, recomputed
+    from the bf16 forward's qkv / lse (attention_colsum's operands) and the backward sweep's dctx bf16 [pad(B*T), H*64] (= dO)."""
+    q1 = T if q1 is None else q1
+    _chk(qkv, torch.bfloat16, "gradcolsum qkv", pad_rows(B * T) * 3 * H * 64)
+    _chk(dctx, torch.bfloat16, "gradcolsum dctx", pad_rows(B * T) * H * 64)
+    _chk(lse, torch.float32, "gradcolsum lse", B * H * T)
+    _chk(out, torch.float32, "gradcolsum out", B * H * T)
+    _chk(w, torch.float32, "gradcolsum w", B * T)
+    ld_w = w.shape[-1] if w.dim() == 2 else T
+    if ld_w < T or w.numel() < B * ld_w:
+        raise L.GavikoHipError(f"gradcolsum w: expected [B, >= T] = [{B}, >= {T}], got {tuple(w.shape)}")
+    if not 0 <= q0 < q1 <= T:
+        raise L.GavikoHipError(f"gradcolsum: query rows [{q0}, {q1}) outside [0, {T})")
+    L.check(L.load().gvk_attention_gradcolsum_bf16(L.ptr(qkv), L.ptr(lse), L.ptr(dctx), H * 64, L.ptr(w), ld_w, L.ptr(out), B, T, H, 3 * H * 64,
+                                                   int(q0), int(q1), L.stream_ptr()), "gvk_attention_gradcolsum_bf16")
+
+
+def relevance_step(r_in, cs, r_out, B, T, H):
+    """r_out f32 [B,T] = r_in + (1 / H) sum_h cs[:, h] (cs f32 [B,H,T], attention_gradcolsum's output; r_out may be r_in)."""
+    _chk(r_in, torch.float32, "relevance r_in", B * T)
+    _chk(r_out, torch.float32, "relevance r_out", B * T)
+    _chk(cs, torch.float32, "relevance cs", B * H * T)
+    L.check(L.load().gvk_relevance_step(L.ptr(r_in), L.ptr(cs), L.ptr(r_out), B, T, H, L.stream_ptr()), "gvk_relevance_step")
+
+
 def _desc(cls, what, **kw):
     """Fill a descriptor struct: tensors -> device pointers (validated fp32, contiguous, on device), None -> NULL."""
     d = cls()

@@ -266,6 +266,15 @@ int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, const void* d
 int gvk_attention_colsum_bf16(const void* qkv, const float* lse, const float* w, int ld_w, float* out, int B, int T, int H, int ld_qkv,
                               int q0, int q1, void* stream);
 int gvk_rollout_step(const float* r_in, const float* colsum, float* r_out, int B, int T, int H, void* stream);
+/* class-specific attention relevance (gradient x attention; Chefer, Gur & Wolf 2021, "Generic Attention-model Explainability"): with
+ * dO = the gradient of one logit with respect to the attention output (bf16 [B*T][ld_dctx], head h in columns 64 h .. 64 h + 63 -- the
+ * backward sweep's dctx), dP[b][h][i][j] = dO[b][i][h][:] . v[b][j][h][:] is that logit's gradient with respect to P, and
+ *   out f32 [B][H][T]  out[b][h][j] = sum_{q0 <= i < q1} w[b][i] * P[b][h][i][j] * max(0, dP[b][h][i][j])   for j < T
+ * with P, w, q0, q1 as in gvk_attention_colsum_bf16; P and dP stay fp32.  Deterministic (no atomics).
+ * gvk_relevance_step: r_out[b][j] = r_in[b][j] + (1 / H) * sum_h out[b][h][j]   (heads summed in order; r_out may alias r_in). */
+int gvk_attention_gradcolsum_bf16(const void* qkv, const float* lse, const void* dctx, int ld_dctx, const float* w, int ld_w, float* out, int B,
+                                  int T, int H, int ld_qkv, int q0, int q1, void* stream);
+int gvk_relevance_step(const float* r_in, const float* colsum, float* r_out, int B, int T, int H, void* stream);
 /* input gradients for explanations (csrc/input_grad.hip).  The patch embedding is a Conv3d with stride == kernel, so its input gradient is
  * the im2col gradient dcols f32 [B*nsum*N][pd*ph*pw] (row b*N + n = patch n of sample b in grid order, column (kd*ph + kh)*pw + kw, the
  * layout of gvk_patchify_*) put back in place:

@@ -2,7 +2,9 @@
   * the column-sum kernel alone at cfg2 (B=4, T=1033, H=12) and cfg5 (ViT-L: B=2, T=1033, H=16), pooled (the 33 prompt + CLS rows of
     GAViKO) and dense (all rows: every rollout step after the first); flops = 2 B H (q1 - q0) T 64 (the score product);
   * the rollout step kernel alone (the separate form: DESIGN kernel table);
-  * attention_rollout against one no-grad forward of the cfg2 model (ViT-B GAViKO, B=4).
+  * the gradient column-sum kernel (gradient x attention: a second MFMA chain for dP = dO . V^T) and the relevance step, same shapes;
+  * attention_rollout against one no-grad forward of the cfg2 model (ViT-B GAViKO, B=4);
+  * attention_relevance and attention_gradmaps against input_gradient (the same forward + input-only sweep without the 12 launches).
 Every kernel figure is the median of 7 rounds of 50 launches recorded into one launch plan.
 usage: python tools/bench_explain.py [--out FILE.jsonl]"""
 import json
@@ -60,6 +62,14 @@ def kernels(name, B, T, H, pooled_rows):
         res.append(dict(shape=name, kernel="colsum", form=form, B=B, T=T, H=H, rows=q1, us=round(us, 2), tflops=round(fl / us * 1e-6, 1)))
     us = plan_time_us(lambda: ops.rollout_step(r, out, r, B, T, H))
     res.append(dict(shape=name, kernel="rollout_step", B=B, T=T, H=H, us=round(us, 2)))
+    dctx = ops.act_zeros(B * T, inner, torch.bfloat16, dev)
+    dctx[: B * T] = (torch.randn(B * T, inner, device=dev) * 1e-3).bfloat16()
+    for form, q1 in (("pooled", pooled_rows), ("dense", T)):
+        us = plan_time_us(lambda: ops.attention_gradcolsum(qkv, lse, dctx, w, out, B, T, H, q0=0, q1=q1))
+        fl = 4.0 * B * H * q1 * T * 64
+        res.append(dict(shape=name, kernel="gradcolsum", form=form, B=B, T=T, H=H, rows=q1, us=round(us, 2), tflops=round(fl / us * 1e-6, 1)))
+    us = plan_time_us(lambda: ops.relevance_step(r, out, r, B, T, H))
+    res.append(dict(shape=name, kernel="relevance_step", B=B, T=T, H=H, us=round(us, 2)))
     fa = plan_time_us(lambda: ops.attention_fwd(qkv, o, lse, B, T, H, 0.125, q_prescaled=True))
     res.append(dict(shape=name, kernel="attention_fwd (for scale)", B=B, T=T, H=H, us=round(fa, 2)))
     return res
@@ -97,7 +107,15 @@ def whole_rollout():
     eng = m._engine()
     efwd = timed(lambda: eng.attention_forward(x))
     roll = timed(lambda: explain.attention_rollout(m, x))
-    return [dict(shape="cfg2 model", what="no-grad forward", ms=round(fwd, 3)),
+    igrad = timed(lambda: explain.input_gradient(m, x))
+    relv = timed(lambda: explain.attention_relevance(m, x))
+    gmaps = timed(lambda: explain.attention_gradmaps(m, x))
+    more = [dict(shape="cfg2 model", what="input_gradient (forward + input-only sweep + un-patchify)", ms=round(igrad, 3)),
+            dict(shape="cfg2 model", what="attention_relevance (the same sweep + 12 gradient column sums + 12 steps)", ms=round(relv, 3)),
+            dict(shape="cfg2 model", what="attention_gradmaps (the same sweep + 12 pooled gradient column sums)", ms=round(gmaps, 3)),
+            dict(shape="cfg2 model", what="relevance beyond input_gradient", ms=round(relv - igrad, 3)),
+            dict(shape="cfg2 model", what="input_gradient + 2 x rollout-beyond-forward (the expected ceiling)", ms=round(igrad + 2 * (roll - efwd), 3))]
+    return more + [dict(shape="cfg2 model", what="no-grad forward", ms=round(fwd, 3)),
             dict(shape="cfg2 model", what="explanation forward (keeps qkv / lse)", ms=round(efwd, 3)),
             dict(shape="cfg2 model", what="attention_rollout (forward + 12 column sums + 12 steps)", ms=round(roll, 3)),
             dict(shape="cfg2 model", what="rollout beyond its forward", ms=round(roll - efwd, 3))]
