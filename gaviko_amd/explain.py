@@ -10,7 +10,21 @@ row-weighted sums of P from them, as the backward recomputes P from lse.
     logits, rel = attention_rollout(model, img)          # rel: [B, T], sums to 1 per sample
     grid = patch_grid(model, rel)                        # [B, D/pd, H/ph, W/pw]
 
-Only the bf16 path and the global self-attention are covered; the MWSA local attention and the GPA cross-attention are not.
+These three cover the global self-attention on the bf16 path.  The parts that make the model GAViKO -- the MWSA local attention
+(gaviko.py:235-238) and the two GPA prompt cross-attentions with their gates (gaviko.py:84-94,164-178) -- have functions of their own, on
+BOTH precision paths (the side paths are fp32 either way): the same keep-everything forward leaves every layer's MWSA qkv / lse and GPA
+latents, queries, statistics and gates, and csrc/gaviko_maps.hip turns them back into probabilities.
+
+    logits, lmaps = local_attention_maps(model, img, rows="all")  # lmaps[i]: [B, N] = sum_r w_r P_i[b, r, :]; .view(B, *grid) is patch_grid's layout
+    logits, gpa = gpa_attention_maps(model, img)                  # gpa[i]: GpaMaps(global_, local, fused [B, P, N]; importance [B, P]; global_weight [B])
+    logits, rel = local_rollout(model, img, start=None, layer=None)   # rel: [B, N], sums to sum(start) per sample
+
+gpa[i].fused[b, p, n] is exactly the coefficient with which patch position n enters enhanced prompt p of layer i.  The reference slices the
+image tokens twice on the global side (gaviko.py:161,107), so gpa[i].global_ is 0 at the first P + 1 patch positions.  The image footprint of
+layer i's prompts through the local path is the composition
+
+    _, gpa = gpa_attention_maps(model, img)
+    _, rel = local_rollout(model, img, start=gpa[i].local.mean(1), layer=i)      # rel.view(B, *grid)
 
 The class-specific token-level map is the gradient-weighted attention relevance of Chefer, Gur & Wolf (2021, "Generic Attention-model
 Explainability"): with A_l the attention probabilities of layer l and dA_l = d logit[b, target[b]] / d A_l,
@@ -33,7 +47,7 @@ parameter gradient changes), un-patchified by csrc/input_grad.hip with the attri
 """
 from __future__ import annotations
 
-from typing import List, Tuple, Union
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -332,3 +346,99 @@ def patch_saliency(model, volume_map: torch.Tensor, reduce: str = "abs") -> torc
     out = torch.empty((v.shape[0],) + tuple(eng.grid), device=v.device)
     ops.patch_reduce(v, out, eng.patch, absval=reduce == "abs")
     return out
+
+
+# ---- GAViKO's own attentions: MWSA local attention and GPA prompt cross-attention ------------------------------------------------
+class GpaMaps(NamedTuple):
+    """One GPA layer: the prompts' cross-attention over the patch positions through the global and the local path, their gated fusion
+    fused = importance * (global_weight * global_ + (1 - global_weight) * local)  [B, P, N], and the two gates as the forward kept them."""
+    global_: torch.Tensor
+    local: torch.Tensor
+    fused: torch.Tensor
+    importance: torch.Tensor
+    global_weight: torch.Tensor
+
+
+def _gaviko_forward(model, img, what):
+    """Everything the three functions below reject, then one deterministic keep-everything forward -> (engine, logits, workspace)."""
+    eng = model._engine()
+    if eng.kind != "gaviko":
+        raise L.GavikoHipError(f"{what}: the MWSA local attention and the GPA prompt attention exist in GAViKO models only (this engine "
+                               f"is {eng.kind!r})")
+    eng, x = _volume_check(model, img, what)
+    logits, ws = _forward(eng, x)
+    return eng, logits.detach(), ws
+
+
+def _window_colsum(eng, ws, i, w, out):
+    m = ws["mw"][i]
+    ops.window_attn_colsum(m["qkv"], m["lse"], w, out, ws["B"], eng.grid[0], eng.grid[1], eng.grid[2], eng.win[0], eng.win[1], eng.win[2],
+                           eng.Lat, eng.C ** -0.5)
+
+
+def local_attention_maps(model, img: torch.Tensor, rows: Union[str, int, torch.Tensor] = "all") -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """-> (logits [B, K], maps): maps[i] is a float32 [B, N] device tensor, maps[i][b, j] = sum_r w[b, r] P_i[b, r, j] with P_i the
+    masked-window attention probabilities of layer i (gaviko.py:235-238) -- rows='all': w = 1 / N (how much attention each patch
+    RECEIVES); an int: that query's window (zeros outside it); a float32 device tensor [B, N]: those weights."""
+    eng = model._engine()
+    N = getattr(eng, "N", 0)
+    if isinstance(rows, bool) or not (isinstance(rows, (int, torch.Tensor)) or rows == "all"):
+        raise L.GavikoHipError(f"rows={rows!r}: expected 'all', a query row index or a float32 [B, N] weight tensor")
+    if isinstance(rows, int) and eng.kind == "gaviko" and not 0 <= rows < N:
+        raise L.GavikoHipError(f"rows={rows}: query row outside [0, {N})")
+    eng, logits, ws = _gaviko_forward(model, img, "local_attention_maps")
+    B, dev = ws["B"], img.device
+    if isinstance(rows, torch.Tensor):
+        if tuple(rows.shape) != (B, N) or rows.dtype != torch.float32 or not rows.is_cuda:
+            raise L.GavikoHipError(f"rows: expected a float32 device tensor [{B}, {N}], got {tuple(rows.shape)} {rows.dtype} on {rows.device}")
+        w = rows.detach().contiguous()
+    elif rows == "all":
+        w = torch.full((B, N), 1.0 / N, device=dev)
+    else:
+        w = torch.zeros((B, N), device=dev)
+        w[:, rows] = 1.0
+    maps = []
+    for i in range(eng.depth):
+        out = torch.empty((B, N), device=dev)
+        _window_colsum(eng, ws, i, w, out)
+        maps.append(out)
+    return logits, maps
+
+
+def gpa_attention_maps(model, img: torch.Tensor) -> Tuple[torch.Tensor, List[GpaMaps]]:
+    """-> (logits [B, K], one GpaMaps per LAYER (shared modules do not share activations)): float32 device tensors of their own."""
+    eng, logits, ws = _gaviko_forward(model, img, "gpa_attention_maps")
+    B, P, N, dev = ws["B"], eng.P, eng.N, img.device
+    res = []
+    for i in range(eng.depth):
+        g = ws["gp"][i]
+        pg, pl, fu = (torch.empty((B, P, N), device=dev) for _ in range(3))
+        ops.gpa_attn_maps(g["xl"], g["ll"], g["qg"], g["ql"], g["lse_g"], g["lse_l"], g["imp"], g["gw"], B, eng.T, N, P, eng.Lat,
+                          global_=pg, local=pl, fused=fu)
+        res.append(GpaMaps(pg, pl, fu, g["imp"].clone(), g["gw"].clone()))
+    return logits, res
+
+
+def local_rollout(model, img: torch.Tensor, start: Optional[torch.Tensor] = None, layer: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (logits [B, K], relevance [B, N] float32, summing to sum(start) per sample): attention rollout on the single-head local stream
+    (gaviko.py:301) with attention_rollout's residual convention --  r = start (None: 1 / N) at the output of layer `layer` (None: the
+    last);  for l = layer .. 0:  r <- 0.5 r + 0.5 r^T P_l."""
+    eng = model._engine()
+    depth = eng.depth
+    if layer is not None and (isinstance(layer, bool) or not isinstance(layer, int) or not 0 <= layer < depth):
+        raise L.GavikoHipError(f"layer={layer!r}: expected None or a layer index in [0, {depth})")
+    if start is not None and not isinstance(start, torch.Tensor):
+        raise L.GavikoHipError(f"start={start!r}: expected None or a float32 device tensor [B, N]")
+    eng, logits, ws = _gaviko_forward(model, img, "local_rollout")
+    B, N, dev = ws["B"], eng.N, img.device
+    if start is None:
+        r = torch.full((B, N), 1.0 / N, device=dev)
+    else:
+        if tuple(start.shape) != (B, N) or start.dtype != torch.float32 or not start.is_cuda:
+            raise L.GavikoHipError(f"start: expected a float32 device tensor [{B}, {N}], got {tuple(start.shape)} {start.dtype} on {start.device}")
+        r = start.detach().clone().contiguous()
+    cs = torch.empty((B, N), device=dev)
+    for l in range(depth - 1 if layer is None else layer, -1, -1):
+        _window_colsum(eng, ws, l, r, cs)
+        ops.rollout_step(r, cs, r, B, N, 1)                   # the single head: mean head fusion over H = 1
+    return logits, r

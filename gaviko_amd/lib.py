@@ -93,6 +93,8 @@ ReduceJob = _struct("ReduceJob", ["a", "b", "out", "a2"], ["M", "J", "L", "accum
 PgradOuter = _struct("PgradOuter", ["narrow", "wide", "narrow2", "wide2", "lat_override", "mean", "rstd", "out", "colsum",
                                     "aff_w", "aff_gamma", "aff_beta", "aff_dgamma", "aff_dbeta", "aff_dbias"],
                      ["M", "M2", "T", "P", "transposed", "accumulate", "C"], ["drop_p"], ["seed"])
+WindowColsumDesc = _struct("WindowColsumDesc", ["qkv", "lse", "w", "out"], ["B", "D", "H", "W", "kd", "kh", "kw", "L"], ["scale"])
+GpaMapsDesc = _struct("GpaMapsDesc", ["xl", "ll", "qg", "ql", "lse_g", "lse_l", "imp", "gw", "pg", "pl", "fused"], ["B", "T", "N", "P", "L"])
 HeadDesc = _struct("HeadDesc", ["g", "ln_gamma", "ln_beta", "wh", "bh", "logits", "pooled", "dlogits", "dg", "dwh", "dbh"],
                    ["B", "T", "C", "K", "r0", "R", "accumulate"])
 
@@ -151,6 +153,8 @@ SIGNATURES = {
     "gvk_window_attn_bwd": [C.POINTER(WindowAttnDesc), _P],
     "gvk_gpa_fwd": [C.POINTER(GpaDesc), _P],
     "gvk_gpa_bwd": [C.POINTER(GpaDesc), _P],
+    "gvk_window_attn_colsum": [C.POINTER(WindowColsumDesc), _P],
+    "gvk_gpa_attn_maps": [C.POINTER(GpaMapsDesc), _P],
     "gvk_rows_broadcast": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_rows_batch_sum": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "gvk_small_linear_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
@@ -205,7 +209,7 @@ NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, [
              "gvk_plan_set_timing": (C.c_int, [C.c_int]),
              "gvk_plan_event_elapsed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)])}
 STRUCTS = {"gvk_gemm_desc": GemmDesc, "gvk_skinny_down_desc": SkinnyDownDesc, "gvk_skinny_up_desc": SkinnyUpDesc,
-           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc}
+           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc}
 
 # diag library only (include/gaviko_hip_diag.h): bound when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so
 DIAG_SIGNATURES = {}

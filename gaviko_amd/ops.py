@@ -636,6 +636,56 @@ def gpa_bwd(**kw):
     L.check(L.load().gvk_gpa_bwd(C.byref(d), L.stream_ptr()), "gvk_gpa_bwd")
 
 
+_MAP_WIDTHS = (4, 8, 16, 20, 32)
+
+
+def window_attn_colsum(qkv, lse, w, out, B, D, H, W, kd, kh, kw, L_, scale):
+    """out f32 [B, N] = sum_i w[b, i] * P[b, i, :] -- the weighted rows of the MWSA probabilities (N = D*H*W), recomputed from
+    window_attn_fwd's operands: qkv f32 [B*N, 3L], lse f32 [B*N], the grid (D, H, W), the window (kd, kh, kw), scale.  w f32 [B, N]."""
+    dims = (B, D, H, W, kd, kh, kw)
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in dims):
+        raise L.GavikoHipError(f"window_attn_colsum: B, grid and window must be positive ints, got {dims}")
+    if L_ not in _MAP_WIDTHS:
+        raise L.GavikoHipError(f"window_attn_colsum: L={L_} unsupported {_MAP_WIDTHS}")
+    N = D * H * W
+    _chk(qkv, torch.float32, "window_attn_colsum qkv", B * N * 3 * L_)
+    _chk(lse, torch.float32, "window_attn_colsum lse", B * N)
+    _chk(w, torch.float32, "window_attn_colsum w", B * N)
+    _chk(out, torch.float32, "window_attn_colsum out", B * N)
+    if any(t is None for t in (qkv, lse, w, out)):
+        raise L.GavikoHipError("window_attn_colsum: qkv, lse, w and out are all required")
+    d = _desc(L.WindowColsumDesc, "window_attn_colsum", qkv=qkv, lse=lse, w=w, out=out, B=B, D=D, H=H, W=W, kd=kd, kh=kh, kw=kw, L=L_,
+              scale=float(scale))
+    L.check(L.load().gvk_window_attn_colsum(C.byref(d), L.stream_ptr()), "gvk_window_attn_colsum")
+
+
+def gpa_attn_maps(xl, ll, qg, ql, lse_g, lse_l, imp, gw, B, T, N, P, L_, *, global_=None, local=None, fused=None):
+    """The cross-attention probabilities of one GPA layer from gpa_fwd's saved buffers (xl f32 [B*T, L], ll [B*N, L], qg / ql [B, P, L]
+    pre-scaled, lse_g / lse_l / imp [B, P], gw [B]) -> global_, local, fused f32 [B, P, N], each optional (at least one):
+    fused = imp * (gw * global_ + (1 - gw) * local).  global_ is 0 at the first P + 1 patch positions (the reference's double slice)."""
+    dims = (B, T, N, P)
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in dims):
+        raise L.GavikoHipError(f"gpa_attn_maps: B, T, N, P must be positive ints, got {dims}")
+    if L_ not in _MAP_WIDTHS:
+        raise L.GavikoHipError(f"gpa_attn_maps: L={L_} unsupported {_MAP_WIDTHS}")
+    if P > 64 or T != P + 1 + N or N <= P + 1:
+        raise L.GavikoHipError(f"gpa_attn_maps: need P <= 64, T = P + 1 + N and N > P + 1 (global image tokens left after the double "
+                               f"slice), got T={T} N={N} P={P}")
+    ins = dict(xl=(xl, B * T * L_), ll=(ll, B * N * L_), qg=(qg, B * P * L_), ql=(ql, B * P * L_), lse_g=(lse_g, B * P), lse_l=(lse_l, B * P),
+               imp=(imp, B * P), gw=(gw, B))
+    for name, (t, n) in ins.items():
+        if t is None:
+            raise L.GavikoHipError(f"gpa_attn_maps: {name} is required")
+        _chk(t, torch.float32, "gpa_attn_maps " + name, n)
+    if global_ is None and local is None and fused is None:
+        raise L.GavikoHipError("gpa_attn_maps: no output requested")
+    for name, t in (("global_", global_), ("local", local), ("fused", fused)):
+        _chk(t, torch.float32, "gpa_attn_maps " + name, B * P * N)
+    d = _desc(L.GpaMapsDesc, "gpa_attn_maps", xl=xl, ll=ll, qg=qg, ql=ql, lse_g=lse_g, lse_l=lse_l, imp=imp, gw=gw, pg=global_, pl=local,
+              fused=fused, B=B, T=T, N=N, P=P, L=L_)
+    L.check(L.load().gvk_gpa_attn_maps(C.byref(d), L.stream_ptr()), "gvk_gpa_attn_maps")
+
+
 def gpa_gate_param_count(Lat, P):
     return L.load().gvk_gpa_gate_param_count(Lat, P)
 

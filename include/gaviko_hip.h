@@ -476,6 +476,34 @@ int gvk_gpa_fwd(const gvk_gpa_desc* d, void* stream);
 int gvk_gpa_bwd(const gvk_gpa_desc* d, void* stream);
 int gvk_gpa_gate_param_count(int L, int P);
 
+/* ------------------------------------------------------------------ probability maps of the two GAViKO attentions for explanations
+ * (csrc/gaviko_maps.hip).  Neither forward builds a probability; both maps are recomputed from what a forward leaves, against its own
+ * log-sum-exp, as the backward passes do.  Deterministic (no atomics); launched on the given stream, not part of a launch plan.
+ *
+ * gvk_window_attn_colsum: weighted rows of the MWSA probability matrix (what a hook on F.softmax of gaviko.py:238 sees), never materialised:
+ *   out f32 [B][N]  out[b][j] = sum_i w[b][i] * P[b][i][j],   P[b][i][j] = exp(scale * q_i . k_j - lse[b][i]) for j in window(i), else 0
+ * qkv, lse, the grid, the window and scale as gvk_window_attn_fwd takes / leaves them; w f32 [B][N].  One wave per key j over the
+ * REVERSE window (the key-side pass of gvk_window_attn_bwd with w_i in the place of dctx_i). */
+typedef struct gvk_window_colsum_desc {
+  const float* qkv; const float* lse; const float* w; float* out;
+  int32_t B, D, H, W, kd, kh, kw, L;
+  float scale;
+} gvk_window_colsum_desc;
+int gvk_window_attn_colsum(const gvk_window_colsum_desc* d, void* stream);
+/* gvk_gpa_attn_maps: the two cross-attention probability blocks of one GPA layer (gaviko.py:90-91) and their gated fusion (:175-178),
+ * from the buffers gvk_gpa_fwd saved -- qg / ql are its PRE-SCALED queries (scale * (Wq prompt + bq)), lse_g / lse_l natural-log:
+ *   pg[b][p][n]    = exp(qg[b][p] . xl[b][P+1+n] - lse_g[b][p])  for n >= P+1, else 0   (the reference slices the image tokens twice,
+ *                    gaviko.py:161,107: the global softmax runs over rows 2P+2 .. T-1 of xl, patch positions P+1 .. N-1)
+ *   pl[b][p][n]    = exp(ql[b][p] . ll[b][n] - lse_l[b][p])
+ *   fused[b][p][n] = imp[b][p] * (gw[b] * pg + (1 - gw[b]) * pl)     -- the coefficient with which position n enters enhanced prompt p
+ * outputs f32 [B][P][N], each may be NULL (not all three).  T = P + 1 + N, N > P + 1, P <= 64. */
+typedef struct gvk_gpa_maps_desc {
+  const float* xl; const float* ll; const float* qg; const float* ql; const float* lse_g; const float* lse_l; const float* imp; const float* gw;
+  float* pg; float* pl; float* fused;
+  int32_t B, T, N, P, L;
+} gvk_gpa_maps_desc;
+int gvk_gpa_attn_maps(const gvk_gpa_maps_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ token assembly and the pooled head
  * rows_broadcast: out[b][row_off + r][:] = src[r][:] + add[r][:]  (cls_token + pos[0]; prompts + prompt_pos;
  *                 vision_transformer.py:154-156, gaviko.py:536-543, vpt.py:127-131).  out is [B*T][C].
