@@ -637,6 +637,40 @@ class Engine(GavikoPaths, PeftPaths):
         finally:
             self._restore_state(keep)
 
+    def perturbed_forward(self, x: torch.Tensor, src: torch.Tensor, *, rank=None, lo=None, hi=None, boxes=None, fill_scalar=None, base=None,
+                          slot=None, rows=None) -> torch.Tensor:
+        """One chunk of a perturbation sweep, for gaviko_amd.explain: Bc = len(src) perturbed copies of the volumes x [S,1,D,H,W] are built
+        straight in the static input slot of the (Bc, inference) workspace -- output sample o is x[src[o]] with the patches of its mask
+        replaced by fill_scalar[src[o]] or by the baseline volume `base` -- and eval_forward's deterministic forward runs on them -> logits
+        [Bc, K].  The mask is a rank interval (rank i32 [S, N], lo / hi i32 [Bc]: lo <= rank < hi) or a box per sample (boxes i32 [Bc, 6],
+        patch-grid units).  slot / rows: the logits row of sample o is also written to rows.view(-1, K)[slot[o]] (slot[o] < 0: nowhere).
+        Every table is a device tensor, so a sweep uploads them once and no step waits for the host.  The forward is the recorded plan of
+        eval_forward at this batch size (one workspace, one plan key for a whole sweep); the mask, perturb and gather launches around it
+        are issued eagerly on the same stream: their arguments are slices of the sweep's tables, which a recorded plan would freeze.
+        The state of a pending backward is put back, as for eval_forward."""
+        if (boxes is None) == (rank is None):
+            raise L.GavikoHipError("perturbed_forward: exactly one of rank (with lo, hi) and boxes")
+        if (slot is None) != (rows is None):
+            raise L.GavikoHipError("perturbed_forward: slot and rows go together")
+        Bc = src.numel()
+        keep = self._pending_state()
+        try:
+            ws = self.workspace(Bc, x.device, False)
+            mask = ws.get("pmask")
+            if mask is None:
+                mask = ws["pmask"] = torch.zeros((Bc, self.N), dtype=torch.uint8, device=x.device)
+            if boxes is not None:
+                ops.patch_mask_box(boxes, mask, self.grid)
+            else:
+                ops.patch_mask_rank(rank, src, lo, hi, mask)
+            ops.perturb_volume(x, mask, src, ws["img"], self.patch, fill_scalar=fill_scalar, base=base)
+            logits = self.forward(ws["img"], train=False, drop=None)
+            if rows is not None:
+                ops.perturb_scores(ws["logits"], src, None, slot, None, None, rows)
+        finally:
+            self._restore_state(keep)
+        return logits
+
     def input_backward(self, img: torch.Tensor, seed):
         """Gradient of the logits with respect to the input volume, for gaviko_amd.explain: a deterministic training forward (no dropout)
         and an input-only backward, both in the 'igrad' workspace -> (logits, ws).  `seed(logits)` returns dlogits [B, K] (the logit

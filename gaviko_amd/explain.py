@@ -44,6 +44,17 @@ parameter gradient changes), un-patchified by csrc/input_grad.hip with the attri
     logits, g = smoothgrad(model, img, samples=16)         # mean over noisy copies (Smilkov et al., 2017)
     logits, attr, delta = integrated_gradients(model, img) # (Sundararajan et al., 2017); delta: the completeness gap
     grid = patch_saliency(model, g)                        # [B, D/pd, H/ph, W/pw]: sum of |g| per patch (patch_grid's layout)
+
+Which map is faithful, and a map without any backward pass: many inference forwards of one volume in which a chosen set of patches is
+replaced by a baseline (csrc/perturb.hip builds the perturbed batch straight in the engine's input slot, Engine.perturbed_forward), for
+every method on both precision paths.  Deletion / insertion curves (Petsiuk et al., 2018) rank the patches by a patch-level map
+([B, N] or patch_grid / patch_saliency's [B, *grid]) and remove / restore the top k for growing k; occlusion sensitivity (Zeiler & Fergus,
+2014) slides a window over the patch grid.
+
+    res = deletion_curve(model, img, grid, target=None, steps=20)      # PerturbationCurve: logits, ks, prob, logit, auc, step_logits
+    res = insertion_curve(model, img, grid, target=None, steps=20)     # small deletion auc and large insertion auc = a faithful map
+    occ = occlusion_sensitivity(model, img, window=(2, 2, 2))          # OcclusionResult: logits, boxes, drops [B, Wn], map [B, *grid]
+    ranks = patch_ranks(model, grid)                                   # [B, N] int32: the order the curves use (ties in patch order)
 """
 from __future__ import annotations
 
@@ -442,3 +453,204 @@ def local_rollout(model, img: torch.Tensor, start: Optional[torch.Tensor] = None
         _window_colsum(eng, ws, l, r, cs)
         ops.rollout_step(r, cs, r, B, N, 1)                   # the single head: mean head fusion over H = 1
     return logits, r
+
+
+# ---- gradient-free attribution and the faithfulness of a map: occlusion sensitivity, deletion / insertion curves -----------------
+class PerturbationCurve(NamedTuple):
+    """deletion_curve / insertion_curve: logits [B, K] of the unperturbed volume; ks [S + 1] int64, the number of patches removed
+    (restored) at every step; prob / logit [B, S + 1] of the explained class; auc [B], the trapezoid area of prob over k / N; step_logits
+    [B, S + 1, K]."""
+    logits: torch.Tensor
+    ks: torch.Tensor
+    prob: torch.Tensor
+    logit: torch.Tensor
+    auc: torch.Tensor
+    step_logits: torch.Tensor
+
+
+class OcclusionResult(NamedTuple):
+    """occlusion_sensitivity: logits [B, K] of the unperturbed volume; boxes [Wn, 6] int64 (d0, d1, h0, h1, w0, w1 in patch-grid units);
+    drops [B, Wn] = prob(x)[target] - prob(x with window w replaced)[target]; map [B, *grid], the mean drop of the windows covering a patch."""
+    logits: torch.Tensor
+    boxes: torch.Tensor
+    drops: torch.Tensor
+    map: torch.Tensor
+
+
+def _relevance_rows(eng, relevance, B, what) -> torch.Tensor:
+    """A patch-level map in one of the two layouts the package produces -- [B, N] or [B, *grid] (patch_grid / patch_saliency) -> float32
+    [B, N], NaN rejected (one device check, before any step of a sweep)."""
+    if not isinstance(relevance, torch.Tensor) or not relevance.is_cuda:
+        raise L.GavikoHipError(f"{what}: the relevance map must be a tensor on the HIP device (there is no CPU path)")
+    shape = tuple(relevance.shape)
+    if shape not in ((B, eng.N), (B,) + tuple(eng.grid)) or not relevance.dtype.is_floating_point:
+        raise L.GavikoHipError(f"{what}: expected a floating-point patch-level map [{B}, {eng.N}] or [{B}, {', '.join(map(str, eng.grid))}], got "
+                               f"{shape} {relevance.dtype} -- token-level maps [B, T] go through patch_grid first, voxel maps through patch_saliency")
+    rel = relevance.detach().reshape(B, eng.N).to(torch.float32).contiguous()
+    if bool(torch.isnan(rel).any()):
+        raise L.GavikoHipError(f"{what}: the relevance map holds NaN, which has no place in an order")
+    return rel
+
+
+def patch_ranks(model, relevance: torch.Tensor) -> torch.Tensor:
+    """relevance [B, N] or [B, *grid] (the layout of patch_grid / patch_saliency) -> ranks [B, N] int32: ranks[b, n] is the position of
+    patch n when the patches of sample b are sorted by descending relevance, ties in patch order -- the inverse permutation of
+    torch.argsort(relevance, descending=True, stable=True)."""
+    eng = model._engine()
+    if not isinstance(relevance, torch.Tensor) or relevance.dim() < 1:
+        raise L.GavikoHipError("patch_ranks: the relevance map must be a tensor on the HIP device (there is no CPU path)")
+    return ops.patch_rank(_relevance_rows(eng, relevance, relevance.shape[0], "patch_ranks"))
+
+
+def _baseline(eng, x, baseline, what):
+    """-> (fill_scalar f32 [B] or None, base [1 or B,1,D,H,W] or None): 'min' (the per-sample minimum of the volume: what RescaleIntensity
+    maps to 0 and RandomAffine pads with), a float, or a baseline volume."""
+    B = x.shape[0]
+    if isinstance(baseline, str):
+        if baseline != "min":
+            raise L.GavikoHipError(f"{what}: baseline={baseline!r}: expected 'min', a float or a volume [1 or B, 1, D, H, W]")
+        V = x.numel() // B
+        if V % 4:                                            # gvk_volume_minmax reads 16-byte words
+            return x.reshape(B, V).amin(1).contiguous(), None
+        part = ops.minmax_partials(B, x.device)
+        ops.volume_minmax(x, part)
+        return part.view(B, -1, 2)[:, :, 0].amin(1).contiguous(), None
+    if isinstance(baseline, (int, float)) and not isinstance(baseline, bool):
+        return torch.full((B,), float(baseline), dtype=torch.float32, device=x.device), None
+    if isinstance(baseline, torch.Tensor):
+        if not baseline.is_cuda:
+            raise L.GavikoHipError(f"{what}: the baseline volume must be on the HIP device (there is no CPU path)")
+        if baseline.dim() != 5 or tuple(baseline.shape[1:]) != tuple(x.shape[1:]) or baseline.shape[0] not in (1, B) or baseline.dtype != torch.float32:
+            raise L.GavikoHipError(f"{what}: expected a float32 baseline volume [1 or {B}, {', '.join(map(str, x.shape[1:]))}], got "
+                                   f"{tuple(baseline.shape)} {baseline.dtype}")
+        return None, baseline.detach().contiguous()
+    raise L.GavikoHipError(f"{what}: baseline={baseline!r}: expected 'min', a float or a volume [1 or B, 1, D, H, W]")
+
+
+def _sweep(eng, x, target, bs, fill, base, jobs, *, rank=None):
+    """The perturbed forwards of one call, in engine chunks of `bs` samples.  jobs[i] = (b, spec) asks for volume b with the patches of
+    `spec` replaced: (lo, hi) = the patches of rank lo <= r < hi (with `rank`), or a box (d0, d1, h0, h1, w0, w1) in patch-grid units.
+    -> (logits [B, K] of the unperturbed volumes, rows [len(jobs), K] in the order of `jobs`, prob [B + len(jobs)], logit [B + len(jobs)]:
+    the B unperturbed volumes first).
+
+    The B unperturbed volumes run first through the same chunks (an empty mask), so one workspace and one launch plan serve the whole
+    call, and a job whose mask is empty (deletion at k = 0, insertion at k = N) is not run again: its row is a copy of volume b's.  The
+    last chunk is padded with repeats that write nowhere.  Example, B = 2, a deletion curve with ks = [0, 500, 1000], bs = 3:
+        result rows   0 1 | 2    3      4      5    6      7        (rows 0, 1: the plain volumes; 2.. : jobs in their order)
+        jobs               (0,k0)(1,k0)(0,k500)(1,k500)(0,k1000)(1,k1000)
+        run           src  0 1 0 | 1 0 1          (plain 0, plain 1, the four non-empty jobs)
+                      slot 0 1 4 | 5 6 7          (the result row each forward's logits are gathered into; -1 for padding)
+        copies        rows 2, 3 <- rows 0, 1      (the two k = 0 jobs)
+    The tables go to the device once; every chunk gathers its logits rows on the device and one launch at the end scores all result
+    rows (src_of_row[r] = the volume of row r picks the target), so nothing between the first and the last forward waits for the host."""
+    B, K, dev = x.shape[0], eng.K, x.device
+    ranked = rank is not None
+    empty = (lambda sp: sp[0] >= sp[1]) if ranked else (lambda sp: sp[0] >= sp[1] or sp[2] >= sp[3] or sp[4] >= sp[5])
+    blank = (0, 0) if ranked else (0, 0, 0, 0, 0, 0)
+    n = B + len(jobs)                                        # result rows
+    src_of_row = list(range(B)) + [b for b, _ in jobs]
+    run = [(b, blank, b) for b in range(B)] + [(b, sp, B + i) for i, (b, sp) in enumerate(jobs) if not empty(sp)]   # (volume, spec, result row)
+    reuse = [(B + i, b) for i, (b, sp) in enumerate(jobs) if empty(sp)]                                              # (result row, plain row)
+    run += [(run[-1][0], run[-1][1], -1)] * ((-len(run)) % bs)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)       # noqa: E731
+    src, spec, slot = i32([r[0] for r in run]), i32([r[1] for r in run]), i32([r[2] for r in run])
+    src_row, row_id = i32(src_of_row), i32(list(range(n)))
+    rows = torch.empty((n, K), device=dev)
+    with torch.no_grad():
+        for c in range(0, len(run), bs):
+            s = slice(c, c + bs)
+            mask = dict(rank=rank, lo=spec[s, 0].contiguous(), hi=spec[s, 1].contiguous()) if ranked else dict(boxes=spec[s])
+            eng.perturbed_forward(x, src[s], fill_scalar=fill, base=base, slot=slot[s], rows=rows, **mask)
+        if reuse:
+            rows[torch.tensor([r for r, _ in reuse]).to(dev)] = rows[torch.tensor([b for _, b in reuse]).to(dev)]
+        logits = rows[:B].clone()
+        tgt = target if target is not None else logits.argmax(dim=1)
+        prob, logit = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        ops.perturb_scores(rows, src_row, tgt.to(torch.int32), row_id, prob, logit)
+    return logits, rows[B:], prob, logit
+
+
+def _perturb_checks(model, img, target, baseline, batch, what):
+    eng, x = _volume_check(model, img, what)
+    B = x.shape[0]
+    bs = _batch(batch, 8)
+    tgt = None
+    if target is not None:                                   # validated (and resolved) before any launch
+        tgt = _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)
+    fill, base = _baseline(eng, x, baseline, what)
+    return eng, x, B, bs, tgt, fill, base
+
+
+def _curve(model, img, relevance, target, steps, ks, baseline, batch, insertion, what) -> PerturbationCurve:
+    eng, x, B, bs, tgt, fill, base = _perturb_checks(model, img, target, baseline, batch, what)
+    N = eng.N
+    if ks is None:
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise L.GavikoHipError(f"steps={steps!r}: expected a positive int")
+        ks = [(s * N) // steps for s in range(steps + 1)]
+    else:
+        ks = [int(k) for k in (ks.tolist() if isinstance(ks, torch.Tensor) else ks)]
+        if not ks or any(not 0 <= k <= N for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+            raise L.GavikoHipError(f"ks={ks!r}: expected an increasing list of patch counts within [0, {N}]")
+    rank = ops.patch_rank(_relevance_rows(eng, relevance, B, what))
+    P = len(ks)
+    # step-major: a chunk holds the same step of consecutive samples (with batch == B, exactly the samples of img in their order)
+    jobs = [(b, (k, N) if insertion else (0, k)) for k in ks for b in range(B)]
+    logits, rows, prob, logit = _sweep(eng, x, tgt, bs, fill, base, jobs, rank=rank)
+    by_sample = lambda t: t.view(P, B, *t.shape[1:]).transpose(0, 1).contiguous()       # noqa: E731  [P * B, ...] step-major -> [B, P, ...]
+    prob, logit = by_sample(prob[B:]), by_sample(logit[B:])
+    ks_dev = torch.tensor(ks, dtype=torch.int32).to(x.device)
+    auc = ops.curve_auc(prob, ks_dev, N)
+    return PerturbationCurve(logits, torch.tensor(ks, dtype=torch.int64), prob, logit, auc, by_sample(rows))
+
+
+def deletion_curve(model, img: torch.Tensor, relevance: torch.Tensor, target=None, *, steps: int = 20, ks=None, baseline="min",
+                   batch: int = 8) -> PerturbationCurve:
+    """Deletion curve (Petsiuk et al., 2018): the patches of every volume are ranked by `relevance` ([B, N] or [B, *grid]: patch_grid /
+    patch_saliency layout; ties in patch order) and the top k are replaced by the baseline for growing k; a faithful map makes the class
+    probability fall fast, i.e. a SMALL auc.  k_s = (s N) // steps for s = 0 .. steps (k_0 = 0: the unperturbed volume), or an explicit
+    increasing list `ks` within [0, N].  target: None (the argmax of the unperturbed logits per sample), an int or a [B] tensor.
+    baseline: 'min' (the per-sample minimum of the volume), a float, or a float32 volume [1 or B, 1, D, H, W] (e.g. a blurred copy).
+    batch: perturbed volumes per engine forward.  Runs on every method and both precision paths; the forward is the deterministic one."""
+    return _curve(model, img, relevance, target, steps, ks, baseline, batch, False, "deletion_curve")
+
+
+def insertion_curve(model, img: torch.Tensor, relevance: torch.Tensor, target=None, *, steps: int = 20, ks=None, baseline="min",
+                    batch: int = 8) -> PerturbationCurve:
+    """Insertion curve: deletion_curve's counterpart that starts from the pure baseline (k_0 = 0) and restores the top-k patches; a faithful
+    map makes the class probability rise fast, i.e. a LARGE auc.  Arguments as for deletion_curve."""
+    return _curve(model, img, relevance, target, steps, ks, baseline, batch, True, "insertion_curve")
+
+
+def _triple(v, name):
+    if isinstance(v, int) and not isinstance(v, bool):
+        v = (v, v, v)
+    if not isinstance(v, (tuple, list)) or len(v) != 3 or any(isinstance(a, bool) or not isinstance(a, int) or a < 1 for a in v):
+        raise L.GavikoHipError(f"{name}={v!r}: expected three positive ints (patch-grid units)")
+    return tuple(v)
+
+
+def occlusion_sensitivity(model, img: torch.Tensor, target=None, *, window=(2, 2, 2), stride=None, baseline="min",
+                          batch: int = 8) -> OcclusionResult:
+    """Occlusion sensitivity (Zeiler & Fergus, 2014) at patch granularity: a window of `window` patches slides over the patch grid in steps
+    of `stride` (None: the window itself, disjoint windows; windows are clipped to the grid), the patches under it are replaced by the
+    baseline, and the drop of the class probability is recorded.  map[b, patch] is the mean drop over the windows that cover the patch
+    (every patch must be covered).  target / baseline / batch as for deletion_curve.  No backward pass is involved."""
+    eng, x, B, bs, tgt, fill, base = _perturb_checks(model, img, target, baseline, batch, "occlusion_sensitivity")
+    win = _triple(window, "window")
+    st = win if stride is None else _triple(stride, "stride")
+    grid = tuple(eng.grid)
+    axes = [[(p, min(p + w, g)) for p in range(0, g, s)] for g, w, s in zip(grid, win, st)]
+    wins = [d + h + w for d in axes[0] for h in axes[1] for w in axes[2]]
+    cover = torch.zeros((len(wins),) + grid)
+    for i, (d0, d1, h0, h1, w0, w1) in enumerate(wins):
+        cover[i, d0:d1, h0:h1, w0:w1] = 1.0
+    if bool((cover.sum(0) == 0).any()):
+        raise L.GavikoHipError(f"occlusion_sensitivity: window={win} with stride={st} leaves patches of the {grid} grid uncovered")
+    Wn = len(wins)
+    jobs = [(b, w) for w in wins for b in range(B)]                  # window-major, like the steps of a curve
+    logits, _, prob, _ = _sweep(eng, x, tgt, bs, fill, base, jobs)
+    drops = prob[:B, None] - prob[B:].view(Wn, B).t()
+    cover = cover.view(Wn, eng.N).to(x.device)
+    amap = (drops[:, :, None] * cover[None]).sum(1) / cover.sum(0)
+    return OcclusionResult(logits, torch.tensor(wins, dtype=torch.int64), drops, amap.view((B,) + grid))

@@ -196,6 +196,12 @@ SIGNATURES = {
     "gvk_scale_f32": [_P, _F, C.c_long, _P],
     "gvk_head_fwd": [C.POINTER(HeadDesc), _P],
     "gvk_head_bwd": [C.POINTER(HeadDesc), _P],
+    "gvk_patch_rank": [_P, _P, _I, _I, _P],
+    "gvk_patch_mask_rank": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_patch_mask_box": [_P, _P, _I, _I, _I, _I, _P],
+    "gvk_perturb_volume": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "gvk_perturb_scores": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "gvk_curve_auc": [_P, _P, _P, _I, _I, _I, _P],
 }
 NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, []), "gvk_abi_version": (C.c_int, []),
              "gvk_attention_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -261,6 +261,143 @@ def patch_reduce(vol: torch.Tensor, out: torch.Tensor, patch, absval=True) -> No
             "gvk_patch_reduce_f32")
 
 
+# ---- perturbation of the input volume at patch granularity (csrc/perturb.hip) ----
+def _tab(t, what, n):
+    """A per-output-sample int32 device table of exactly n entries (only dtype and length are checked: the values are the caller's
+    contract, and the kernels clamp them rather than read out of bounds)."""
+    if t is None:
+        raise L.GavikoHipError(f"{what}: the table is required")
+    _chk(t, torch.int32, what)
+    if t.numel() != n:
+        raise L.GavikoHipError(f"{what}: expected {n} int32 entries, got {tuple(t.shape)}")
+
+
+def patch_rank(rel: torch.Tensor, rank: torch.Tensor = None) -> torch.Tensor:
+    """rel f32 [S, N] -> rank i32 [S, N]: the position of every patch in the stable descending order of its row (the inverse permutation
+    of torch.argsort(rel, descending=True, stable=True)).  NaN is not ordered: the caller rejects it."""
+    _chk(rel, torch.float32, "patch_rank rel")
+    if rel.dim() != 2 or rel.shape[0] < 1 or rel.shape[1] < 1:
+        raise L.GavikoHipError(f"patch_rank rel: expected [S, N], got {tuple(rel.shape)}")
+    S, N = rel.shape
+    if N > 16384:
+        raise L.GavikoHipError(f"patch_rank: N = {N} patches exceed the 16384 one workgroup keeps in LDS")
+    if rank is None:
+        rank = torch.empty((S, N), dtype=torch.int32, device=rel.device)
+    _chk(rank, torch.int32, "patch_rank rank")
+    if tuple(rank.shape) != (S, N):
+        raise L.GavikoHipError(f"patch_rank rank: shape {tuple(rank.shape)} != rel {tuple(rel.shape)}")
+    L.check(L.load().gvk_patch_rank(L.ptr(rel), L.ptr(rank), S, N, L.stream_ptr()), "gvk_patch_rank")
+    return rank
+
+
+def patch_mask_rank(rank: torch.Tensor, src: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, mask: torch.Tensor) -> None:
+    """mask u8 [Bout, N] = lo[o] <= rank[src[o], n] < hi[o]; rank i32 [S, N], src / lo / hi i32 [Bout] device tables (src within [0, S))."""
+    _chk(rank, torch.int32, "patch_mask_rank rank")
+    _chk(mask, torch.uint8, "patch_mask_rank mask")
+    if rank.dim() != 2 or mask.dim() != 2 or mask.shape[1] != rank.shape[1] or mask.shape[0] < 1:
+        raise L.GavikoHipError(f"patch_mask_rank: expected rank [S, N] and mask [Bout, N], got {tuple(rank.shape)} and {tuple(mask.shape)}")
+    Bout, N = mask.shape
+    for t, n in ((src, "src"), (lo, "lo"), (hi, "hi")):
+        _tab(t, "patch_mask_rank " + n, Bout)
+    L.check(L.load().gvk_patch_mask_rank(L.ptr(rank), L.ptr(src), L.ptr(lo), L.ptr(hi), L.ptr(mask), Bout, rank.shape[0], N, L.stream_ptr()),
+            "gvk_patch_mask_rank")
+
+
+def patch_mask_box(boxes: torch.Tensor, mask: torch.Tensor, grid) -> None:
+    """mask u8 [Bout, N] = patch inside boxes[o] = (d0, d1, h0, h1, w0, w1), half-open, in units of the patch grid `grid` = (nd, nh, nw);
+    boxes i32 [Bout, 6] device table."""
+    nd, nh, nw = (int(g) for g in grid)
+    _chk(mask, torch.uint8, "patch_mask_box mask")
+    if mask.dim() != 2 or mask.shape[0] < 1 or mask.shape[1] != nd * nh * nw or min(nd, nh, nw) < 1:
+        raise L.GavikoHipError(f"patch_mask_box: expected mask [Bout, {nd * nh * nw}] for the grid {(nd, nh, nw)}, got {tuple(mask.shape)}")
+    _tab(boxes, "patch_mask_box boxes", mask.shape[0] * 6)
+    L.check(L.load().gvk_patch_mask_box(L.ptr(boxes), L.ptr(mask), mask.shape[0], nd, nh, nw, L.stream_ptr()), "gvk_patch_mask_box")
+
+
+def perturb_volume(x: torch.Tensor, mask: torch.Tensor, src: torch.Tensor, out: torch.Tensor, patch, *, fill_scalar=None, base=None) -> None:
+    """out[o] = where(mask[o] upsampled to the voxels, fill, x[src[o]]), bit for bit.  x f32 [S,1,D,H,W], out f32 [Bout,1,D,H,W] (not
+    overlapping x), mask u8 [Bout, N], src i32 [Bout] (within [0, S)); fill: fill_scalar f32 [S] (one value per source) or base f32
+    [1 or S,1,D,H,W] (a baseline volume, shared or one per source)."""
+    _chk(x, torch.float32, "perturb_volume x")
+    _chk(out, torch.float32, "perturb_volume out")
+    if x.dim() != 5 or out.dim() != 5 or x.shape[1] != 1 or tuple(out.shape[1:]) != tuple(x.shape[1:]) or x.shape[0] < 1 or out.shape[0] < 1:
+        raise L.GavikoHipError(f"perturb_volume: expected x [S,1,D,H,W] and out [Bout,1,D,H,W], got {tuple(x.shape)} and {tuple(out.shape)}")
+    S, _, D, H, W = x.shape
+    Bout = out.shape[0]
+    pd, ph, pw = (int(p) for p in patch)
+    if min(pd, ph, pw) < 1 or D % pd or H % ph or W % pw:
+        raise L.GavikoHipError(f"perturb_volume: volume {D}x{H}x{W} not divisible by patch {pd}x{ph}x{pw}")
+    N = (D // pd) * (H // ph) * (W // pw)
+    _chk(mask, torch.uint8, "perturb_volume mask")
+    if tuple(mask.shape) != (Bout, N):
+        raise L.GavikoHipError(f"perturb_volume mask: expected [{Bout}, {N}], got {tuple(mask.shape)}")
+    _tab(src, "perturb_volume src", Bout)
+    if (fill_scalar is None) == (base is None):
+        raise L.GavikoHipError("perturb_volume: exactly one of fill_scalar and base")
+    nbase = 0
+    if fill_scalar is not None:
+        _chk(fill_scalar, torch.float32, "perturb_volume fill_scalar")
+        if fill_scalar.numel() != S:
+            raise L.GavikoHipError(f"perturb_volume fill_scalar: expected {S} values (one per source), got {tuple(fill_scalar.shape)}")
+    else:
+        _chk(base, torch.float32, "perturb_volume base")
+        if base.dim() != 5 or tuple(base.shape[1:]) != tuple(x.shape[1:]) or base.shape[0] not in (1, S):
+            raise L.GavikoHipError(f"perturb_volume base: expected [1 or {S}, 1, {D}, {H}, {W}], got {tuple(base.shape)}")
+        nbase = base.shape[0]
+    xe, oe = x.data_ptr() + x.numel() * 4, out.data_ptr() + out.numel() * 4
+    if not (oe <= x.data_ptr() or xe <= out.data_ptr()):
+        raise L.GavikoHipError("perturb_volume: out must not overlap x")
+    if base is not None and not (oe <= base.data_ptr() or base.data_ptr() + base.numel() * 4 <= out.data_ptr()):
+        raise L.GavikoHipError("perturb_volume: out must not overlap base")
+    if Bout * D * H * W >= 1 << 31:
+        raise L.GavikoHipError(f"perturb_volume: {Bout} x {D * H * W} voxels per launch exceed the kernel's 32-bit index range")
+    L.check(L.load().gvk_perturb_volume(L.ptr(x), L.ptr(mask), L.ptr(src), L.ptr(fill_scalar), L.ptr(base), nbase, L.ptr(out), Bout, S, D, H, W,
+                                        pd, ph, pw, L.stream_ptr()), "gvk_perturb_volume")
+
+
+def perturb_scores(logits: torch.Tensor, src: torch.Tensor, target: torch.Tensor, slot: torch.Tensor, prob: torch.Tensor, logit: torch.Tensor,
+                   rows: torch.Tensor = None) -> None:
+    """For every output sample o with slot[o] >= 0: prob.flat[slot[o]] = softmax(logits[o])[target[src[o]]], logit.flat[slot[o]] = that logit,
+    rows.view(-1, K)[slot[o]] = logits[o] (optional).  logits f32 [Bout, K]; src / slot i32 [Bout], target i32 [S] device tables (target
+    within [0, K)).  prob = logit = None (then src and target are not read): the rows only."""
+    _chk(logits, torch.float32, "perturb_scores logits")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise L.GavikoHipError(f"perturb_scores logits: expected [Bout, K], got {tuple(logits.shape)}")
+    Bout, K = logits.shape
+    _tab(slot, "perturb_scores slot", Bout)
+    if (prob is None) != (logit is None) or (prob is None and rows is None):
+        raise L.GavikoHipError("perturb_scores: prob and logit go together, and without them rows is required")
+    if prob is not None:
+        if target is None:
+            raise L.GavikoHipError("perturb_scores: prob / logit need a target table")
+        _tab(src, "perturb_scores src", Bout)
+        _chk(target, torch.int32, "perturb_scores target", 1)
+        _chk(prob, torch.float32, "perturb_scores prob", 1)
+        _chk(logit, torch.float32, "perturb_scores logit", 1)
+    nslots = prob.numel() if prob is not None else rows.numel() // K
+    _chk(rows, torch.float32, "perturb_scores rows", K)
+    if (logit is not None and logit.numel() != nslots) or (rows is not None and rows.numel() != nslots * K):
+        raise L.GavikoHipError(f"perturb_scores: {nslots} slots; logit needs as many and rows {nslots} x {K}")
+    S = target.numel() if prob is not None else 0
+    L.check(L.load().gvk_perturb_scores(L.ptr(logits), L.ptr(src) if prob is not None else None, L.ptr(target) if prob is not None else None,
+                                        L.ptr(slot), L.ptr(prob), L.ptr(logit), L.ptr(rows), Bout, S, K, nslots, L.stream_ptr()),
+            "gvk_perturb_scores")
+
+
+def curve_auc(prob: torch.Tensor, ks: torch.Tensor, N: int, auc: torch.Tensor = None) -> torch.Tensor:
+    """prob f32 [S, P], ks i32 [P] (device) -> auc f32 [S]: the trapezoid area of every curve over x = ks / N."""
+    _chk(prob, torch.float32, "curve_auc prob")
+    if prob.dim() != 2 or prob.shape[0] < 1 or prob.shape[1] < 1 or int(N) < 1:
+        raise L.GavikoHipError(f"curve_auc: expected prob [S, P] and N >= 1, got {tuple(prob.shape)} and N = {N}")
+    S, P = prob.shape
+    _tab(ks, "curve_auc ks", P)
+    if auc is None:
+        auc = torch.empty(S, dtype=torch.float32, device=prob.device)
+    _chk(auc, torch.float32, "curve_auc auc", S)
+    L.check(L.load().gvk_curve_auc(L.ptr(prob), L.ptr(ks), L.ptr(auc), S, P, int(N), L.stream_ptr()), "gvk_curve_auc")
+    return auc
+
+
 def layernorm_fwd(x, gamma, beta, M, C_, *, y16=None, y32=None, mean=None, rstd=None, eps=1e-5):
     if y16 is not None and y16.dtype == torch.float32:       # fp32 compute path: the "operand" output is fp32
         y16, y32 = None, y16

@@ -672,6 +672,31 @@ typedef struct gvk_dropout_desc {
 } gvk_dropout_desc;
 int gvk_dropout_rows(const gvk_dropout_desc* d, void* stream);
 
+/* ---- perturbation of the input volume at patch granularity (csrc/perturb.hip): occlusion sensitivity, deletion / insertion curves ----
+ * N = (D/pd)(H/ph)(W/pw) patches in patch-grid order, V = D*H*W voxels, S source volumes, Bout output samples of one chunk.  The per-output
+ * tables (src, lo, hi, boxes, slot) are int32 DEVICE arrays: a sweep uploads them once and passes every chunk its slice.
+ * gvk_patch_rank: rank i32 [S][N], rank[s][n] = #{m : rel[s][m] > rel[s][n]} + #{m < n : rel[s][m] == rel[s][n]} -- the inverse permutation of
+ *   a stable descending argsort of rel f32 [S][N].  N <= 16384.  NaN is the caller's to reject.  Deterministic.
+ * gvk_patch_mask_rank: mask u8 [Bout][N] = lo[o] <= rank[src[o]][n] < hi[o]            (deletion at k: (0, k); insertion at k: (k, N)).
+ * gvk_patch_mask_box:  mask u8 [Bout][N] = patch n inside boxes[o] = {d0, d1, h0, h1, w0, w1} (half-open, patch-grid units, clipped by the grid).
+ * gvk_perturb_volume:  out f32 [Bout][V], out[o][v] = mask[o][patch(v)] ? fill : x[src[o]][v] with fill = fill_scalar[src[o]] or
+ *   base[nbase == 1 ? 0 : src[o]][v] (exactly one of the two pointers; nbase = 1 or S).  A selection of 32-bit words: bit-exact.  16-byte
+ *   accesses when pw % 4 == 0 and the pointers are 16-byte aligned, one voxel per thread otherwise.  out must not overlap x.
+ *   Bytes: Bout*V*4 written, at most (S + nbase)*V*4 read.
+ * gvk_perturb_scores:  per output sample o with slot[o] in [0, nslots): prob[slot[o]] = softmax(logits[o])[target[src[o]]] (fp32, max-subtracted),
+ *   logit[slot[o]] = logits[o][target[src[o]]], rows (optional) [nslots][K] row slot[o] = logits[o].  slot[o] < 0 writes nothing.  prob ==
+ *   logit == NULL: the rows only (src / target unused).  Deterministic.
+ * gvk_curve_auc:       auc[s] = trapezoid area of prob f32 [S][P] over x_i = ks[i] / N (ks int32 [P], device).  Deterministic. */
+int gvk_patch_rank(const float* rel, int32_t* rank, int S, int N, void* stream);
+int gvk_patch_mask_rank(const int32_t* rank, const int32_t* src, const int32_t* lo, const int32_t* hi, uint8_t* mask, int Bout, int S, int N,
+                        void* stream);
+int gvk_patch_mask_box(const int32_t* boxes, uint8_t* mask, int Bout, int nd, int nh, int nw, void* stream);
+int gvk_perturb_volume(const float* x, const uint8_t* mask, const int32_t* src, const float* fill_scalar, const float* base, int nbase,
+                       float* out, int Bout, int S, int D, int H, int W, int pd, int ph, int pw, void* stream);
+int gvk_perturb_scores(const float* logits, const int32_t* src, const int32_t* target, const int32_t* slot, float* prob, float* logit,
+                       float* rows, int Bout, int S, int K, int nslots, void* stream);
+int gvk_curve_auc(const float* prob, const int32_t* ks, float* auc, int S, int P, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
