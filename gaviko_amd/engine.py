@@ -671,6 +671,42 @@ class Engine(GavikoPaths, PeftPaths):
             self._restore_state(keep)
         return logits
 
+    def member_seed(self, Bc: int, device, seed: Optional[int] = None) -> torch.Tensor:
+        """The dropout seed word (one int64 device word) of the (Bc, inference) workspace that member_forward runs in; seed: set it first
+        (one fill_), so that the draws of a sweep are reproducible.  Every forward advances the word by 7919 and draws its masks from the
+        advanced value.  The state of a pending backward is put back."""
+        keep = self._pending_state()
+        try:
+            word = self.workspace(Bc, device, False)["seed"]
+        finally:
+            self._restore_state(keep)
+        if seed is not None:
+            word.fill_(int(seed))
+        return word
+
+    def member_forward(self, x: torch.Tensor, src: torch.Tensor, flip: torch.Tensor, drop: Optional[dict], *, slot=None, rows=None) -> torch.Tensor:
+        """One chunk of a member sweep, for gaviko_amd.uncertainty: Bc = len(src) members of the volumes x [S,1,D,H,W] are built straight in
+        the static input slot of the (Bc, inference) workspace -- member o is x[src[o]] mirrored along the axes in the bits of flip[o] (0: a
+        plain replica) -- and an inference forward runs on them -> logits [Bc, K].  drop=None: eval_forward's deterministic plan; a dict with
+        live rates: the recorded plan of that drop configuration, the masks drawn from the workspace's seed word (member_seed) by the row
+        index inside the chunk.  slot / rows: the logits row of member o is also written to rows.view(-1, K)[slot[o]] (slot[o] < 0:
+        nowhere).  src / flip / slot are device tensors, so a sweep uploads them once and no step waits for the host; the build and gather
+        launches are issued eagerly around the replayed forward (a recorded launch would freeze their arguments).  The state of a pending
+        backward is put back, as for eval_forward."""
+        if (slot is None) != (rows is None):
+            raise L.GavikoHipError("member_forward: slot and rows go together")
+        Bc = src.numel()
+        keep = self._pending_state()
+        try:
+            ws = self.workspace(Bc, x.device, False)
+            ops.tta_volumes(x, src, flip, ws["img"])
+            logits = self.forward(ws["img"], train=False, drop=drop)
+            if rows is not None:
+                ops.perturb_scores(ws["logits"], None, None, slot, None, None, rows)
+        finally:
+            self._restore_state(keep)
+        return logits
+
     def input_backward(self, img: torch.Tensor, seed):
         """Gradient of the logits with respect to the input volume, for gaviko_amd.explain: a deterministic training forward (no dropout)
         and an input-only backward, both in the 'igrad' workspace -> (logits, ws).  `seed(logits)` returns dlogits [B, K] (the logit

@@ -202,6 +202,9 @@ SIGNATURES = {
     "gvk_perturb_volume": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_perturb_scores": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_curve_auc": [_P, _P, _P, _I, _I, _I, _P],
+    "gvk_tta_volumes": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "gvk_predictive_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_calibration_bins": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
 NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, []), "gvk_abi_version": (C.c_int, []),
              "gvk_attention_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

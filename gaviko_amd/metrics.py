@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .lib import GavikoHipError
 
 
 def kappa_quadratic(confusion: np.ndarray) -> float:
@@ -38,6 +39,37 @@ def macro_ovr_auc(counts: np.ndarray) -> float:
     if (counts[:, 1] == 0).any() or (counts[:, 2] == 0).any():
         raise ValueError("Only one class present in y_true for at least one one-vs-rest problem. ROC AUC score is not defined in that case.")
     return float((counts[:, 0] / (2.0 * counts[:, 1] * counts[:, 2])).mean())
+
+
+def calibration(proba: torch.Tensor, labels: torch.Tensor, bins: int = 15) -> Dict[str, object]:
+    """Calibration of top-1 confidences (Guo et al., 2017) from the device probabilities gvk_eval_rows wrote: proba f32 [N, K], labels [N]
+    within [0, K).  gvk_calibration_bins counts, per equal-width confidence bin (i / bins, (i + 1) / bins], the rows, the correct top-1
+    predictions and the confidence sum, and sums the Brier and NLL terms, every sum in row order; the rest is float64 on the host:
+      ece  = sum_i (n_i / N) |acc_i - conf_i|        mce = max_i |acc_i - conf_i| over the non-empty bins
+      brier = (1 / N) sum_n sum_k (p_nk - 1[y_n = k])^2        nll = (1 / N) sum_n -log max(p_n,y_n, FLT_MIN)
+      bin_count int64 [bins], bin_accuracy / bin_confidence f64 [bins] (NaN for an empty bin): the reliability diagram."""
+    if not isinstance(proba, torch.Tensor) or not proba.is_cuda:
+        raise GavikoHipError("calibration: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    if proba.dim() != 2:
+        raise GavikoHipError(f"calibration: expected proba [N, K], got {tuple(proba.shape)}")
+    N, K = proba.shape
+    labels = torch.as_tensor(labels).to(proba.device).to(torch.int64).contiguous()
+    if labels.numel() != N or N < 1:
+        raise GavikoHipError(f"calibration: {labels.numel()} labels for {N} rows of probabilities")
+    if int(labels.min()) < 0 or int(labels.max()) >= K:
+        raise GavikoHipError(f"calibration: labels outside [0, {K})")
+    r = ops.calibration_bins(proba.detach().float().contiguous(), labels, bins)
+    count = r["count"].cpu().numpy()
+    correct = r["correct"].cpu().numpy().astype(np.float64)
+    conf_sum = r["conf_sum"].cpu().numpy()
+    some = count > 0
+    acc = np.full(bins, np.nan)
+    conf = np.full(bins, np.nan)
+    acc[some] = correct[some] / count[some]
+    conf[some] = conf_sum[some] / count[some]
+    gap = np.abs(acc[some] - conf[some])
+    return {"ece": float((count[some] / float(N) * gap).sum()), "mce": float(gap.max()), "brier": float(r["brier"].item()) / float(N),
+            "nll": float(r["nll"].item()) / float(N), "bin_count": count, "bin_accuracy": acc, "bin_confidence": conf}
 
 
 class Evaluator:
@@ -65,8 +97,13 @@ class Evaluator:
             auc: Optional[float] = macro_ovr_auc(counts.cpu().numpy())
         except ValueError:
             auc = None
+        try:
+            cal: Optional[dict] = calibration(proba, labels)
+        except GavikoHipError:                               # labels outside [0, K): the confusion counts skip them, calibration has no term for them
+            cal = None
         return {"accuracy": float(np.trace(conf)) / float(N), "quadratic_kappa": kappa_quadratic(conf), "auc": auc, "confusion": conf,
-                "y_pred": pred.cpu().numpy(), "y_pred_proba": proba.cpu().numpy(), "y_test": labels.cpu().numpy()}
+                "y_pred": pred.cpu().numpy(), "y_pred_proba": proba.cpu().numpy(), "y_test": labels.cpu().numpy(),
+                "calibration": cal}
 
 
 def _versioned_csv(results_dir: str, method: str, backbone: str, kind: str, mri_paths, y_pred):

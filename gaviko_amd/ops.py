@@ -1219,3 +1219,87 @@ def dropout_rows(x, drop_p, seed, seed_ptr, out32=None, out16=None, M=None, N=No
     d = L.DropoutDesc(x=L.ptr(x), out32=L.ptr(out32) if out32 is not None else None, out16=L.ptr(out16) if out16 is not None else None,
                       seed_ptr=L.ptr(seed_ptr), M=M, N=N, ld=ld, rows_in=rows_in, rows_out=rows_out, row_off=row_off, drop_p=float(drop_p), seed=int(seed))
     L.check(L.load().gvk_dropout_rows(C.byref(d), L.stream_ptr()), "gvk_dropout_rows")
+
+
+# ---- predictive uncertainty and calibration (csrc/uncertainty.hip) ----
+STATS_MAX_CLASSES = 256         # gvk_predictive_stats: 4 classes per lane of one wave, in registers
+CALIBRATION_MAX_BINS = 254      # gvk_calibration_bins: one thread of the workgroup per bin (+ one each for the Brier and NLL sums)
+
+
+def tta_volumes(x: torch.Tensor, src: torch.Tensor, flip: torch.Tensor, out: torch.Tensor) -> None:
+    """out[o] = x[src[o]] mirrored along the axes named by the bits of flip[o] (bit 0 = D, bit 1 = H, bit 2 = W), bit for bit; flip[o] = 0 is a
+    plain replica.  x f32 [S,1,D,H,W], out f32 [Bout,1,D,H,W] (not overlapping x), src / flip i32 [Bout] device tables (src within [0, S))."""
+    _chk(x, torch.float32, "tta_volumes x")
+    _chk(out, torch.float32, "tta_volumes out")
+    if x.dim() != 5 or out.dim() != 5 or x.shape[1] != 1 or tuple(out.shape[1:]) != tuple(x.shape[1:]) or x.shape[0] < 1 or out.shape[0] < 1 \
+            or min(x.shape[2:]) < 1:
+        raise L.GavikoHipError(f"tta_volumes: expected x [S,1,D,H,W] and out [Bout,1,D,H,W], got {tuple(x.shape)} and {tuple(out.shape)}")
+    S, _, D, H, W = x.shape
+    Bout = out.shape[0]
+    _tab(src, "tta_volumes src", Bout)
+    _tab(flip, "tta_volumes flip", Bout)
+    xe, oe = x.data_ptr() + x.numel() * 4, out.data_ptr() + out.numel() * 4
+    if not (oe <= x.data_ptr() or xe <= out.data_ptr()):
+        raise L.GavikoHipError("tta_volumes: out must not overlap x")
+    if Bout * D * H * W >= 1 << 31:
+        raise L.GavikoHipError(f"tta_volumes: {Bout} x {D * H * W} voxels per launch exceed the kernel's 32-bit index range")
+    L.check(L.load().gvk_tta_volumes(L.ptr(x), L.ptr(src), L.ptr(flip), L.ptr(out), Bout, S, D, H, W, L.stream_ptr()), "gvk_tta_volumes")
+
+
+def predictive_stats(member_logits: torch.Tensor, B: int, S: int, out: dict = None) -> dict:
+    """member_logits f32 [B, S, K] (B samples, S members each) -> dict of device tensors: probs f32 [B, K] (mean member softmax), pred i32 [B]
+    (its argmax, lowest index on a tie), entropy / expected_entropy / mutual_info / variation_ratio f32 [B] (nats; mutual_info clamped at 0),
+    std f32 [B, K] (population), votes i32 [B, K] (the members' own argmax counts).  `out`: the same dict, to write into existing tensors."""
+    _chk(member_logits, torch.float32, "predictive_stats member_logits")
+    B, S = int(B), int(S)
+    if S < 1:
+        raise L.GavikoHipError(f"predictive_stats: S = {S} members (at least 1)")
+    if B < 1 or member_logits.numel() % (B * S) or member_logits.numel() == 0:
+        raise L.GavikoHipError(f"predictive_stats: {tuple(member_logits.shape)} is not [B = {B}, S = {S}, K]")
+    K = member_logits.numel() // (B * S)
+    if not 2 <= K <= STATS_MAX_CLASSES:
+        raise L.GavikoHipError(f"predictive_stats: K = {K} classes outside [2, {STATS_MAX_CLASSES}] (one wave keeps 4 classes per lane in registers)")
+    dev = member_logits.device
+    spec = {"probs": ((B, K), torch.float32), "pred": ((B,), torch.int32), "entropy": ((B,), torch.float32),
+            "expected_entropy": ((B,), torch.float32), "mutual_info": ((B,), torch.float32), "variation_ratio": ((B,), torch.float32),
+            "std": ((B, K), torch.float32), "votes": ((B, K), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in spec.items()}
+    for k, (shape, dt) in spec.items():
+        if k not in out:
+            raise L.GavikoHipError(f"predictive_stats out: {k!r} is missing")
+        _chk(out[k], dt, "predictive_stats " + k)
+        if tuple(out[k].shape) != shape:
+            raise L.GavikoHipError(f"predictive_stats {k}: expected {shape}, got {tuple(out[k].shape)}")
+    L.check(L.load().gvk_predictive_stats(L.ptr(member_logits), L.ptr(out["probs"]), L.ptr(out["pred"]), L.ptr(out["entropy"]),
+                                          L.ptr(out["expected_entropy"]), L.ptr(out["mutual_info"]), L.ptr(out["variation_ratio"]),
+                                          L.ptr(out["std"]), L.ptr(out["votes"]), B, S, K, L.stream_ptr()), "gvk_predictive_stats")
+    return out
+
+
+def calibration_bins(proba: torch.Tensor, target: torch.Tensor, nbins: int, out: dict = None) -> dict:
+    """proba f32 [N, K], target i64 [N] (within [0, K): the caller's contract) -> dict of device tensors over the equal-width confidence bins
+    (i / nbins, (i + 1) / nbins]: count i64 [nbins], correct i64 [nbins], conf_sum f64 [nbins]; brier f64 [1], nll f64 [1] (sums over the rows)."""
+    _chk(proba, torch.float32, "calibration_bins proba")
+    if proba.dim() != 2 or proba.shape[0] < 1 or proba.shape[1] < 1:
+        raise L.GavikoHipError(f"calibration_bins proba: expected [N, K], got {tuple(proba.shape)}")
+    N, K = proba.shape
+    _chk(target, torch.int64, "calibration_bins target")
+    if target.numel() != N:
+        raise L.GavikoHipError(f"calibration_bins target: expected {N} labels, got {tuple(target.shape)}")
+    if isinstance(nbins, bool) or not isinstance(nbins, int) or not 1 <= nbins <= CALIBRATION_MAX_BINS:
+        raise L.GavikoHipError(f"calibration_bins: nbins = {nbins!r} outside [1, {CALIBRATION_MAX_BINS}] (one thread of the workgroup per bin)")
+    dev = proba.device
+    spec = {"count": (nbins, torch.int64), "correct": (nbins, torch.int64), "conf_sum": (nbins, torch.float64), "brier": (1, torch.float64),
+            "nll": (1, torch.float64)}
+    if out is None:
+        out = {k: torch.empty(n, dtype=dt, device=dev) for k, (n, dt) in spec.items()}
+    for k, (n, dt) in spec.items():
+        if k not in out:
+            raise L.GavikoHipError(f"calibration_bins out: {k!r} is missing")
+        _chk(out[k], dt, "calibration_bins " + k)
+        if out[k].numel() != n:
+            raise L.GavikoHipError(f"calibration_bins {k}: expected {n} entries, got {tuple(out[k].shape)}")
+    L.check(L.load().gvk_calibration_bins(L.ptr(proba), L.ptr(target), L.ptr(out["count"]), L.ptr(out["correct"]), L.ptr(out["conf_sum"]),
+                                          L.ptr(out["brier"]), L.ptr(out["nll"]), N, K, nbins, L.stream_ptr()), "gvk_calibration_bins")
+    return out

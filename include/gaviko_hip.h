@@ -697,6 +697,31 @@ int gvk_perturb_scores(const float* logits, const int32_t* src, const int32_t* t
                        float* rows, int Bout, int S, int K, int nslots, void* stream);
 int gvk_curve_auc(const float* prob, const int32_t* ks, float* auc, int S, int P, int N, void* stream);
 
+/* ---- predictive uncertainty and calibration (csrc/uncertainty.hip): Monte-Carlo dropout, flip test-time augmentation, reliability bins ----
+ * gvk_tta_volumes: out f32 [Bout][D][H][W], out[o] = x[src[o]] mirrored along the axes named by the bits of flip[o] (bit 0 = D, bit 1 = H,
+ *   bit 2 = W); flip[o] = 0 is a plain replica.  x f32 [S][D][H][W]; src / flip int32 [Bout] DEVICE tables (src within [0, S)).  A move of
+ *   32-bit words: bit-exact.  16-byte accesses when W % 4 == 0 and the pointers are 16-byte aligned (the W mirror reads the mirrored float4
+ *   and reverses its lanes), one voxel per thread otherwise.  out must not overlap x; Bout * D*H*W < 2^31.  Bytes: Bout*V*4 written, as many read.
+ * gvk_predictive_stats: member_logits f32 [B][S][K] (B samples, S members each) -> per sample
+ *     probs f32 [B][K]        mean over the members of softmax(logits) (max-subtracted, fp32)
+ *     pred i32 [B]            argmax of probs, lowest index on an exact tie
+ *     entropy [B]             H[mean p] in nats (0 log 0 = 0)
+ *     expected_entropy [B]    mean over the members of H[p_s]
+ *     mutual_info [B]         max(entropy - expected_entropy, 0)
+ *     variation_ratio [B]     1 - max_k votes[k] / S
+ *     std f32 [B][K]          population standard deviation of the member probabilities (two passes: exactly 0 for S = 1)
+ *     votes i32 [B][K]        how many members have their own argmax (lowest index on a tie) at k
+ *   One wave per sample, no atomics: deterministic.  S >= 1; 2 <= K <= 256 (4 classes per lane in registers).
+ * gvk_calibration_bins: proba f32 [N][K] (what gvk_eval_rows wrote), target int64 [N] -> per equal-width confidence bin (i/nbins, (i+1)/nbins]
+ *   count int64 [nbins], correct int64 [nbins] (top-1 hits), conf_sum f64 [nbins]; brier f64 [1] = sum_n sum_k (p_nk - 1[y_n = k])^2;
+ *   nll f64 [1] = sum_n -log max(p_n,y_n, FLT_MIN).  Confidence = max_k p, prediction = its lowest index, bin = ceil(conf * nbins) - 1 (exact
+ *   in double), clamped to [0, nbins).  One workgroup, every sum in row order: deterministic.  1 <= nbins <= 254; labels within [0, K). */
+int gvk_tta_volumes(const float* x, const int32_t* src, const int32_t* flip, float* out, int Bout, int S, int D, int H, int W, void* stream);
+int gvk_predictive_stats(const float* member_logits, float* probs, int32_t* pred, float* entropy, float* expected_entropy, float* mutual_info,
+                         float* variation_ratio, float* std, int32_t* votes, int B, int S, int K, void* stream);
+int gvk_calibration_bins(const float* proba, const void* target, int64_t* count, int64_t* correct, double* conf_sum, double* brier, double* nll,
+                         int N, int K, int nbins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
