@@ -323,11 +323,12 @@ class Engine(GavikoPaths, PeftPaths):
         if names is None or any(n in self._fold_names for n in names):
             self._fold_version = None
 
-    def workspace(self, B: int, device, train: bool, keep_attn: bool = False, tag: Optional[str] = None):
+    def workspace(self, B: int, device, train: bool, keep_attn: bool = False, tag: Optional[str] = None, feat: Optional[tuple] = None):
         """keep_attn (inference only, gaviko_amd.explain): a workspace of its own whose forward keeps every layer's qkv / lse (and every
         other per-layer slot) as a training forward does, for the attention-map kernels.  tag: another workspace of its own for the same
-        (B, mode) -- 'igrad', the input-gradient sweeps of gaviko_amd.explain."""
-        key = (B, train, str(device)) + (("attn",) if keep_attn else ()) + ((tag,) if tag else ())
+        (B, mode) -- 'igrad', the input-gradient sweeps of gaviko_amd.explain.  feat (inference only, gaviko_amd.features): a workspace of
+        its own with the per-layer summary slots feat_cls / feat_patch [len(feat)][B][C] of feature_forward."""
+        key = (B, train, str(device)) + (("attn",) if keep_attn else ()) + ((tag,) if tag else ()) + (("feat", feat) if feat else ())
         if key in self._wss:
             self._ws = self._wss[key]
             return self._ws
@@ -353,6 +354,9 @@ class Engine(GavikoPaths, PeftPaths):
             ws["act"][:, self.mlp + 3 * self.Lat: self.mlp + 3 * self.Lat + 2] = 1.0     # the two bias columns (b_hi, b_lo); the rest of the slot stays 0
         ws["stat"] = [[torch.zeros(M, device=device) for _ in range(4)] for _ in range(nsave)]   # mean1, rstd1, mean2, rstd2
         ws["pooled"] = torch.zeros((B, C), device=device)
+        if feat:
+            ws["feat_cls"] = torch.zeros((len(feat), B, C), device=device)
+            ws["feat_patch"] = torch.zeros((len(feat), B, C), device=device)
         if self._fold_ln1:
             ws["xg16"] = z(M, C, bf16)                                          # bf16 copy of the global stream entering a folded layer
             ws["spart"] = torch.zeros((C // 64) * M * 2, device=device)         # per-row (sum, sum of squares) over 64-column groups
@@ -564,7 +568,8 @@ class Engine(GavikoPaths, PeftPaths):
         return
 
     # ------------------------------------------------------------------ forward
-    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None, keep_attn: bool = False, ws_tag: Optional[str] = None) -> torch.Tensor:
+    def forward(self, img: torch.Tensor, train: bool, drop: Optional[dict] = None, keep_attn: bool = False, ws_tag: Optional[str] = None,
+                feat: Optional[tuple] = None) -> torch.Tensor:
         L.require_device()
         if not img.is_cuda:
             raise L.GavikoHipError("input volume must be on the HIP device: gaviko_amd has no CPU path")
@@ -577,10 +582,11 @@ class Engine(GavikoPaths, PeftPaths):
         # nn.Dropout of the backbone itself (vision_transformer.py:33-34,52-54,157; vpt.py:129,148): live for the classes without a
         # train() override (linear / bitfit / fft, melo) and for VPT's prompt_dropout.  bf16 path only.
         sv["bdrop"], sv["edrop"], sv["pdrop"] = (float(drop.get(k, 0.0)) for k in ("dropout", "emb_dropout", "prompt_dropout"))
+        sv["feat"] = tuple(feat) if (feat and not train) else ()     # feature_forward: the layers whose entering stream is summarised
         if (sv["bdrop"] > 0 or sv["edrop"] > 0 or sv["pdrop"] > 0) and self.kind not in ("vit", "melo", "vpt", "adaptformer", "gaviko", "dvpt", "evp", "ssf"):
             raise L.GavikoHipError(f"backbone dropout > 0 in training mode: unknown kind {self.kind!r}")
         self.refresh_weights(need_dgrad=train)
-        ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train, tag=ws_tag)
+        ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train, tag=ws_tag, feat=sv["feat"] or None)
         if img.data_ptr() != ws["img"].data_ptr():           # a caller that fills input_buffer() itself skips the copy-in launch
             ws["img"].copy_(img.detach())                   # static input buffer (the only per-step host-visible copy-in)
         # unfrozen backbone tensors (`fft` / `bitfit`, train.py:123-137): which ones train, and whether GEMM inputs must be kept
@@ -598,6 +604,8 @@ class Engine(GavikoPaths, PeftPaths):
             key += ("attn",)                                 # its own workspace: its own launch plan
         if ws_tag:
             key += (ws_tag,)
+        if sv["feat"]:
+            key += ("feat", sv["feat"])                     # its own workspace and two token_pool launches per layer: its own plan
         self._keep_inputs = bool(sv["wgrad"])
         sv["pre_is_grad"] = self._pre_is_grad = bool(train and self._gelu_grad and not self._keep_inputs and sv["bdrop"] <= 0 and not bb)
         self._fold_on = (not self._keep_inputs) and self._ensure_fold()      # ONE place decides: operands are current whenever the fold is taken
@@ -636,6 +644,44 @@ class Engine(GavikoPaths, PeftPaths):
             return self.forward(img, train=False, drop=None)
         finally:
             self._restore_state(keep)
+
+    def feature_forward(self, img: torch.Tensor, layers: Optional[tuple] = None):
+        """The deterministic inference forward (no dropout) that also hands out the representation, for gaviko_amd.features.
+        layers=None: eval_forward's own recorded plan and workspace -> (logits, pooled); pooled [B, C] is a clone of the vector the head's
+        nn.Linear consumes (the mean over _pool_rows() of the final LayerNorm).
+        layers = a sorted tuple of indices in 0..depth (l: the global token stream entering layer l; depth: the output of the last layer,
+        before transformer.norm): a workspace and a plan of their own, in which two gvk_token_pool launches per requested layer run on the
+        main stream while that layer's stream is still live -> (logits, pooled, cls, patch_mean), the last two [len(layers), B, C]:
+        cls[j] = row r_cls (0 for VPT's [cls | prompts | patches], else row_off - 1), patch_mean[j] = the mean over the rows
+        row_off .. Ts[l] - 1 of that layer's own sequence (deep VPT's shrinks).  The launches write fixed workspace slots, so they are
+        recorded and replay.  With `depth` requested the last layer's MLP computes every row in this plan (dead-row pruning would leave the
+        patch rows unwritten); the logits are bit-identical either way.  GAViKO's local stream is not summarised.  The state of a
+        pending backward is put back, as for eval_forward."""
+        if layers is not None:
+            try:
+                layers = tuple(int(l) for l in layers)
+            except (TypeError, ValueError):
+                raise L.GavikoHipError(f"feature_forward: layers={layers!r}: expected None or a sorted tuple of ints") from None
+            if not layers or any(not 0 <= l <= self.depth for l in layers) or any(a >= b for a, b in zip(layers, layers[1:])):
+                raise L.GavikoHipError(f"feature_forward: layers={layers!r}: expected strictly increasing indices within [0, {self.depth}] "
+                                       f"(l: the stream entering layer l; {self.depth}: the output of the last layer)")
+        keep = self._pending_state()
+        try:
+            logits = self.forward(img, train=False, drop=None, feat=layers)
+            ws = self._ws
+            if layers is None:
+                return logits, ws["pooled"].clone()
+            return logits, ws["pooled"].clone(), ws["feat_cls"].clone(), ws["feat_patch"].clone()
+        finally:
+            self._restore_state(keep)
+
+    def _feat_pool(self, ws, sv, l, g, T):
+        """feature_forward: the CLS row and the patch-row mean of the stream g [B][T][C] entering layer l (l = depth: the last output)."""
+        if l in sv["feat"]:
+            j = sv["feat"].index(l)
+            r_cls = 0 if self.kind == "vpt" else self.row_off - 1
+            ops.token_pool(g, sv["B"], T, self.C, r_cls, 1, out=ws["feat_cls"][j])
+            ops.token_pool(g, sv["B"], T, self.C, self.row_off, T - self.row_off, out=ws["feat_patch"][j])
 
     def perturbed_forward(self, x: torch.Tensor, src: torch.Tensor, *, rank=None, lo=None, hi=None, boxes=None, fill_scalar=None, base=None,
                           slot=None, rows=None) -> torch.Tensor:
@@ -872,6 +918,8 @@ class Engine(GavikoPaths, PeftPaths):
             Mi = B * self.Ts[i]
             repack = self.kind == "vpt" and self.deep
             gout = ws["Go"] if repack else ws["G"][go]
+            if sv["feat"]:
+                self._feat_pool(ws, sv, i, ws["G"][gi], self.Ts[i])       # before anything of layer i touches its input (EVP adds its prompt in place)
             if gaviko:
                 if not train and i > 0:
                     self._wait("loc", "gpa")                         # eval ping-pongs Lc: the GPA of layer i-1 must be done with it
@@ -909,8 +957,10 @@ class Engine(GavikoPaths, PeftPaths):
             # fc2 carries proj_up of the PLAIN latents of every row (ready right behind the LayerNorm); the GPA has the two GEMMs' time
             # to finish, and only the P prompt rows it replaces are fixed up afterwards
             # the last layer's output is read at the pooled rows only (frozen backbone, no dropout behind fc2): its MLP runs on those rows
+            # (feature_forward with `depth` requested reads every row of that output: no pruning in that plan)
             last_rows = (self._panels(B, self._pool_rows()[0] + self._pool_rows()[1])
-                         if (gaviko and i + 1 == self.depth and up_in_fc2 and not self._keep_inputs and sv["bdrop"] <= 0) else None)
+                         if (gaviko and i + 1 == self.depth and up_in_fc2 and not self._keep_inputs and sv["bdrop"] <= 0
+                             and self.depth not in sv["feat"]) else None)
             self._mlp_block_fwd(ws, i, si, ws["G1"][si], gout, Mi, train, sv["bdrop"],
                                 up_in_fc2=up_in_fc2, stats_out=fold_next, panels=last_rows)
             if self.kind == "adaptformer":
@@ -942,6 +992,8 @@ class Engine(GavikoPaths, PeftPaths):
         if gaviko:
             self._wait(None, "loc")                                  # join the local chain (capture needs every fork joined)
         gfin = self._final_stream(ws, train)
+        if sv["feat"]:
+            self._feat_pool(ws, sv, self.depth, gfin, self.Ts[-1])
         r0, R = self._pool_rows()
         ops.head_fwd(g=gfin, ln_gamma=d(nm.root + "transformer.norm.weight"), ln_beta=d(nm.root + "transformer.norm.bias"),
                      wh=d(nm.head() + ".weight"), bh=d(nm.head() + ".bias"), logits=ws["logits"], pooled=ws["pooled"],

@@ -95,6 +95,8 @@ PgradOuter = _struct("PgradOuter", ["narrow", "wide", "narrow2", "wide2", "lat_o
                      ["M", "M2", "T", "P", "transposed", "accumulate", "C"], ["drop_p"], ["seed"])
 WindowColsumDesc = _struct("WindowColsumDesc", ["qkv", "lse", "w", "out"], ["B", "D", "H", "W", "kd", "kh", "kw", "L"], ["scale"])
 GpaMapsDesc = _struct("GpaMapsDesc", ["xl", "ll", "qg", "ql", "lse_g", "lse_l", "imp", "gw", "pg", "pl", "fused"], ["B", "T", "N", "P", "L"])
+FeatureTopkDesc = _struct("FeatureTopkDesc", ["q", "g", "exclude", "idx", "score", "scratch"], ["Nq", "Ng", "C", "k", "metric", "nslabs"],
+                          i64=["scratch_words"])
 HeadDesc = _struct("HeadDesc", ["g", "ln_gamma", "ln_beta", "wh", "bh", "logits", "pooled", "dlogits", "dg", "dwh", "dbh"],
                    ["B", "T", "C", "K", "r0", "R", "accumulate"])
 
@@ -205,12 +207,18 @@ SIGNATURES = {
     "gvk_tta_volumes": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_predictive_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gvk_calibration_bins": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_token_pool": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "gvk_l2_normalize_rows": [_P, _P, _P, _I, _I, _F, _P],
+    "gvk_feature_topk": [C.POINTER(FeatureTopkDesc), _P],
+    "gvk_knn_vote": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "gvk_class_means": [_P, _P, _P, _P, _I, _I, _I, _P],
 }
 NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, []), "gvk_abi_version": (C.c_int, []),
              "gvk_attention_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
              "gvk_attention_bwd_status_offset": (C.c_size_t, [C.c_size_t]),
              "gvk_gpa_gate_param_count": (C.c_int, [C.c_int, C.c_int]), "gvk_gemm_stat_parts": (C.c_int, [C.c_int]), "gvk_minmax_partials": (C.c_int, []),
              "gvk_param_grads_scratch": (C.c_int64, [C.POINTER(PgradOuter), C.c_int, C.POINTER(ReduceJob), C.c_int, C.c_int, C.c_int]),
+             "gvk_feature_topk_slabs": (C.c_int, [C.c_int, C.c_int, C.c_int]),
              "gvk_plan_begin": (C.c_int, []), "gvk_plan_end": (C.c_int, []), "gvk_plan_abort": (C.c_int, []),
              "gvk_plan_size": (C.c_int, [C.c_int]), "gvk_plan_replay": (C.c_int, [C.c_int]), "gvk_plan_free": (C.c_int, [C.c_int]),
              "gvk_plan_event_record": (C.c_int, [_P]), "gvk_plan_event_wait": (C.c_int, [_P, C.c_int]),
@@ -218,7 +226,8 @@ NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, [
              "gvk_plan_set_timing": (C.c_int, [C.c_int]),
              "gvk_plan_event_elapsed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)])}
 STRUCTS = {"gvk_gemm_desc": GemmDesc, "gvk_skinny_down_desc": SkinnyDownDesc, "gvk_skinny_up_desc": SkinnyUpDesc,
-           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc}
+           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
+           "gvk_feature_topk_desc": FeatureTopkDesc}
 
 # diag library only (include/gaviko_hip_diag.h): bound when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so
 DIAG_SIGNATURES = {}

@@ -1303,3 +1303,151 @@ def calibration_bins(proba: torch.Tensor, target: torch.Tensor, nbins: int, out:
     L.check(L.load().gvk_calibration_bins(L.ptr(proba), L.ptr(target), L.ptr(out["count"]), L.ptr(out["correct"]), L.ptr(out["conf_sum"]),
                                           L.ptr(out["brier"]), L.ptr(out["nll"]), N, K, nbins, L.stream_ptr()), "gvk_calibration_bins")
     return out
+
+
+# ---- feature embeddings and kNN probes (csrc/features.hip) ----
+FEATURE_MAX_DIM = 1024          # gvk_token_pool / gvk_feature_topk: C % 4 == 0, C <= 1024
+TOPK_MAX_K = 32                 # gvk_feature_topk / gvk_knn_vote: sorted lists of at most 32 entries
+VOTE_MAX_CLASSES = 256          # gvk_knn_vote: 4 classes per lane of one wave
+TOPK_METRICS = {"ip": 0, "l2": 1}
+
+
+def _feat_rows(t, what, C=None):
+    """A contiguous f32 device matrix [N, C] with C a multiple of 4 within [4, 1024] -> (N, C)."""
+    if not isinstance(t, torch.Tensor):
+        raise L.GavikoHipError(f"{what}: expected a tensor, got {type(t).__name__}")
+    _chk(t, torch.float32, what)
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise L.GavikoHipError(f"{what}: expected [N, C], got {tuple(t.shape)}")
+    N, Cc = t.shape
+    if Cc < 4 or Cc % 4 or Cc > FEATURE_MAX_DIM:
+        raise L.GavikoHipError(f"{what}: C = {Cc} (a multiple of 4 within [4, {FEATURE_MAX_DIM}])")
+    if C is not None and Cc != C:
+        raise L.GavikoHipError(f"{what}: C = {Cc}, expected {C}")
+    return N, Cc
+
+
+def token_pool(g: torch.Tensor, B: int, T: int, C: int, r0: int, R: int, out: torch.Tensor = None) -> torch.Tensor:
+    """out f32 [B, C] = mean over the rows [r0, r0 + R) of the token stream g f32 [B][T][C] (the first B * T * C elements of g; row pitch
+    C).  R = 1 copies row r0 bit for bit.  The summation order depends on R alone."""
+    _chk(g, torch.float32, "token_pool g")
+    B, T, C, r0, R = int(B), int(T), int(C), int(r0), int(R)
+    if B < 1 or T < 1 or g.numel() < B * T * C:
+        raise L.GavikoHipError(f"token_pool: g has {g.numel()} elements, [B = {B}, T = {T}, C = {C}] needs {B * T * C}")
+    if C < 4 or C % 4 or C > FEATURE_MAX_DIM:
+        raise L.GavikoHipError(f"token_pool: C = {C} (a multiple of 4 within [4, {FEATURE_MAX_DIM}])")
+    if r0 < 0 or R < 1 or R > T - r0:
+        raise L.GavikoHipError(f"token_pool: rows [{r0}, {r0} + {R}) outside the {T} rows of the stream")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=g.device)
+    _chk(out, torch.float32, "token_pool out", B * C)
+    L.check(L.load().gvk_token_pool(L.ptr(g), L.ptr(out), B, T, C, r0, R, L.stream_ptr()), "gvk_token_pool")
+    return out
+
+
+def l2_normalize_rows(x: torch.Tensor, out: torch.Tensor = None, norm: torch.Tensor = None, eps: float = 1e-12) -> torch.Tensor:
+    """y[n] = x[n] / max(||x[n]||, eps) for x f32 [N, C]; out=x normalises in place; norm f32 [N] (optional) receives the norms."""
+    if not isinstance(x, torch.Tensor):
+        raise L.GavikoHipError(f"l2_normalize_rows x: expected a tensor, got {type(x).__name__}")
+    _chk(x, torch.float32, "l2_normalize_rows x")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise L.GavikoHipError(f"l2_normalize_rows x: expected [N, C], got {tuple(x.shape)}")
+    if not float(eps) > 0.0:
+        raise L.GavikoHipError(f"l2_normalize_rows: eps = {eps!r} (must be positive)")
+    N, C_ = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(out, torch.float32, "l2_normalize_rows out")
+    if tuple(out.shape) != tuple(x.shape):
+        raise L.GavikoHipError(f"l2_normalize_rows out: expected {tuple(x.shape)}, got {tuple(out.shape)}")
+    if out.data_ptr() != x.data_ptr():
+        xe, oe = x.data_ptr() + x.numel() * 4, out.data_ptr() + out.numel() * 4
+        if not (oe <= x.data_ptr() or xe <= out.data_ptr()):
+            raise L.GavikoHipError("l2_normalize_rows: out must be x itself or not overlap it")
+    if norm is not None:
+        _chk(norm, torch.float32, "l2_normalize_rows norm")
+        if norm.numel() != N:
+            raise L.GavikoHipError(f"l2_normalize_rows norm: expected {N} entries, got {tuple(norm.shape)}")
+    L.check(L.load().gvk_l2_normalize_rows(L.ptr(x), L.ptr(out), L.ptr(norm), N, C_, float(eps), L.stream_ptr()), "gvk_l2_normalize_rows")
+    return out
+
+
+def feature_topk(q: torch.Tensor, g: torch.Tensor, k: int, metric: str = "ip", exclude: torch.Tensor = None, slabs: int = None):
+    """The k best bank rows of every query -> (idx i32 [Nq, k], score f32 [Nq, k]), best first.  q f32 [Nq, C], g f32 [Ng, C];
+    metric 'ip' (score q . g, larger is better) or 'l2' (score = squared distance, smaller is better); an exact tie of the fp32 score goes to
+    the lower bank index.  exclude i32 [Nq] (device): one bank index per query that is skipped (-1: none).  slabs: force the number of bank
+    slabs (rounded to the nearest valid count, at most 128; None: the default split) -- the result does not depend on it."""
+    Nq, C_ = _feat_rows(q, "feature_topk q")
+    Ng, _ = _feat_rows(g, "feature_topk g", C_)
+    if metric not in TOPK_METRICS:
+        raise L.GavikoHipError(f"feature_topk: metric = {metric!r}: expected 'ip' or 'l2'")
+    if g.device != q.device:
+        raise L.GavikoHipError(f"feature_topk: q on {q.device}, g on {g.device}")
+    if Nq * Ng >= 1 << 31:
+        raise L.GavikoHipError(f"feature_topk: Nq * Ng = {Nq} * {Ng} exceeds the kernel's 32-bit range (split the queries)")
+    if exclude is not None:
+        _tab(exclude, "feature_topk exclude", Nq)
+    avail = Ng - (1 if exclude is not None else 0)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(TOPK_MAX_K, avail):
+        raise L.GavikoHipError(f"feature_topk: k = {k!r} outside [1, min({TOPK_MAX_K}, {avail})] ({Ng} bank rows"
+                               + (", one excluded per query)" if exclude is not None else ")"))
+    if slabs is not None and (isinstance(slabs, bool) or not isinstance(slabs, int) or slabs < 1):
+        raise L.GavikoHipError(f"feature_topk: slabs = {slabs!r}: expected None or a positive int")
+    lib = L.load()
+    nslabs = lib.gvk_feature_topk_slabs(Nq, Ng, 0 if slabs is None else slabs)
+    words = 2 * Nq * nslabs * k
+    scratch = torch.empty(words, dtype=torch.int32, device=q.device)
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=q.device)
+    score = torch.empty((Nq, k), dtype=torch.float32, device=q.device)
+    d = L.FeatureTopkDesc(q=L.ptr(q), g=L.ptr(g), exclude=L.ptr(exclude) if exclude is not None else None, idx=L.ptr(idx), score=L.ptr(score),
+                          scratch=L.ptr(scratch), Nq=Nq, Ng=Ng, C=C_, k=k, metric=TOPK_METRICS[metric], nslabs=nslabs, scratch_words=words)
+    L.check(lib.gvk_feature_topk(C.byref(d), L.stream_ptr()), "gvk_feature_topk")
+    return idx, score
+
+
+def knn_vote(idx: torch.Tensor, score: torch.Tensor, labels: torch.Tensor, num_classes: int, weights: str = "uniform", temperature: float = 0.07):
+    """Neighbour lists idx i32 / score f32 [Nq, k] (what feature_topk returns; for 'l2' pass -distance) and bank labels i32 [Ng] within
+    [0, num_classes) -> (probs f32 [Nq, K], pred i32 [Nq]).  weights 'uniform': votes / k; 'softmax': exp((score_j - score_0) / temperature),
+    normalised, summed in rank order.  pred: the lowest class on an exact tie.  The labels' range is the caller's contract."""
+    _chk(idx, torch.int32, "knn_vote idx")
+    _chk(score, torch.float32, "knn_vote score")
+    if idx is None or score is None or idx.dim() != 2 or tuple(idx.shape) != tuple(score.shape) or idx.shape[0] < 1:
+        raise L.GavikoHipError(f"knn_vote: expected idx and score [Nq, k], got {None if idx is None else tuple(idx.shape)} and "
+                               f"{None if score is None else tuple(score.shape)}")
+    Nq, k = idx.shape
+    if not 1 <= k <= TOPK_MAX_K:
+        raise L.GavikoHipError(f"knn_vote: k = {k} outside [1, {TOPK_MAX_K}]")
+    _chk(labels, torch.int32, "knn_vote labels")
+    if labels is None or labels.dim() != 1 or labels.numel() < 1:
+        raise L.GavikoHipError(f"knn_vote labels: expected i32 [Ng], got {None if labels is None else tuple(labels.shape)}")
+    K = num_classes
+    if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= VOTE_MAX_CLASSES:
+        raise L.GavikoHipError(f"knn_vote: num_classes = {K!r} outside [2, {VOTE_MAX_CLASSES}]")
+    if weights not in ("uniform", "softmax"):
+        raise L.GavikoHipError(f"knn_vote: weights = {weights!r}: expected 'uniform' or 'softmax'")
+    if weights == "softmax" and not float(temperature) > 0.0:
+        raise L.GavikoHipError(f"knn_vote: temperature = {temperature!r} (must be positive)")
+    probs = torch.empty((Nq, K), dtype=torch.float32, device=idx.device)
+    pred = torch.empty(Nq, dtype=torch.int32, device=idx.device)
+    L.check(L.load().gvk_knn_vote(L.ptr(idx), L.ptr(score), L.ptr(labels), L.ptr(probs), L.ptr(pred), Nq, labels.numel(), k, K,
+                                  1 if weights == "softmax" else 0, float(temperature), L.stream_ptr()), "gvk_knn_vote")
+    return probs, pred
+
+
+def class_means(x: torch.Tensor, labels: torch.Tensor, num_classes: int):
+    """x f32 [N, C], labels i32 [N] within [0, num_classes) -> (mean f32 [K, C], count i32 [K]); every class summed in row order; an empty
+    class gives count 0 and a row of exact zeros.  The labels' range is the caller's contract (rows with other labels join no class)."""
+    if not isinstance(x, torch.Tensor):
+        raise L.GavikoHipError(f"class_means x: expected a tensor, got {type(x).__name__}")
+    _chk(x, torch.float32, "class_means x")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise L.GavikoHipError(f"class_means x: expected [N, C], got {tuple(x.shape)}")
+    N, C_ = x.shape
+    _tab(labels, "class_means labels", N)
+    K = num_classes
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 65535:
+        raise L.GavikoHipError(f"class_means: num_classes = {K!r} outside [1, 65535]")
+    mean = torch.empty((K, C_), dtype=torch.float32, device=x.device)
+    count = torch.empty(K, dtype=torch.int32, device=x.device)
+    L.check(L.load().gvk_class_means(L.ptr(x), L.ptr(labels), L.ptr(mean), L.ptr(count), N, C_, K, L.stream_ptr()), "gvk_class_means")
+    return mean, count

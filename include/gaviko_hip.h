@@ -722,6 +722,43 @@ int gvk_predictive_stats(const float* member_logits, float* probs, int32_t* pred
 int gvk_calibration_bins(const float* proba, const void* target, int64_t* count, int64_t* correct, double* conf_sum, double* brier, double* nll,
                          int N, int K, int nbins, void* stream);
 
+/* ---- feature embeddings and kNN probes (csrc/features.hip; gaviko_amd/features.py) ----
+ * All fp32, no atomics, every sum in a fixed order: two runs are bit-identical.
+ * gvk_token_pool: out f32 [B][C], out[b][c] = (1/R) sum_{r in [r0, r0+R)} g[b][r][c] of a token stream g f32 [B][T][C] (row pitch C).
+ *   1 <= R <= T - r0, C % 4 == 0, C <= 1024.  R = 1 copies row r0 bit for bit (no division).  16 waves per (64-column tile, sample): wave w adds
+ *   the rows w, w+16, ... in order, the 16 partials are added as a fixed binary tree -- the order depends on R alone.  Bytes: B*R*C*4 read.
+ * gvk_l2_normalize_rows: y[n] = x[n] / max(||x[n]||, eps) for x f32 [N][C]; y == x (in place) or disjoint; norm f32 [N] (optional) receives
+ *   ||x[n]||.  One wave per row, the squares added per lane in column order, then the xor butterfly.
+ * gvk_feature_topk: queries q f32 [Nq][C], bank g f32 [Ng][C] -> idx int32 [Nq][k], score f32 [Nq][k], best first.
+ *     metric 0: score = q . g, larger is better.  metric 1: score = (||q||^2 + ||g||^2) - 2 q . g (squared L2), smaller is better.
+ *   An exact tie of the fp32 score goes to the LOWER bank index.  exclude int32 [Nq] (optional): one bank index per query that is skipped
+ *   (-1: none).  NaN scores are never selected; a slot with no candidate left holds index -1.
+ *   1 <= k <= 32, k <= Ng - (exclude ? 1 : 0), C % 4 == 0, C <= 1024, Nq, Ng >= 1, Nq * Ng < 2^31.
+ *   Products on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation), 16 queries x 16 bank rows per tile, the contraction in an
+ *   order that depends on C alone: a score does not depend on Nq, Ng, its tile or the slab split.  The bank is cut into `nslabs` slabs of
+ *   16-row tiles over workgroups (grid = query tiles x slabs, so a handful of queries still fills the device); every slab keeps a sorted
+ *   top-k per query, a second kernel merges the slab lists by the same (score, index) rule -- the result does not depend on nslabs.
+ *   nslabs must be a value gvk_feature_topk_slabs(Nq, Ng, want) returns (want <= 0: the default; want > 0: the nearest valid count, at most
+ *   128); scratch: 2 * Nq * nslabs * k 32-bit words.
+ * gvk_knn_vote: idx / score [Nq][k] (as written above), labels int32 [Ng] -> probs f32 [Nq][K], pred int32 [Nq] (argmax, lowest class on a tie).
+ *   mode 0: probs[c] = #{j: label[idx_j] == c} / k.  mode 1: w_j = exp((score_j - score_0) / temperature), probs[c] = sum_{j: label = c} w_j /
+ *   sum_j w_j, summed in rank order (for metric 1 pass -distance).  Weights and sums in double, one rounding at the store.  An index outside
+ *   [0, Ng) or a label outside [0, K) has no vote (the caller rejects such labels).  1 <= k <= 32, 2 <= K <= 256.
+ * gvk_class_means: x f32 [N][C], labels int32 [N] -> mean f32 [K][C], count int32 [K]; every class summed in row order; an empty class
+ *   gives count 0 and a row of exact zeros. */
+typedef struct gvk_feature_topk_desc {
+  const float* q; const float* g; const int32_t* exclude; int32_t* idx; float* score; void* scratch;
+  int32_t Nq, Ng, C, k, metric, nslabs;
+  int64_t scratch_words;
+} gvk_feature_topk_desc;
+int gvk_token_pool(const float* g, float* out, int B, int T, int C, int r0, int R, void* stream);
+int gvk_l2_normalize_rows(const float* x, float* y, float* norm, int N, int C, float eps, void* stream);
+int gvk_feature_topk_slabs(int Nq, int Ng, int want);
+int gvk_feature_topk(const gvk_feature_topk_desc* d, void* stream);
+int gvk_knn_vote(const int32_t* idx, const float* score, const int32_t* labels, float* probs, int32_t* pred, int Nq, int Ng, int k, int K, int mode,
+                 float temperature, void* stream);
+int gvk_class_means(const float* x, const int32_t* labels, float* mean, int32_t* count, int N, int C, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
