@@ -1,8 +1,11 @@
-"""Constants, switches and small helpers shared by the launch-plan engine (engine.py) and its method-specific halves
-(engine_gaviko.py: the MWSA / GPA side paths; engine_peft.py: AdaptFormer, LoRA, unfrozen-backbone gradients, EVP, DVPT, SSF)."""
+"""Constants, switches and small helpers shared by the launch-plan engine (engine.py) and its halves (engine_gaviko.py: the MWSA / GPA
+side paths; engine_peft.py: AdaptFormer, LoRA, unfrozen-backbone gradients, EVP, DVPT, SSF; engine_analysis.py: the entry points of
+gaviko_amd.explain / uncertainty / features)."""
 from __future__ import annotations
 
 import os
+
+import torch
 
 from . import lib as L
 
@@ -39,6 +42,17 @@ _SIDE_STREAMS = {}                       # (device index, kind) -> the process-w
 # attention backward (669 vs 688: it then slows the next layer's dgrad GEMMs as much as it slowed the attention kernels, start->fc1d 82 -> 98 us).
 _EPI_NAMES = {0: "store_bf16", 1: "bias_res_f32", 2: "bias_gelu_bf16", 3: "patch_f32", 4: "gelu_bwd_bf16", 5: "store_f32", 6: "bias_res_f32_bf16",
               7: "bias_relu_bf16", 8: "relu_bwd_bf16"}
+
+
+def flat_views(params, names, device, min_elems: int = 0):
+    """-> (buf, {name: view}): one zero fp32 buffer on `device` holding a slice of params[name]'s shape for every name, in that order."""
+    buf = torch.zeros(max(min_elems, sum(params[n].numel() for n in names)), device=device)
+    views, off = {}, 0
+    for n in names:
+        k = params[n].numel()
+        views[n] = buf[off: off + k].view(params[n].shape)
+        off += k
+    return buf, views
 
 
 def evp_highpass_operator(D: int, H: int, W: int, rate: float):

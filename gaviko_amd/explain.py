@@ -3,8 +3,8 @@
 In the reference every global self-attention runs its probabilities through an `nn.Softmax` module (`Attention.attend`,
 vision_transformer.py:50,67), and a forward hook there yields the attention maps.  Here the modules are parameter containers and the
 flash kernels never build the probability matrix, so the maps are recomputed from the forward's own buffers: an inference forward in a
-workspace of its own keeps every layer's qkv and softmax statistics (Engine.attention_forward), and csrc/attention_map.hip forms the
-row-weighted sums of P from them, as the backward recomputes P from lse.
+workspace of its own keeps every layer's qkv and softmax statistics (Engine.attention_forward; the engine side of this module is
+engine_analysis.py), and csrc/attention_map.hip forms the row-weighted sums of P from them, as the backward recomputes P from lse.
 
     logits, maps = attention_maps(model, img)            # maps[i]: [B, H, T_i], the pooled query's attention in layer i
     logits, rel = attention_rollout(model, img)          # rel: [B, T], sums to 1 per sample
@@ -64,6 +64,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from ._checks import batch_rows, chunk_tables, volume_check
 
 _ATTENTIONS = ("global",)
 
@@ -158,7 +159,7 @@ def _relevance_checks(model, img, target, what):
     B = img.shape[0]
     if target is not None:
         _targets(eng, torch.zeros((B, eng.K)), target, B)            # a bad target is rejected here (host tensors only)
-    eng, x = _volume_check(model, img, what)                         # (and the device)
+    eng, x = volume_check(model, img, what)                         # (and the device)
 
     def seed(logits):
         return torch.nn.functional.one_hot(_targets(eng, logits, target, B), eng.K).to(logits.dtype)
@@ -206,18 +207,6 @@ def patch_grid(model, relevance: torch.Tensor) -> torch.Tensor:
 
 
 # ---- gradient attributions ----------------------------------------------------------------------------------------------------
-def _volume_check(model, img, what):
-    eng = model._engine()
-    if not isinstance(img, torch.Tensor) or not img.is_cuda:
-        raise L.GavikoHipError(f"{what} runs on the HIP device: move the model and the input there (there is no CPU path)")
-    want = (1,) + tuple(g * p for g, p in zip(eng.grid, eng.patch))
-    if img.dim() != 5 or tuple(img.shape[1:]) != want or img.shape[0] < 1:
-        raise L.GavikoHipError(f"{what}: expected img [B, {', '.join(map(str, want))}], got {tuple(img.shape)}")
-    if img.dtype != torch.float32:
-        raise L.GavikoHipError(f"{what}: expected a float32 volume, got {img.dtype}")
-    return eng, img.detach().contiguous()
-
-
 def _targets(eng, logits, target, B) -> torch.Tensor:
     """int64 [B] device tensor of the logit to explain per sample: None -> the argmax of `logits`, an int, or a [B] tensor."""
     dev = logits.device
@@ -244,14 +233,6 @@ def _onehot(tgt, K):
     return lambda logits: torch.nn.functional.one_hot(tgt, K).to(logits.dtype)
 
 
-def _batch(batch, default):
-    if batch is None:
-        return default
-    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
-        raise L.GavikoHipError(f"batch={batch!r}: expected a positive int")
-    return batch
-
-
 def _accumulate(eng, rows, tgt_rows, out, S, alpha, x=None, x0=None, batch=1):
     """out[b] = sum_s alpha * g(rows[b*S + s]) (* (x[b] - x0[b])): the input gradients of the logit tgt_rows[r] at every row r, in engine
     batches of `batch` rows; each output sample's rows are summed in s order by gvk_unpatchify_f32 (one FMA per step), so the result does
@@ -273,7 +254,7 @@ def _accumulate(eng, rows, tgt_rows, out, S, alpha, x=None, x0=None, batch=1):
 def input_gradient(model, img: torch.Tensor, target=None, *, times_input: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (logits [B, K], grad [B, 1, D, H, W] float32): d logit[b, target[b]] / d img[b] (times img with times_input: gradient x input).
     target: None (the argmax per sample), an int, or a [B] tensor of class indices."""
-    eng, x = _volume_check(model, img, "input_gradient")
+    eng, x = volume_check(model, img, "input_gradient")
     B = x.shape[0]
     box = {}
 
@@ -293,7 +274,7 @@ def smoothgrad(model, img: torch.Tensor, target=None, *, samples: int = 16, sigm
                batch: int = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (logits [B, K] of the clean input, grad [B, 1, D, H, W]): the mean input gradient over `samples` noisy copies x + N(0, s^2) per
     volume, s = sigma * (max - min) of that volume.  target None: the clean input's argmax.  batch: engine rows per sweep (default B)."""
-    eng, x = _volume_check(model, img, "smoothgrad")
+    eng, x = volume_check(model, img, "smoothgrad")
     B = x.shape[0]
     if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
         raise L.GavikoHipError(f"samples={samples!r}: expected a positive int")
@@ -301,7 +282,7 @@ def smoothgrad(model, img: torch.Tensor, target=None, *, samples: int = 16, sigm
         raise L.GavikoHipError(f"sigma={sigma!r}: expected >= 0")
     if isinstance(target, (int, torch.Tensor)) and not isinstance(target, bool):
         _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)
-    bs = _batch(batch, B)
+    bs = batch_rows(batch, B)
     with torch.no_grad():
         logits = eng.eval_forward(x)
         tgt = _targets(eng, logits, target, B)
@@ -321,18 +302,18 @@ def integrated_gradients(model, img: torch.Tensor, target=None, *, baseline: tor
     """-> (logits [B, K], attributions [B, 1, D, H, W], delta [B]): (x - x0) * mean_k grad(x0 + a_k (x - x0)), a_k = (k + 1/2) / steps
     (the midpoint rule), and the completeness gap delta = sum(attr) - (f(x) - f(x0)) of the explained logit (float64).  baseline: None
     (zeros) or a volume of img's shape.  batch: engine rows per sweep (default B)."""
-    eng, x = _volume_check(model, img, "integrated_gradients")
+    eng, x = volume_check(model, img, "integrated_gradients")
     B = x.shape[0]
     if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
         raise L.GavikoHipError(f"steps={steps!r}: expected a positive int")
     if baseline is None:
         x0 = torch.zeros_like(x)
     else:
-        _, x0 = _volume_check(model, baseline if baseline.dim() == 5 else baseline[None], "integrated_gradients baseline")
+        _, x0 = volume_check(model, baseline if baseline.dim() == 5 else baseline[None], "integrated_gradients baseline")
         x0 = x0.expand_as(x).contiguous()
     if isinstance(target, (int, torch.Tensor)) and not isinstance(target, bool):
         _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)
-    bs = _batch(batch, B)
+    bs = batch_rows(batch, B)
     with torch.no_grad():
         logits = eng.eval_forward(x)
         f0 = eng.eval_forward(x0)
@@ -353,7 +334,7 @@ def patch_saliency(model, volume_map: torch.Tensor, reduce: str = "abs") -> torc
     the map (reduce='sum'), in the layout of patch_grid."""
     if reduce not in ("abs", "sum"):
         raise L.GavikoHipError(f"reduce={reduce!r}: expected 'abs' or 'sum'")
-    eng, v = _volume_check(model, volume_map, "patch_saliency")
+    eng, v = volume_check(model, volume_map, "patch_saliency")
     out = torch.empty((v.shape[0],) + tuple(eng.grid), device=v.device)
     ops.patch_reduce(v, out, eng.patch, absval=reduce == "abs")
     return out
@@ -376,7 +357,7 @@ def _gaviko_forward(model, img, what):
     if eng.kind != "gaviko":
         raise L.GavikoHipError(f"{what}: the MWSA local attention and the GPA prompt attention exist in GAViKO models only (this engine "
                                f"is {eng.kind!r})")
-    eng, x = _volume_check(model, img, what)
+    eng, x = volume_check(model, img, what)
     logits, ws = _forward(eng, x)
     return eng, logits.detach(), ws
 
@@ -551,13 +532,12 @@ def _sweep(eng, x, target, bs, fill, base, jobs, *, rank=None):
     src_of_row = list(range(B)) + [b for b, _ in jobs]
     run = [(b, blank, b) for b in range(B)] + [(b, sp, B + i) for i, (b, sp) in enumerate(jobs) if not empty(sp)]   # (volume, spec, result row)
     reuse = [(B + i, b) for i, (b, sp) in enumerate(jobs) if empty(sp)]                                              # (result row, plain row)
-    run += [(run[-1][0], run[-1][1], -1)] * ((-len(run)) % bs)
+    src, spec, slot = chunk_tables(bs, dev, [r[0] for r in run], [r[1] for r in run], slot=[r[2] for r in run])
     i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)       # noqa: E731
-    src, spec, slot = i32([r[0] for r in run]), i32([r[1] for r in run]), i32([r[2] for r in run])
     src_row, row_id = i32(src_of_row), i32(list(range(n)))
     rows = torch.empty((n, K), device=dev)
     with torch.no_grad():
-        for c in range(0, len(run), bs):
+        for c in range(0, slot.numel(), bs):
             s = slice(c, c + bs)
             mask = dict(rank=rank, lo=spec[s, 0].contiguous(), hi=spec[s, 1].contiguous()) if ranked else dict(boxes=spec[s])
             eng.perturbed_forward(x, src[s], fill_scalar=fill, base=base, slot=slot[s], rows=rows, **mask)
@@ -571,9 +551,9 @@ def _sweep(eng, x, target, bs, fill, base, jobs, *, rank=None):
 
 
 def _perturb_checks(model, img, target, baseline, batch, what):
-    eng, x = _volume_check(model, img, what)
+    eng, x = volume_check(model, img, what)
     B = x.shape[0]
-    bs = _batch(batch, 8)
+    bs = batch_rows(batch, 8)
     tgt = None
     if target is not None:                                   # validated (and resolved) before any launch
         tgt = _targets(eng, torch.zeros((B, eng.K), device=x.device), target, B)

@@ -21,7 +21,8 @@ rows the layer itself still has.  GAViKO's local stream is not summarised.
 Ties.  Neighbours are ordered by the fp32 score (inner product: larger first; squared L2: smaller first); an exact tie goes to the lower
 bank index.  'cosine' normalises both sides (gvk_l2_normalize_rows) and takes inner products.  A vote tie goes to the lower class.
 
-Nothing here touches module flags, .grad, the flat gradient buffer or the state of a pending backward.
+The forwards are Engine.feature_forward (engine_analysis.py).  Nothing here touches module flags, .grad, the flat gradient buffer or the
+state of a pending backward.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from ._checks import batch_rows, volume_check
 
 METRICS = ("cosine", "ip", "l2")
 
@@ -60,18 +62,6 @@ class Prototypes(NamedTuple):
     count: torch.Tensor                     # i32 [K]
 
 
-def _volumes(model, img, what):
-    eng = model._engine()
-    if not isinstance(img, torch.Tensor) or not img.is_cuda:
-        raise L.GavikoHipError(f"{what} runs on the HIP device: move the model and the input there (there is no CPU path)")
-    want = (1,) + tuple(g * p for g, p in zip(eng.grid, eng.patch))
-    if img.dim() != 5 or tuple(img.shape[1:]) != want or img.shape[0] < 1:
-        raise L.GavikoHipError(f"{what}: expected img [B, {', '.join(map(str, want))}], got {tuple(img.shape)}")
-    if img.dtype != torch.float32:
-        raise L.GavikoHipError(f"{what}: expected a float32 volume, got {img.dtype}")
-    return eng, img.detach().contiguous()
-
-
 def _layers(eng, layers):
     if layers is None:
         return None
@@ -95,15 +85,10 @@ def embed(model, img: torch.Tensor, *, layers=None, batch: Optional[int] = None)
     the token stream entering each named layer ('all': 0 .. depth).  The volumes go through Engine.feature_forward in chunks of `batch`
     (default min(B, 8); a last partial chunk is padded with repeats that are dropped); everything stays on the device, and the result is
     bit-identical for every chunk size.  Runs on every method and both precision paths."""
-    eng, x = _volumes(model, img, "embed")
+    eng, x = volume_check(model, img, "embed")
     lay = _layers(eng, layers)
     B = x.shape[0]
-    if batch is None:
-        bs = min(B, 8)
-    elif isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
-        raise L.GavikoHipError(f"embed: batch={batch!r}: expected a positive int")
-    else:
-        bs = batch
+    bs = batch_rows(batch, min(B, 8), "embed: ")
     dev, C, n = x.device, eng.C, 0 if lay is None else len(lay)
     pooled = torch.empty((B, C), device=dev)
     logits = torch.empty((B, eng.K), device=dev)

@@ -10,9 +10,9 @@ entropy) and the part they do not (the mutual information), the per-class spread
     r.probs, r.pred, r.entropy, r.mutual_info, r.std, r.votes          # device tensors; r.member_logits [B, S, K] keeps every member
 
 Every member is built on the device straight in the engine's static input slot (csrc/uncertainty.hip: gvk_tta_volumes mirrors or
-replicates the source volume, one HBM pass), the chunk's forward is the engine's recorded inference plan, the logits rows are gathered on
-the device and one launch (gvk_predictive_stats) reduces them at the end: nothing between the first and the last forward waits for the
-host.  Module flags, .grad, the flat gradient buffer and the state of a pending backward are left alone.
+replicates the source volume, one HBM pass), the chunk's forward is the engine's recorded inference plan (Engine.member_forward,
+engine_analysis.py), the logits rows are gathered on the device and one launch (gvk_predictive_stats) reduces them at the end: nothing
+between the first and the last forward waits for the host.  Module flags, .grad, the flat gradient buffer and the state of a pending backward are left alone.
 
 Member order and chunking are part of the contract.  Row o = b * S + s of the sweep is member s of volume b (sample-major); the rows are
 cut into chunks of `batch` rows (default: the largest multiple of S that is <= 8, else S; a last partial chunk is padded with repeats
@@ -28,6 +28,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from ._checks import batch_rows, chunk_tables, volume_check
 
 _ALL_FLIPS = [(), (0,), (1,), (0, 1), (2,), (0, 2), (1, 2), (0, 1, 2)]        # flip code = sum of 1 << axis: the codes 0 .. 7 in order
 
@@ -45,24 +46,8 @@ class Predictive(NamedTuple):
     epochs: List[int]               # the dropout seed word each chunk's forward drew from ([] for tta)
 
 
-def _volume_check(model, img, what):
-    eng = model._engine()
-    if not isinstance(img, torch.Tensor) or not img.is_cuda:
-        raise L.GavikoHipError(f"{what} runs on the HIP device: move the model and the input there (there is no CPU path)")
-    want = (1,) + tuple(g * p for g, p in zip(eng.grid, eng.patch))
-    if img.dim() != 5 or tuple(img.shape[1:]) != want or img.shape[0] < 1:
-        raise L.GavikoHipError(f"{what}: expected img [B, {', '.join(map(str, want))}], got {tuple(img.shape)}")
-    if img.dtype != torch.float32:
-        raise L.GavikoHipError(f"{what}: expected a float32 volume, got {img.dtype}")
-    return eng, img.detach().contiguous()
-
-
 def _chunk_rows(batch, S, what):
-    if batch is None:
-        return (8 // S) * S if S <= 8 else S
-    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
-        raise L.GavikoHipError(f"{what}: batch={batch!r}: expected a positive int")
-    return batch
+    return batch_rows(batch, (8 // S) * S if S <= 8 else S, f"{what}: ")
 
 
 def training_drop_config(model) -> dict:
@@ -81,15 +66,9 @@ def _sweep(eng, x, S, codes, bs, drop, seed):
     """B * S members in chunks of bs rows -> (member_logits [B, S, K], epochs).  codes[s]: the flip code of member s."""
     B, K, dev = x.shape[0], eng.K, x.device
     n = B * S
-    src = [o // S for o in range(n)]
-    flip = [codes[o % S] for o in range(n)]
-    slot = list(range(n))
-    pad = (-n) % bs
-    src, flip, slot = src + [src[-1]] * pad, flip + [flip[-1]] * pad, slot + [-1] * pad
-    i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)       # noqa: E731
-    src, flip, slot = i32(src), i32(flip), i32(slot)
+    src, flip, slot = chunk_tables(bs, dev, [o // S for o in range(n)], [codes[o % S] for o in range(n)], slot=list(range(n)))
     rows = torch.empty((n, K), device=dev)
-    nchunks = (n + pad) // bs
+    nchunks = slot.numel() // bs
     words = None
     with torch.no_grad():
         if drop is not None:
@@ -117,7 +96,7 @@ def mc_dropout(model, img: torch.Tensor, *, samples: int = 32, batch: Optional[i
     members would be identical.  seed: an int fixes the workspace's seed word at the start of the sweep, and the same (seed, samples,
     batch) then gives bit-identical member_logits; None continues from wherever the word stands, so two calls differ.  epochs[c] is the
     word chunk c's masks were drawn from (seed + 7919 (c + 1) with a seed).  Runs on every method and both precision paths."""
-    eng, x = _volume_check(model, img, "mc_dropout")
+    eng, x = volume_check(model, img, "mc_dropout")
     if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
         raise L.GavikoHipError(f"mc_dropout: samples={samples!r}: expected a positive int")
     bs = _chunk_rows(batch, samples, "mc_dropout")
@@ -163,7 +142,7 @@ def tta(model, img: torch.Tensor, *, flips="all", batch: Optional[int] = None) -
     """Flip test-time augmentation: one deterministic inference forward per flip of every volume.  flips: 'all' (the 8 subsets of the three
     axes, in the order of their codes sum(1 << axis)), 'train' ([(), (0,)]: the RandomFlip(axis 0) the training pipeline draws) or a list
     of axis tuples over (0, 1, 2) = (D, H, W).  member_logits[b, s] belongs to flips[s].  Runs on every method and both precision paths."""
-    eng, x = _volume_check(model, img, "tta")
+    eng, x = volume_check(model, img, "tta")
     codes = _flip_codes(flips)
     bs = _chunk_rows(batch, len(codes), "tta")
     logits, _ = _sweep(eng, x, len(codes), codes, bs, None, None)

@@ -238,6 +238,47 @@ def test_explain_between_forward_and_backward_leaves_the_step_unchanged(dev):
             assert torch.equal(a[n], b[n]), n
 
 
+def test_relevance_backward_whose_seed_raises_leaves_the_step_unchanged(dev):
+    """The exception path of the engine's state guard: relevance_backward between a training forward and its backward, with a seed
+    callable that raises on the host.  The error comes through, _relv is cleared, the pending backward's gradients are bit-identical to the
+    same step without the call, and a later relevance_backward equals a fresh engine's bit for bit."""
+    x, y = volumes(1)
+    x, y = x.to(dev), y.to(dev)
+    m, _ = build("gaviko", dict(GAVIKO), dev)
+    eng = m._engine()
+
+    def failing_seed(logits):
+        raise ValueError("no seed today")
+
+    def step(interrupted):
+        for p in m.parameters():
+            p.grad = None
+        out = m(x)
+        if interrupted:
+            with pytest.raises(ValueError, match="no seed today"):
+                eng.relevance_backward(x, failing_seed)
+            assert eng._relv is None
+        torch.nn.functional.cross_entropy(out, y).backward()
+        torch.cuda.synchronize()
+        return out.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+
+    for _ in range(3):                                   # eager, record, replay of the training plans
+        a_out, a = step(False)
+        b_out, b = step(True)
+        assert a and torch.equal(a_out, b_out)
+        for n in a:
+            assert torch.equal(a[n], b[n]), n
+
+    seed = lambda logits: torch.nn.functional.one_hot(torch.tensor([2], device=dev), eng.K).to(logits.dtype)      # noqa: E731
+    logits, _, rv = eng.relevance_backward(x, seed)
+    fresh, _ = build("gaviko", dict(GAVIKO), dev)
+    want_logits, _, want = fresh._engine().relevance_backward(x, seed)
+    torch.cuda.synchronize()
+    assert eng._relv is None
+    assert torch.equal(logits, want_logits) and torch.equal(rv["r"], want["r"])
+    assert float((rv["r"] - rv["w0"]).max()) > 0.0       # the relevance kernels did run
+
+
 @pytest.mark.parametrize("precision", ["bf16", "fp32"])
 def test_explain_replay_smoothgrad_and_batch_split(dev, precision):
     """Eager, recorded and replayed input-only sweeps give the same bits; smoothgrad(samples=1, sigma=0) is input_gradient; IG over steps
