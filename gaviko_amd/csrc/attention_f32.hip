@@ -254,47 +254,37 @@ __global__ __launch_bounds__(2 * kRows) void attn_f32_bwd_kv_kernel(const float*
 extern "C" int gvk_attention_fwd_f32_dropout(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
                                              float drop_p, uint64_t seed, const void* seed_ptr, void* stream) {
   using namespace gvk;
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_fwd_f32: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_fwd_f32: the dropout mask index (query*T + key) is 32-bit");
+  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_fwd_f32_dropout: drop_p in [0,1) and a seed word");
+  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_fwd_f32_dropout: the dropout mask index (query*T + key) is 32-bit");
   const AttnDropF dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  GVK_REQUIRE(qkv && out, "gvk_attention_fwd_f32: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_fwd_f32: empty shape");
+  GVK_REQUIRE(qkv && out, "gvk_attention_fwd_f32_dropout: null pointer");
+  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_fwd_f32_dropout: empty shape");
   GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 4 == 0 && ld_out >= H * 64 && ld_out % 4 == 0,
-              "gvk_attention_fwd_f32: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
+              "gvk_attention_fwd_f32_dropout: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
   const dim3 grid((T + kRows - 1) / kRows, H, B), block(2 * kRows);
   if (drop_p > 0.f) GVK_LAUNCH((attn_f32_fwd_kernel<true>), grid, block, 0, (hipStream_t)stream, qkv, out, lse, T, H, ld_qkv, ld_out, scale, dr);
   else GVK_LAUNCH((attn_f32_fwd_kernel<false>), grid, block, 0, (hipStream_t)stream, qkv, out, lse, T, H, ld_qkv, ld_out, scale, dr);
-  return check_launch("attention_fwd_f32");
-}
-
-extern "C" int gvk_attention_fwd_f32(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                     void* stream) {
-  return gvk_attention_fwd_f32_dropout(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, 0.f, 0, nullptr, stream);
+  return check_launch("attention_fwd_f32_dropout");
 }
 
 extern "C" int gvk_attention_bwd_f32_dropout(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                                              int B, int T, int H, int ld_qkv, int ld_out, float scale, float drop_p, uint64_t seed,
                                              const void* seed_ptr, void* stream) {
   using namespace gvk;
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_bwd_f32: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_bwd_f32: the dropout mask index (query*T + key) is 32-bit");
+  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_bwd_f32_dropout: drop_p in [0,1) and a seed word");
+  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_bwd_f32_dropout: the dropout mask index (query*T + key) is 32-bit");
   const AttnDropF dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv, "gvk_attention_bwd_f32: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_bwd_f32: empty shape");
+  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv, "gvk_attention_bwd_f32_dropout: null pointer");
+  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_bwd_f32_dropout: empty shape");
   GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 4 == 0 && ld_out >= H * 64 && ld_out % 4 == 0,
-              "gvk_attention_bwd_f32: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
+              "gvk_attention_bwd_f32_dropout: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
   const dim3 grid((T + kRows - 1) / kRows, H, B), block(2 * kRows);
   hipStream_t s = (hipStream_t)stream;
   if (drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_dq_kernel<true>), grid, block, 0, s, qkv, out, dout, lse, delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
   else GVK_LAUNCH((attn_f32_bwd_dq_kernel<false>), grid, block, 0, s, qkv, out, dout, lse, delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
-  int rc = check_launch("attention_bwd_f32/dq");
+  int rc = check_launch("attention_bwd_f32_dropout/dq");
   if (rc) return rc;
   if (drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_kv_kernel<true>), grid, block, 0, s, qkv, dout, lse, (const float*)delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
   else GVK_LAUNCH((attn_f32_bwd_kv_kernel<false>), grid, block, 0, s, qkv, dout, lse, (const float*)delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
-  return check_launch("attention_bwd_f32/dkdv");
-}
-
-extern "C" int gvk_attention_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
-                                     int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream) {
-  return gvk_attention_bwd_f32_dropout(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, 0.f, 0, nullptr, stream);
+  return check_launch("attention_bwd_f32_dropout/dkdv");
 }

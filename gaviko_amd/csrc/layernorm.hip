@@ -255,30 +255,6 @@ extern "C" int gvk_layernorm_fwd_fix(float* x, const float* gamma, const float* 
   return check_launch("layernorm_fwd_fix");
 }
 
-extern "C" int gvk_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                                 const float* dres, float* dx, void* dx_bf16, int M, int C, void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(dy && x && mean && rstd && gamma && dx, "gvk_layernorm_bwd: null pointer");
-  GVK_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && C <= 256 * kMaxChunks, "gvk_layernorm_bwd: C=%d must be a multiple of 4 and <= 1024", C);
-  GVK_LAUNCH(ln_bwd_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const void*)dy, x, mean, rstd, gamma, dres, dx,
-                     (bf16*)dx_bf16, M, C, 0, 0);
-  return check_launch("layernorm_bwd");
-}
-
-extern "C" int gvk_layernorm_bwd_rows(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                                      const float* dres, float* dx, void* dx_bf16, int groups, int rows_per_group, int group_stride, int C,
-                                      void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(dy && x && mean && rstd && gamma && dx, "gvk_layernorm_bwd_rows: null pointer");
-  GVK_REQUIRE(groups > 0 && rows_per_group > 0 && group_stride >= rows_per_group, "gvk_layernorm_bwd_rows: groups=%d rows_per_group=%d group_stride=%d",
-              groups, rows_per_group, group_stride);
-  GVK_REQUIRE(C > 0 && C % 4 == 0 && C <= 256 * kMaxChunks, "gvk_layernorm_bwd_rows: C=%d must be a multiple of 4 and <= 1024", C);
-  const int M = groups * rows_per_group;
-  GVK_LAUNCH(ln_bwd_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const void*)dy, x, mean, rstd, gamma, dres, dx,
-                     (bf16*)dx_bf16, M, C, rows_per_group, group_stride);
-  return check_launch("layernorm_bwd_rows");
-}
-
 // ---- LayerNorm with a fused rank-L projection of the rows it holds: the row-per-wave projection kernel of rowwise.hip run
 // with a LayerNorm prologue (mode 1: forward, projects the raw rows; mode 2: backward, projects dx).
 namespace gvk {
@@ -312,42 +288,35 @@ extern "C" int gvk_layernorm_fwd_proj(const float* x, const float* gamma, const 
   return launch_proj(a, proj, (hipStream_t)stream, "gvk_layernorm_fwd_proj");
 }
 
-extern "C" int gvk_layernorm_bwd_proj(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                                      const float* dres, float* dx, void* dx_bf16, int M, int C, const gvk_rowproj_desc* proj,
-                                      void* stream) {
+// dx = dres + LN'(dy) (+ bf16 copy), dy in fp32 or in bf16 (what the dgrad GEMM in front stores: half the bytes on both sides); optionally
+// for the leading rows of every group only, or with the rank-L projection of dx (DownArgs mode 2)
+extern "C" int gvk_layernorm_bwd(const gvk_ln_bwd_desc* d, void* stream) {
   using namespace gvk;
-  GVK_REQUIRE(dy && x && mean && rstd && gamma && dx, "gvk_layernorm_bwd_proj: null pointer");
-  GVK_REQUIRE(M > 0 && C > 0, "gvk_layernorm_bwd_proj: empty shape");
-  if (int rc = check_proj(proj, C, "gvk_layernorm_bwd_proj")) return rc;
-  DownArgs a{};
-  a.mode = 2; a.x = x; a.dy = dy; a.mean_in = mean; a.rstd_in = rstd; a.ln_g = gamma; a.dres = dres; a.dx = dx; a.dx16 = (bf16*)dx_bf16;
-  a.M = M; a.C = C; a.eps = 1e-5f; a.inv_keep = 1.f;
-  return launch_proj(a, proj, (hipStream_t)stream, "gvk_layernorm_bwd_proj");
-}
-
-// The three backward forms above with the output gradient in bf16 (what the dgrad GEMM in front stores: half the bytes on both sides)
-extern "C" int gvk_layernorm_bwd_dy16(const gvk_ln_bwd_dy16_desc* d, void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(d && d->dy_bf16 && d->x && d->mean && d->rstd && d->gamma && d->dx, "gvk_layernorm_bwd_dy16: null pointer");
+  GVK_REQUIRE(d && d->dy && d->x && d->mean && d->rstd && d->gamma && d->dx, "gvk_layernorm_bwd: null pointer");
   const int C = d->C;
-  GVK_REQUIRE(d->M > 0 && C > 0 && C % 4 == 0 && C <= 256 * kMaxChunks, "gvk_layernorm_bwd_dy16: C=%d must be a multiple of 4 and <= 1024", C);
+  GVK_REQUIRE(d->M > 0 && C > 0 && C % 4 == 0 && C <= 256 * kMaxChunks, "gvk_layernorm_bwd: C=%d must be a multiple of 4 and <= 1024", C);
+  GVK_REQUIRE(d->dy_bf16 == 0 || d->dy_bf16 == 1, "gvk_layernorm_bwd: dy_bf16 must be 0 (fp32 dy) or 1 (bf16 dy)");
   if (d->proj != nullptr) {
-    GVK_REQUIRE(d->rows_per_group == 0, "gvk_layernorm_bwd_dy16: the projection form covers all rows");
-    if (int rc = check_proj(d->proj, C, "gvk_layernorm_bwd_dy16")) return rc;
+    GVK_REQUIRE(d->rows_per_group == 0, "gvk_layernorm_bwd: the projection form covers all rows");
+    if (int rc = check_proj(d->proj, C, "gvk_layernorm_bwd")) return rc;
     DownArgs a{};
-    a.mode = 2; a.x = d->x; a.dy16 = (const bf16*)d->dy_bf16; a.mean_in = d->mean; a.rstd_in = d->rstd; a.ln_g = d->gamma; a.dres = d->dres; a.dx = d->dx;
+    a.mode = 2; a.x = d->x; a.mean_in = d->mean; a.rstd_in = d->rstd; a.ln_g = d->gamma; a.dres = d->dres; a.dx = d->dx;
+    if (d->dy_bf16) a.dy16 = (const bf16*)d->dy; else a.dy = (const float*)d->dy;
     a.dx16 = (bf16*)d->dx_bf16; a.M = d->M; a.C = C; a.eps = 1e-5f; a.inv_keep = 1.f;
-    return launch_proj(a, d->proj, (hipStream_t)stream, "gvk_layernorm_bwd_dy16");
+    return launch_proj(a, d->proj, (hipStream_t)stream, "gvk_layernorm_bwd");
   }
   int M = d->M, rpg = 0, gs = 0;
   if (d->rows_per_group > 0) {
     GVK_REQUIRE(d->groups > 0 && d->group_stride >= d->rows_per_group && (long)(d->groups - 1) * d->group_stride + d->rows_per_group <= d->M,
-                "gvk_layernorm_bwd_dy16: groups=%d rows_per_group=%d group_stride=%d do not fit M=%d", d->groups, d->rows_per_group, d->group_stride, d->M);
+                "gvk_layernorm_bwd: groups=%d rows_per_group=%d group_stride=%d do not fit M=%d", d->groups, d->rows_per_group, d->group_stride, d->M);
     M = d->groups * d->rows_per_group; rpg = d->rows_per_group; gs = d->group_stride;
   }
-  GVK_LAUNCH(ln_bwd_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, d->dy_bf16, d->x, d->mean, d->rstd, d->gamma, d->dres, d->dx,
-             (bf16*)d->dx_bf16, M, C, rpg, gs);
-  return check_launch("layernorm_bwd_dy16");
+  const dim3 grid((M + 3) / 4), block(256);
+  if (d->dy_bf16) GVK_LAUNCH(ln_bwd_kernel<true>, grid, block, 0, (hipStream_t)stream, d->dy, d->x, d->mean, d->rstd, d->gamma, d->dres, d->dx,
+                             (bf16*)d->dx_bf16, M, C, rpg, gs);
+  else GVK_LAUNCH(ln_bwd_kernel<false>, grid, block, 0, (hipStream_t)stream, d->dy, d->x, d->mean, d->rstd, d->gamma, d->dres, d->dx,
+                  (bf16*)d->dx_bf16, M, C, rpg, gs);
+  return check_launch("layernorm_bwd");
 }
 
 // LayerNorm backward of the MLP block fused with GPA's rank-L scatter (gaviko.py:155: dG1 += dzx . W_d): one pass over the row

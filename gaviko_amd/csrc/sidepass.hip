@@ -60,7 +60,7 @@ __device__ __forceinline__ f32x4 load_w_down(const float* __restrict__ w, int C,
 // NGW = 32-column groups per wave (C = 256 NGW, or fewer: waves past the end work on zeros), WL = weight layout.
 // MODE 0: y = act(f(x) . W^T + b), f = identity | LayerNorm(ln_g, ln_b) | dropout mask                                  (gvk_skinny_down)
 // MODE 1: y16 = bf16 LayerNorm(x) with mean / rstd saved, and the projection of the RAW row                            (gvk_layernorm_fwd_proj)
-// MODE 2: dx = dres + LayerNorm'(dy; x, mean_in, rstd_in, ln_g) (+ bf16 copy dx16), and the projection of dx             (gvk_layernorm_bwd_proj)
+// MODE 2: dx = dres + LayerNorm'(dy; x, mean_in, rstd_in, ln_g) (+ bf16 copy dx16), and the projection of dx             (gvk_layernorm_bwd with proj)
 template <int NGW, int WL, int MODE>
 __global__ __launch_bounds__(64 * kSW, NGW <= 3 ? 4 : 2) void side_down_kernel(DownArgs p) {     // <= 128 VGPRs: two workgroups per CU (259 tiles on 256 CUs)
   __shared__ float red[kSW][16];

@@ -128,7 +128,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         self._recording = False
         self._keep_inputs = False               # unfrozen backbone weights: the forward keeps the GEMM inputs for their wgrads
         self._eff: Dict[str, torch.Tensor] = {}
-        # GPA projections of backbone rows ride along in the backbone's LayerNorm kernels (gvk_layernorm_*_proj)
+        # GPA projections of backbone rows ride along in the backbone's LayerNorm kernels (gvk_layernorm_fwd_proj, gvk_ln_bwd_desc.proj)
         self._fuse_proj = (kind == "gaviko" and not self.fp32 and ops.rowproj_supported(self.Lat, dim)
                            and L.diag_env("GAVIKO_HIP_FUSE_PROJ", "1") != "0")
         # In the backward, the LayerNorm-1 backward of layer i > 0 also leaves dcomb = dG . W_up for the GPA core of layer i - 1 (computing it
@@ -1197,9 +1197,9 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
             self._ssf_ln_grad(ws, gv, m, ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
         if top:                                                              # the other rows of dG1 are dGout: zero, in one memset
             ops.memset_zero(dGin)
-        self._ln_bwd(ws, dy16, ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, dx=dGin, dres=dGout,
-                     dx16=None if self.kind in ("gaviko", "adaptformer", "dvpt") else ws["dG16"],
-                     rows=(B, sum(self._pool_rows()), T) if top else None)
+        ops.layernorm_bwd(ws["dx16b"] if dy16 else ws["dx32"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout,
+                          dx16=None if self.kind in ("gaviko", "adaptformer", "dvpt") else ws["dG16"],
+                          rows=(B, sum(self._pool_rows()), T) if top else None)
         if dvpt:
             self._dvpt_bwd_scatter(ws, i, dGin, M)                           # dG1 += (dz . Wd) * QuickGELU'(G1)  (+ operand copy)
         if self.kind == "adaptformer":
@@ -1246,21 +1246,8 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         if self._fuse_proj and i > 0:                                        # + dcomb = dx . W_up for the GPA core of layer i - 1
             pre_lo, _ = self._gpa_names(i - 1)
             proj = dict(w=d(pre_lo + ".proj_up.weight"), y=ws["bw"]["dcomb"], w_layout=1, L_=self.Lat)
-        self._ln_bwd(ws, dy16, ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, dx=dx, dres=dGin, dx16=None if bot else ws["dG16"],
-                     rows=(B, self.P, T) if bot else None, proj=proj)
-
-    def _ln_bwd(self, ws, dy16, x, mean, rstd, gamma, M, *, dx, dres, dx16=None, rows=None, proj=None):
-        """dx = dres + LN'(dy) (+ its GEMM-operand copy dx16) for the dy the dgrad GEMM left: ws['dx16b'] when dy16, else ws['dx32'].
-        rows = (groups, rows per group, group stride): the leading rows of every sample only.  proj = dict(w=, y=, L_=, w_layout=): the
-        rank-L projection of dx rides along."""
-        if dy16:
-            ops.layernorm_bwd_dy16(ws["dx16b"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16, rows=rows, proj=proj)
-        elif rows is not None:
-            ops.layernorm_bwd_rows(ws["dx32"], x, mean, rstd, gamma, *rows, self.C, dx=dx, dres=dres, dx16=dx16)
-        elif proj is not None:
-            ops.layernorm_bwd_proj(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16, **proj)
-        else:
-            ops.layernorm_bwd(ws["dx32"], x, mean, rstd, gamma, M, self.C, dx=dx, dres=dres, dx16=dx16)
+        ops.layernorm_bwd(ws["dx16b"] if dy16 else ws["dx32"], ws["G"][i], st[0], st[1], d(a + ".norm.weight"), M, C, dx=dx, dres=dGin,
+                          dx16=None if bot else ws["dG16"], rows=(B, self.P, T) if bot else None, proj=proj)
 
     def _grad_supported(self, name: str) -> bool:
         # head: always; backbone tensors: the classes of _BB_KINDS (plain ViT `linear` / `bitfit` / `fft`, AdaptFormer and Gaviko with

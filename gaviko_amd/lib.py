@@ -26,7 +26,7 @@ if os.environ.get("GPU_MAX_HW_QUEUES") is None:
     except Exception:
         pass
 
-ABI_VERSION = 12                                  # gvk_abi_version() of the library these declarations describe
+ABI_VERSION = 13                                  # gvk_abi_version() of the library these declarations describe
 # GAVIKO_HIP_DIAG=1 (tools/ only): load the measurement build libgaviko_hip_diag.so (`python -m gaviko_amd.build --diag`) -- the product
 # library ignores every A/B switch of the kernel sources and exports no diagnostics (include/gaviko_hip_diag.h)
 DIAG = os.environ.get("GAVIKO_HIP_DIAG", "0") == "1"
@@ -87,8 +87,8 @@ AdamDesc = _struct("AdamDesc", ["ptr_tab", "blk_tab", "grad", "m", "v", "norm_sq
 LossDesc = _struct("LossDesc", ["logits", "target", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"], ["gamma", "eps"], i64=["ignore_index"])
 DropoutDesc = _struct("DropoutDesc", ["x", "out32", "out16", "seed_ptr"], ["M", "N", "ld", "rows_in", "rows_out", "row_off"], ["drop_p"], ["seed"])
 RowProjDesc = _struct("RowProjDesc", ["w", "bias", "y", "z", "y_split"], ["L", "w_layout", "act", "ld_split", "col_split"])
-LnBwdDy16Desc = _struct("LnBwdDy16Desc", ["dy_bf16", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
-                        ["M", "C", "groups", "rows_per_group", "group_stride"])
+LnBwdDesc = _struct("LnBwdDesc", ["dy", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
+                    ["M", "C", "groups", "rows_per_group", "group_stride", "dy_bf16"])
 ReduceJob = _struct("ReduceJob", ["a", "b", "out", "a2"], ["M", "J", "L", "accumulate", "M2"])
 PgradOuter = _struct("PgradOuter", ["narrow", "wide", "narrow2", "wide2", "lat_override", "mean", "rstd", "out", "colsum",
                                     "aff_w", "aff_gamma", "aff_beta", "aff_dgamma", "aff_dbeta", "aff_dbias"],
@@ -108,8 +108,6 @@ _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 SIGNATURES = {
     "gvk_gemm_nt_bf16": [C.POINTER(GemmDesc), _P],
     "gvk_gemm_nt_f32": [C.POINTER(GemmDesc), _P],
-    "gvk_attention_fwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "gvk_attention_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "gvk_patchify_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_transpose_f32": [_P, _P, _I, _I, _P],
     "gvk_transpose_bf16": [_P, _P, _I, _I, _P],
@@ -122,8 +120,7 @@ SIGNATURES = {
     "gvk_layernorm_fwd_fix": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _I, _I, _I, _P],
     "gvk_patchify_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "gvk_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "gvk_layernorm_bwd_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "gvk_layernorm_bwd": [C.POINTER(LnBwdDesc), _P],
     "gvk_layernorm_bwd_affine": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gvk_attention_fwd_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "gvk_qkv_prescale_bf16": [_P, _I, _I, _I, _F, _P],
@@ -166,8 +163,6 @@ SIGNATURES = {
     "gvk_cast_bf16_f32_strided": [_P, _P, _I, _I, _I, _P],
     "gvk_lora_merge_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "gvk_layernorm_fwd_proj": [_P, _P, _P, _P, _P, _P, _I, _I, _F, C.POINTER(RowProjDesc), _P],
-    "gvk_layernorm_bwd_dy16": [C.POINTER(LnBwdDy16Desc), _P],
-    "gvk_layernorm_bwd_proj": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(RowProjDesc), _P],
     "gvk_layernorm_bwd_up": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_ssf_fold_weight": [_P, _P, _P, _P, _I, _I, _I, _P],
     "gvk_ssf_fold_vec": [_P, _P, _P, _P, _I, _P],

@@ -452,20 +452,6 @@ def layernorm_fwd_proj(x, gamma, beta, M, C_, *, y16, mean=None, rstd=None, eps=
                                             C.byref(d), L.stream_ptr()), "gvk_layernorm_fwd_proj")
 
 
-def layernorm_bwd_proj(dy, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None, w, y, L_=ROWPROJ_L, w_layout=1):
-    """LayerNorm backward + rank-L projection of the output rows dx (one pass)."""
-    for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")):
-        _chk(t, torch.float32, "ln_bwd " + n, M * C_)
-    _chk(dres, torch.float32, "ln_bwd dres", M * C_)
-    _chk(dx16, torch.bfloat16, "ln_bwd dx16", M * C_)
-    _chk(mean, torch.float32, "ln_bwd mean", M)
-    _chk(rstd, torch.float32, "ln_bwd rstd", M)
-    _chk(gamma, torch.float32, "ln_bwd gamma", C_)
-    d = _rowproj(M, C_, w, y, None, None, L_, w_layout, 0)
-    L.check(L.load().gvk_layernorm_bwd_proj(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx),
-                                            L.ptr(dx16), M, C_, C.byref(d), L.stream_ptr()), "gvk_layernorm_bwd_proj")
-
-
 def layernorm_bwd_up(dy, x, mean, rstd, gamma, M, C_, *, dx, dres, dx16, lat, w, L_, w_layout):
     """dx = dres + LN'(dy) + lat . W^T (+ bf16 copy): the MLP block's LayerNorm backward and GPA's dG1 += dzx . W_d in one pass."""
     for t, n in ((dy, "dy"), (x, "x"), (dx, "dx"), (dres, "dres")):
@@ -480,55 +466,32 @@ def layernorm_bwd_up(dy, x, mean, rstd, gamma, M, C_, *, dx, dres, dx16, lat, w,
                                           L.ptr(lat), L.ptr(w), w_layout, M, C_, L_, L.stream_ptr()), "gvk_layernorm_bwd_up")
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None):
-    if dx16 is not None and dx16.dtype == torch.float32:     # fp32 compute path: the operand copy is a plain copy of dx
-        layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, dx=dx, dres=dres)
+def layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None, rows=None, proj=None):
+    """dx = dres + LN'(dy) (+ bf16 copy dx16); dy in fp32 or bf16 (its dtype selects the kernel).  rows = (groups, rows_per_group, group_stride)
+    restricts it to the first rows_per_group rows of every group of group_stride rows (every sample's leading tokens); the other rows of
+    dx / dx16 are left as they are.  proj = dict(w=, y=, L_=, w_layout=) adds the rank-L projection y = dx . W of the output rows."""
+    if rows is not None and proj is not None:
+        raise L.GavikoHipError("ln_bwd: the projection form covers all rows (rows and proj are exclusive)")
+    if dx16 is not None and dx16.dtype == torch.float32 and rows is None:     # fp32 compute path: the operand copy is a plain copy of dx
+        layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, dx=dx, dres=dres, proj=proj)
         copy_(dx16, dx)
         return
-    for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")):
+    dy_bf16 = dy.dtype == torch.bfloat16
+    _chk(dy, torch.bfloat16 if dy_bf16 else torch.float32, "ln_bwd dy", M * C_)
+    for t, n in ((x, "x"), (dx, "dx")):
         _chk(t, torch.float32, "ln_bwd " + n, M * C_)
     _chk(dres, torch.float32, "ln_bwd dres", M * C_)
     _chk(dx16, torch.bfloat16, "ln_bwd dx16", M * C_)
     _chk(mean, torch.float32, "ln_bwd mean", M)
     _chk(rstd, torch.float32, "ln_bwd rstd", M)
     _chk(gamma, torch.float32, "ln_bwd gamma", C_)
-    L.check(L.load().gvk_layernorm_bwd(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx),
-                                       L.ptr(dx16), M, C_, L.stream_ptr()), "gvk_layernorm_bwd")
-
-
-def layernorm_bwd_dy16(dy16, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None, rows=None, proj=None):
-    """LayerNorm backward with the output gradient in bf16 (gvk_layernorm_bwd_dy16).  rows = (groups, rows_per_group, group_stride) restricts it
-    to the leading rows of every group; proj = dict(w=, y=, L_=, w_layout=) adds the rank-L projection of dx (as layernorm_bwd_proj)."""
-    _chk(dy16, torch.bfloat16, "ln_bwd_dy16 dy", M * C_)
-    for t, n in ((x, "x"), (dx, "dx")):
-        _chk(t, torch.float32, "ln_bwd_dy16 " + n, M * C_)
-    _chk(dres, torch.float32, "ln_bwd_dy16 dres", M * C_)
-    _chk(dx16, torch.bfloat16, "ln_bwd_dy16 dx16", M * C_)
-    _chk(mean, torch.float32, "ln_bwd_dy16 mean", M)
-    _chk(rstd, torch.float32, "ln_bwd_dy16 rstd", M)
-    _chk(gamma, torch.float32, "ln_bwd_dy16 gamma", C_)
     g, rpg, gs = rows if rows is not None else (0, 0, 0)
     pj = None
     if proj is not None:
         pj = _rowproj(M, C_, proj["w"], proj["y"], None, None, proj.get("L_", ROWPROJ_L), proj.get("w_layout", 1), 0)
-    d = L.LnBwdDy16Desc(L.ptr(dy16), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx), L.ptr(dx16),
-                        C.cast(C.pointer(pj), C.c_void_p) if pj is not None else None, M, C_, int(g), int(rpg), int(gs))
-    L.check(L.load().gvk_layernorm_bwd_dy16(C.byref(d), L.stream_ptr()), "gvk_layernorm_bwd_dy16")
-
-
-def layernorm_bwd_rows(dy, x, mean, rstd, gamma, groups, rows_per_group, group_stride, C_, *, dx, dres=None, dx16=None):
-    """layernorm_bwd for the first `rows_per_group` rows of every group of `group_stride` rows (every sample's leading tokens); the other
-    rows of dx / dx16 are left as they are."""
-    M = (groups - 1) * group_stride + rows_per_group
-    for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")):
-        _chk(t, torch.float32, "ln_bwd_rows " + n, M * C_)
-    _chk(dres, torch.float32, "ln_bwd_rows dres", M * C_)
-    _chk(dx16, torch.bfloat16, "ln_bwd_rows dx16", M * C_)
-    _chk(mean, torch.float32, "ln_bwd_rows mean", M)
-    _chk(rstd, torch.float32, "ln_bwd_rows rstd", M)
-    _chk(gamma, torch.float32, "ln_bwd_rows gamma", C_)
-    L.check(L.load().gvk_layernorm_bwd_rows(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx), L.ptr(dx16),
-                                            groups, rows_per_group, group_stride, C_, L.stream_ptr()), "gvk_layernorm_bwd_rows")
+    d = L.LnBwdDesc(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx), L.ptr(dx16),
+                    C.cast(C.pointer(pj), C.c_void_p) if pj is not None else None, M, C_, int(g), int(rpg), int(gs), int(dy_bf16))
+    L.check(L.load().gvk_layernorm_bwd(C.byref(d), L.stream_ptr()), "gvk_layernorm_bwd")
 
 
 def layernorm_bwd_affine(dy, x, mean, rstd, dgamma, dbeta, scratch, M, C_, accumulate=False):
@@ -567,7 +530,7 @@ def attention_fwd(qkv, out, lse, B, T, H, scale, drop_p=0.0, seed=0, seed_ptr=No
         _chk(out, torch.float32, "attn out", B * T * inner)
         _chk(lse, torch.float32, "attn lse", B * H * T)
         L.check(L.load().gvk_attention_fwd_f32_dropout(L.ptr(qkv), L.ptr(out), L.ptr(lse), B, T, H, 3 * inner, inner, scale, float(drop_p), int(seed),
-                                                       L.ptr(seed_ptr) if drop_p > 0 else None, L.stream_ptr()), "gvk_attention_fwd_f32")
+                                                       L.ptr(seed_ptr) if drop_p > 0 else None, L.stream_ptr()), "gvk_attention_fwd_f32_dropout")
         return
     _chk(qkv, torch.bfloat16, "attn qkv", pad_rows(B * T) * 3 * inner)
     _chk(out, torch.bfloat16, "attn out", B * T * inner)
@@ -875,7 +838,7 @@ def attention_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, scale, drop_p=0.0, 
         _chk(delta, torch.float32, "attn_bwd delta", B * H * T)
         L.check(L.load().gvk_attention_bwd_f32_dropout(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, H,
                                                        3 * inner, inner, scale, float(drop_p), int(seed), L.ptr(seed_ptr) if drop_p > 0 else None,
-                                                       L.stream_ptr()), "gvk_attention_bwd_f32")
+                                                       L.stream_ptr()), "gvk_attention_bwd_f32_dropout")
         return
     _chk(qkv, torch.bfloat16, "attn_bwd qkv", pad_rows(B * T) * 3 * inner)
     _chk(out, torch.bfloat16, "attn_bwd out", pad_rows(B * T) * inner)

@@ -139,11 +139,8 @@ int gvk_gemm_stat_parts(int N);
  * gvk_gemm_nt_f32: v_mfma_f32_16x16x4_f32 (exact fp32 products), N % 64 == 0, K % 16 == 0.
  * gvk_attention_*_f32: flash-style fp32 VALU kernels; delta f32 [B][H][T] is scratch written by the backward. */
 int gvk_gemm_nt_f32(const gvk_gemm_desc* d, void* stream);
-int gvk_attention_fwd_f32(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                          void* stream);
-int gvk_attention_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
-                          int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream);
-/* fp32 counterparts of gvk_attention_fwd/bwd_bf16_dropout (same mask function, so the two precisions drop the same elements) */
+/* fp32 attention, with or without dropout (drop_p = 0: seed / seed_ptr unused): the counterparts of gvk_attention_fwd/bwd_bf16 and of their
+ * _dropout forms (same mask function, so the two precisions drop the same elements) */
 int gvk_attention_fwd_f32_dropout(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
                                   float drop_p, uint64_t seed, const void* seed_ptr, void* stream);
 int gvk_attention_bwd_f32_dropout(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
@@ -181,13 +178,6 @@ int gvk_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
  * written back; then every row is normalised.  Replaces gvk_prompt_up_fix + gvk_layernorm_fwd at a layer boundary. */
 int gvk_layernorm_fwd_fix(float* x, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd, int M, int C, float eps,
                           const float* enh, const float* lat, const float* wup, int T, int P, int L, void* stream);
-/* bwd (input gradient only -- frozen affine): dx = dres + LN'(dy); dres may be NULL; dx_bf16 (optional) = bf16 copy. */
-int gvk_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                      const float* dres, float* dx, void* dx_bf16, int M, int C, void* stream);
-/* the same for a row SUBSET: rows g * group_stride + r, r < rows_per_group, g < groups, of every operand (the first rows of every sample);
- * the other rows are neither read nor written */
-int gvk_layernorm_bwd_rows(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                           const float* dres, float* dx, void* dx_bf16, int groups, int rows_per_group, int group_stride, int C, void* stream);
 /* affine gradients of a trainable LayerNorm: dgamma[c] += sum_m dy*xhat, dbeta[c] += sum_m dy (accumulate=0 overwrites).
  * scratch: f32 [2*64*C]. */
 int gvk_layernorm_bwd_affine(const float* dy, const float* x, const float* mean, const float* rstd, float* dgamma,
@@ -196,7 +186,7 @@ int gvk_layernorm_bwd_affine(const float* dy, const float* x, const float* mean,
 /* LayerNorm with a fused rank-L projection of the rows it already holds (L = 20 = configs/gaviko.yaml prompt_latent_dim):
  *   fwd_proj:  y_bf16 = LN(x) as gvk_layernorm_fwd, and   proj->y = act(x . W^T + bias)        of the RAW input rows
  *              (gaviko.py:155-156: GPA proj_down + QuickGELU of the post-attention stream; proj->z = pre-activation);
- *   bwd_proj:  dx as gvk_layernorm_bwd, and               proj->y = dx . W                      of the OUTPUT rows
+ *   bwd (gvk_ln_bwd_desc.proj):  dx as without it, and    proj->y = dx . W                      of the OUTPUT rows
  *              (autograd of gaviko.py:187 proj_up: the next-lower layer's dcomb = dG . W_up).
  * w_layout 0: w [L][C]; 1: w [C][L].  Covers L in {4, 8, 16, 20} and 128 <= C <= 1024; otherwise use gvk_skinny_down. */
 typedef struct gvk_rowproj_desc {
@@ -209,18 +199,20 @@ typedef struct gvk_rowproj_desc {
 } gvk_rowproj_desc;
 int gvk_layernorm_fwd_proj(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd,
                            int M, int C, float eps, const gvk_rowproj_desc* proj, void* stream);
-int gvk_layernorm_bwd_proj(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                           const float* dres, float* dx, void* dx_bf16, int M, int C, const gvk_rowproj_desc* proj, void* stream);
-/* gvk_layernorm_bwd / _rows / _bwd_proj with the output gradient dy in bf16 [M][C] -- the form a dgrad GEMM with the STORE_BF16 epilogue
- * leaves it in (fc1 / qkv dgrad of a frozen backbone: half the bytes written by the GEMM and read here).  rows_per_group = 0: all M rows;
- * otherwise rows g * group_stride + r, r < rows_per_group, g < groups (then proj must be NULL).  proj != NULL: as gvk_layernorm_bwd_proj. */
-typedef struct gvk_ln_bwd_dy16_desc {
-  const void* dy_bf16; const float* x; const float* mean; const float* rstd; const float* gamma; const float* dres;
+/* bwd (input gradient only -- frozen affine): dx = dres + LN'(dy) over f32 [M][C] rows; dres may be NULL; dx_bf16 (optional) = bf16 copy of dx.
+ * Three optional features:
+ *   dy_bf16 = 1: dy is bf16 [M][C] -- the form a dgrad GEMM with the STORE_BF16 epilogue leaves it in (fc1 / qkv dgrad of a frozen backbone:
+ *     half the bytes written by the GEMM and read here); 0: dy is f32;
+ *   rows_per_group > 0: a row SUBSET, rows g * group_stride + r, r < rows_per_group, g < groups, of every operand (the first rows of every
+ *     sample; must fit M); the other rows are neither read nor written.  0: all M rows;
+ *   proj != NULL: the rank-L projection proj->y = dx . W rides along (see gvk_rowproj_desc above); all rows only (rows_per_group = 0). */
+typedef struct gvk_ln_bwd_desc {
+  const void* dy; const float* x; const float* mean; const float* rstd; const float* gamma; const float* dres;
   float* dx; void* dx_bf16;
   const gvk_rowproj_desc* proj;
-  int32_t M, C, groups, rows_per_group, group_stride;
-} gvk_ln_bwd_dy16_desc;
-int gvk_layernorm_bwd_dy16(const gvk_ln_bwd_dy16_desc* d, void* stream);
+  int32_t M, C, groups, rows_per_group, group_stride, dy_bf16;
+} gvk_ln_bwd_desc;
+int gvk_layernorm_bwd(const gvk_ln_bwd_desc* d, void* stream);
 /* LayerNorm backward fused with a rank-L update of the same rows:  dx = dres + LN'(dy; x, mean, rstd, gamma) + lat . W^T  (+ bf16 copy).
  * Replaces gvk_layernorm_bwd followed by gvk_skinny_up(accumulate) on the backbone stream: the autograd of gaviko.py:304 (the MLP block's
  * LayerNorm) and of gaviko.py:155 (GPA's proj_down of the global tokens: dG1 += dzx . W_d) in one pass.  lat f32 [M][L]; w_layout 0: W [C][L],

@@ -45,10 +45,7 @@ EXCLUDED = {
 }
 
 # kernels that no test calls directly, each with the reason it is left out
-UNCOVERED = {
-    "gvk_attention_fwd_f32": "superseded by gvk_attention_fwd_f32_dropout (drop_p = 0 runs the same kernel); no wrapper calls it",
-    "gvk_attention_bwd_f32": "superseded by gvk_attention_bwd_f32_dropout (drop_p = 0 runs the same kernel); no wrapper calls it",
-}
+UNCOVERED = {}
 
 
 def header_symbols():

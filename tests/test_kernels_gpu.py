@@ -224,6 +224,10 @@ def test_patch_embed_path(dev):
     assert (Lo[: B * 1000].view(B, 1000, C_).cpu().double() - ref).abs().max().item() < 5e-4
 
 
+LN_BWD_DX_TOL = 2e-5          # fp32 dx against fp64, relative to max(1, |dx|max)
+LN_BWD_DX16_TOL = 2 ** -7     # its bf16 copy, relative to |dx|max
+
+
 @pytest.mark.parametrize("M,C_", [(1033, 768), (77, 192), (515, 1024), (9, 384)])
 def test_layernorm_fwd_bwd(dev, M, C_):
     from gaviko_amd import ops
@@ -249,14 +253,45 @@ def test_layernorm_fwd_bwd(dev, M, C_):
     dx16 = torch.zeros((M, C_), dtype=torch.bfloat16, device=dev)
     ops.layernorm_bwd(dy.to(dev), X, mean, rstd, Gm, M, C_, dx=dx, dres=dres.to(dev), dx16=dx16)
     want = xd.grad + dres.double()
-    assert (dx.cpu().double() - want).abs().max().item() < 2e-5 * max(1.0, want.abs().max().item())
-    assert (dx16.cpu().double() - want).abs().max().item() < 2 ** -7 * want.abs().max().item()
+    assert (dx.cpu().double() - want).abs().max().item() < LN_BWD_DX_TOL * max(1.0, want.abs().max().item())
+    assert (dx16.cpu().double() - want).abs().max().item() < LN_BWD_DX16_TOL * want.abs().max().item()
     dg = torch.zeros(C_, device=dev)
     db = torch.zeros(C_, device=dev)
     scratch = torch.zeros(128 * C_, device=dev)
     ops.layernorm_bwd_affine(dy.to(dev), X, mean, rstd, dg, db, scratch, M, C_)
     assert (dg.cpu().double() - gd.grad).abs().max().item() < 1e-4 * max(1.0, gd.grad.abs().max().item())
     assert (db.cpu().double() - bd.grad).abs().max().item() < 1e-4 * max(1.0, bd.grad.abs().max().item())
+
+
+@pytest.mark.parametrize("with_dres", [True, False])
+@pytest.mark.parametrize("C_", [192, 768])
+def test_layernorm_bwd_leading_rows_f32_dy(dev, C_, with_dres):
+    """layernorm_bwd(rows=(B, P, T)) with an fp32 dy against fp64: the first P rows of every sample get dx = dres + LN'(dy) and its bf16 copy,
+    every other row of dx / dx16 keeps its bits.  B * P = 6 rows on 4-row workgroups: the first workgroup spans the group boundary."""
+    from gaviko_amd import ops
+    B, T, P = 2, 9, 3
+    M = B * T
+    x = _rand((M, C_), 36, 2.0) + 0.3
+    gamma = 1 + _rand((C_,), 37, 0.2)
+    dy = _rand((M, C_), 38)
+    dres = _rand((M, C_), 39) if with_dres else None
+    xd = x.double().requires_grad_(True)
+    torch.nn.functional.layer_norm(xd, (C_,), gamma.double(), None, 1e-5).backward(dy.double())
+    want = xd.grad + (dres.double() if with_dres else 0.0)
+    X, Gm = x.to(dev), gamma.to(dev)
+    mean, rstd = torch.zeros(M, device=dev), torch.zeros(M, device=dev)
+    ops.layernorm_fwd(X, Gm, torch.zeros(C_, device=dev), M, C_, y32=torch.empty(M, C_, device=dev), mean=mean, rstd=rstd)
+    dx = torch.full((M, C_), 7.0, device=dev)
+    dx16 = torch.full((M, C_), 7.0, dtype=torch.bfloat16, device=dev)
+    ops.layernorm_bwd(dy.to(dev), X, mean, rstd, Gm, M, C_, dx=dx, dres=dres.to(dev) if with_dres else None, dx16=dx16, rows=(B, P, T))
+    inside = (torch.arange(M) % T) < P
+    assert int(inside.sum()) == B * P
+    got, got16 = dx.cpu(), dx16.cpu()
+    assert torch.equal(got[~inside], torch.full((M - B * P, C_), 7.0))
+    assert torch.equal(got16[~inside], torch.full((M - B * P, C_), 7.0, dtype=torch.bfloat16))
+    w = want[inside]
+    assert (got[inside].double() - w).abs().max().item() < LN_BWD_DX_TOL * max(1.0, w.abs().max().item())
+    assert (got16[inside].double() - w).abs().max().item() < LN_BWD_DX16_TOL * w.abs().max().item()
 
 
 def test_casts(dev):

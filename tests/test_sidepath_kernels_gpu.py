@@ -393,7 +393,7 @@ def test_layernorm_bwd_with_fused_projection(dev, M, C):
     from gaviko_amd import ops
     _g = torch.Generator(device=dev).manual_seed(M + C)
     rnd = lambda *sh, device: torch.randn(*sh, device=device, generator=_g)
-    """gvk_layernorm_bwd_proj = LayerNorm backward (dx, bf16 copy) + dx . W_up ([C][L] weight, autograd of gaviko.py:187)."""
+    """gvk_layernorm_bwd with proj = LayerNorm backward (dx, bf16 copy) + dx . W_up ([C][L] weight, autograd of gaviko.py:187)."""
     L_ = 20
     x, dy, dres = rnd(M, C, device=dev), rnd(M, C, device=dev), rnd(M, C, device=dev)
     g = 1 + 0.2 * rnd(C, device=dev)
@@ -402,7 +402,7 @@ def test_layernorm_bwd_with_fused_projection(dev, M, C):
     dx, dx2 = torch.empty(M, C, device=dev), torch.empty(M, C, device=dev)
     dx16 = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
     y = torch.empty(M, L_, device=dev)
-    ops.layernorm_bwd_proj(dy, x, mean, rstd, g, M, C, dx=dx, dres=dres, dx16=dx16, w=wup, y=y, w_layout=1)
+    ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=dx, dres=dres, dx16=dx16, proj=dict(w=wup, y=y, w_layout=1))
     ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=dx2, dres=dres)
     # same fp32 arithmetic, different order of the two row sums (wave shuffle tree vs four-lane + eight-wave partials): round-off apart
     assert (dx - dx2).abs().max().item() <= 4e-6 * dx2.abs().max().item()
@@ -411,7 +411,7 @@ def test_layernorm_bwd_with_fused_projection(dev, M, C):
 
 
 def test_layernorm_bwd_with_bf16_gradient_input(dev):
-    """gvk_layernorm_bwd_dy16: the three backward forms (all rows / the leading rows of every sample / with the rank-L projection) reading the
+    """gvk_layernorm_bwd with a bf16 dy: the three backward forms (all rows / the leading rows of every sample / with the rank-L projection) reading the
     output gradient as bf16 -- the same numbers as the fp32-input kernels fed the upcast values (bit-equal for the two plain forms: one kernel)."""
     from gaviko_amd import ops
     B, T, C, L_, P = 4, 1033, 768, 20, 32
@@ -426,21 +426,23 @@ def test_layernorm_bwd_with_bf16_gradient_input(dev):
     mean, rstd = x.mean(-1).contiguous(), (x.var(-1, unbiased=False) + 1e-5).rsqrt().contiguous()
     a, b = torch.empty(M, C, device=dev), torch.empty(M, C, device=dev)
     a16, b16 = (torch.empty(M, C, dtype=torch.bfloat16, device=dev) for _ in range(2))
-    ops.layernorm_bwd_dy16(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, dx16=a16)
+    ops.layernorm_bwd(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, dx16=a16)
     ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=b, dres=dres, dx16=b16)
     assert torch.equal(a, b) and torch.equal(a16, b16)
     a.fill_(7.0); b.fill_(7.0)
-    ops.layernorm_bwd_dy16(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, rows=(B, P, T))
-    ops.layernorm_bwd_rows(dy, x, mean, rstd, g, B, P, T, C, dx=b, dres=dres)
+    ops.layernorm_bwd(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, rows=(B, P, T))
+    ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=b, dres=dres, rows=(B, P, T))
     assert torch.equal(a, b)
     assert bool((a[P:T] == 7.0).all()) and bool((a[T:T + P] != 7.0).any())
     ya, yb = torch.empty(M, L_, device=dev), torch.empty(M, L_, device=dev)
-    ops.layernorm_bwd_dy16(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, dx16=a16, proj=dict(w=wup, y=ya, w_layout=1, L_=L_))
-    ops.layernorm_bwd_proj(dy, x, mean, rstd, g, M, C, dx=b, dres=dres, dx16=b16, w=wup, y=yb, w_layout=1)
+    ops.layernorm_bwd(dy16, x, mean, rstd, g, M, C, dx=a, dres=dres, dx16=a16, proj=dict(w=wup, y=ya, w_layout=1, L_=L_))
+    ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=b, dres=dres, dx16=b16, proj=dict(w=wup, y=yb, w_layout=1))
     assert (a - b).abs().max().item() <= 4e-6 * b.abs().max().item()
     assert torch.allclose(ya, yb, atol=3e-5, rtol=1e-5)
     with pytest.raises(ops.L.GavikoHipError, match="all rows"):
-        ops.layernorm_bwd_dy16(dy16, x, mean, rstd, g, M, C, dx=a, rows=(B, P, T), proj=dict(w=wup, y=ya, w_layout=1, L_=L_))
+        ops.layernorm_bwd(dy16, x, mean, rstd, g, M, C, dx=a, rows=(B, P, T), proj=dict(w=wup, y=ya, w_layout=1, L_=L_))
+    with pytest.raises(ops.L.GavikoHipError, match="all rows"):
+        ops.layernorm_bwd(dy, x, mean, rstd, g, M, C, dx=b, rows=(B, P, T), proj=dict(w=wup, y=yb, w_layout=1, L_=L_))
 
 
 def test_fused_projection_rejects_other_latent_widths(dev):

@@ -59,4 +59,4 @@ dxo = f(M, C)
 t("layernorm_fwd (plain)", lambda: ops.layernorm_fwd(x, g, bt, M, C, y16=y16, mean=mean, rstd=rstd), 1.5 * pass_b)
 t("layernorm_fwd_proj layout0 gelu", lambda: ops.layernorm_fwd_proj(x, g, bt, M, C, y16=y16, mean=mean, rstd=rstd, w=w, bias=b, z=z, y=y, act=1, w_layout=0), 1.5 * pass_b)
 t("layernorm_bwd (plain, dres, dx16)", lambda: ops.layernorm_bwd(out, x, mean, rstd, g, M, C, dx=dxo, dres=res, dx16=y16), 4.5 * pass_b)
-t("layernorm_bwd_proj layout1", lambda: ops.layernorm_bwd_proj(out, x, mean, rstd, g, M, C, dx=dxo, dres=res, dx16=y16, w=wt, y=y, w_layout=1), 4.5 * pass_b)
+t("layernorm_bwd proj layout1", lambda: ops.layernorm_bwd(out, x, mean, rstd, g, M, C, dx=dxo, dres=res, dx16=y16, proj=dict(w=wt, y=y, w_layout=1)), 4.5 * pass_b)
