@@ -15,6 +15,13 @@ torchio 0.20.16 (requirements.txt:6) and its SimpleITK backend are not installed
   module's own (rotation R = R2.R1.R0 about the array axes), not SimpleITK's LPS ones: same augmentation distribution up to
   axis naming, not the same voxels for the same seed.  Parity vs torchio is UNPINNED; the kernels are pinned against
   `oracle/data_ref.py` (numpy) and scipy.ndimage.affine_transform.
+
+The intensity group train.py:43-48 declares (RandomNoise, RandomBiasField, RandomBlur; its OneOf line is commented out in the shipped
+script) is built too, as two more kernels (`csrc/intensity.hip`): `train_transforms(intensity=True)` puts `OneOf` of the three between the
+spatial pass and RescaleIntensity.  RandomMotion (k-space compositing, a 3-D FFT of the whole volume) is not built.  The parameter
+sampling is torchio's; the noise field comes from this package's counter hash, not torch's generator, and the bias-field axes are the
+array axes: same distributions, not the same voxels for the same seed.  Parity vs torchio is UNPINNED here as well; the kernels are pinned
+against scipy.ndimage.gaussian_filter and a numpy restatement (`tests/intensity_ref.py`).
 """
 from __future__ import annotations
 
@@ -135,24 +142,149 @@ class RescaleIntensity:
     def __init__(self, out_min_max=(0, 1)):
         self.out_min, self.out_max = float(out_min_max[0]), float(out_min_max[1])
 
+# ---- intensity transforms: train.py:43-48 minus RandomMotion ----------------------------------------------------------------------
+# Each `sample(rng)` returns None (not applied) or (class name, params) and draws, in this order: one uniform for p, then the
+# parameters as listed in its docstring.  Parity with torchio itself is unpinned (module docstring).
+class RandomNoise:
+    """tio.RandomNoise(mean=0, std=(0, 0.25), p=1): y = x + N(mean, std).  A scalar mean m means mean ~ U(-m, m), a scalar std d means
+    std ~ U(0, d).  Draws: mean, std, a 64-bit seed of the counter-hash noise field (`csrc/intensity.hip`)."""
+
+    def __init__(self, mean=0, std=(0, 0.25), p: float = 1.0):
+        self.mean = _pair(mean, "mean")
+        self.std = (0.0, float(std)) if isinstance(std, (int, float)) else _pair(std, "std")
+        if self.std[0] < 0 or self.std[1] < self.std[0]:
+            raise ValueError("RandomNoise: std is a non-negative number or a (low, high) pair with 0 <= low <= high")
+        self.p = float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        mean, std = rng.uniform(*self.mean), rng.uniform(*self.std)
+        return "RandomNoise", dict(mean=float(mean), std=float(std), seed=int(rng.integers(0, 2 ** 64, dtype=np.uint64)))
+
+
+def bias_terms(order: int):
+    """Exponents (a, b, c) of the bias-field polynomial in coefficient order: torchio's nested loops over x, y, z orders, which are array
+    axes 0, 1, 2 here."""
+    return [(a, b, c) for a in range(order + 1) for b in range(order + 1 - a) for c in range(order + 1 - a - b)]
+
+
+class RandomBiasField:
+    """tio.RandomBiasField(coefficients=0.5, order=3, p=1): y = x * exp(P), P a polynomial of total degree <= order in the three array
+    coordinates normalised to [-1, 1].  Draws: one coefficient ~ U(-c, c) per term of `bias_terms(order)`, in that order."""
+
+    def __init__(self, coefficients=0.5, order: int = 3, p: float = 1.0):
+        if not 0 <= int(order) <= 3:
+            raise NotImplementedError("RandomBiasField: polynomial orders 0..3 are built")
+        self.coefficients, self.order, self.p = _pair(coefficients, "coefficients"), int(order), float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        return "RandomBiasField", dict(coefficients=rng.uniform(self.coefficients[0], self.coefficients[1], len(bias_terms(self.order))), order=self.order)
+
+
+class RandomBlur:
+    """tio.RandomBlur(std=(0, 2), p=1): scipy.ndimage.gaussian_filter with one sigma ~ U(low, high) per array axis (spacing 1).  A scalar
+    std d means U(0, d).  Draws: the three sigmas.  sigma above 4 (kernel radius above 16) is not built."""
+
+    def __init__(self, std=(0, 2), p: float = 1.0):
+        self.std = (0.0, float(std)) if isinstance(std, (int, float)) else _pair(std, "std")
+        if self.std[0] < 0 or self.std[1] < self.std[0]:
+            raise ValueError("RandomBlur: std is a non-negative number or a (low, high) pair with 0 <= low <= high")
+        if int(4.0 * self.std[1] + 0.5) > ops.BLUR_MAX_RADIUS:
+            raise NotImplementedError("RandomBlur: sigma above 4 (kernel radius above 16) is not built")
+        self.p = float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        return "RandomBlur", dict(std=rng.uniform(self.std[0], self.std[1], 3))
+
+
+INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur)
+_BUILT = "RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, OneOf of the last three, RescaleIntensity (at most one)"
+
+
+class OneOf:
+    """tio.OneOf(transforms, p=1): with probability p exactly one member is applied, chosen by weight (a dict transform -> weight, or a
+    sequence with equal weights; weights are normalised).  The member's own p still applies.  Draws: one uniform for p, one for the choice,
+    then the member's."""
+
+    def __init__(self, transforms, p: float = 1.0):
+        items = list(transforms.items()) if isinstance(transforms, dict) else [(t, 1.0) for t in transforms]
+        if not items:
+            raise ValueError("OneOf: at least one transform")
+        for t, w in items:
+            if not isinstance(t, INTENSITY_TRANSFORMS):
+                raise NotImplementedError(f"OneOf: {type(t).__name__} is not built on the device ({_BUILT}; RandomMotion is not built)")
+            if w < 0:
+                raise ValueError("OneOf: weights are non-negative")
+        total = float(sum(w for _, w in items))
+        if total <= 0:
+            raise ValueError("OneOf: the weights sum to zero")
+        self.transforms = [t for t, _ in items]
+        self.weights = np.array([w / total for _, w in items], dtype=np.float64)
+        self.p = float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        i = min(int(np.searchsorted(np.cumsum(self.weights), rng.random(), side="right")), len(self.transforms) - 1)
+        return self.transforms[i].sample(rng)
+
+
+def blur_tables(sigmas):
+    """Host half of `ops.gaussian_blur3d` for sigmas [B][3]: (weights float32 [B][3][2R+1], radius int32 [B][3]) exactly as
+    scipy.ndimage.gaussian_filter builds them (truncate = 4.0: radius int(4 sigma + 0.5), exp(-0.5 k^2 / sigma^2) normalised in float64; an
+    axis with sigma <= 1e-15 is skipped = radius 0 with the single weight 1)."""
+    s = np.asarray(sigmas, dtype=np.float64).reshape(-1, 3)
+    weights = np.zeros((len(s), 3, ops.BLUR_TAPS), dtype=np.float32)
+    weights[:, :, 0] = 1.0
+    radius = np.zeros((len(s), 3), dtype=np.int32)
+    for b in range(len(s)):
+        for a in range(3):
+            if s[b, a] > 1e-15:
+                r = int(4.0 * s[b, a] + 0.5)
+                if r > ops.BLUR_MAX_RADIUS:
+                    raise ValueError(f"blur_tables: sigma {s[b, a]} needs radius {r}; sigma above 4 (radius above {ops.BLUR_MAX_RADIUS}) is not built")
+                k = np.arange(-r, r + 1, dtype=np.float64)
+                w = np.exp(-0.5 / (s[b, a] * s[b, a]) * k ** 2)
+                weights[b, a, :2 * r + 1] = w / w.sum()
+                radius[b, a] = r
+    return weights, radius
+
+
+def bias_coefficients(coefficients, order: int, to_order: int) -> np.ndarray:
+    """The coefficients of an order-`order` bias field laid out for a launch at `to_order` >= order (the missing terms are zero)."""
+    have = {t: c for t, c in zip(bias_terms(order), coefficients)}
+    return np.array([have.get(t, 0.0) for t in bias_terms(to_order)], dtype=np.float64)
+
 
 class DeviceCompose:
     """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Spatial transforms are merged
-    into one resampling pass (affine first, flips on its output), RescaleIntensity runs last, as in the reference's Compose."""
+    into one resampling pass (affine first, flips on its output), the intensity transforms (singly or inside OneOf) follow in listed
+    order, RescaleIntensity runs last, as in the reference's Compose.  Per sample the random draws are: affine, flips, then every
+    intensity transform in listed order; with no intensity transform listed the consumed stream is what it was before they existed."""
 
     def __init__(self, transforms: Sequence, seed: Optional[int] = None):
         self.affine = [t for t in transforms if isinstance(t, RandomAffine)]
         self.flips = [t for t in transforms if isinstance(t, RandomFlip)]
         self.rescale = [t for t in transforms if isinstance(t, RescaleIntensity)]
-        if len(self.affine) > 1 or len(self.rescale) > 1 or len(self.affine) + len(self.flips) + len(self.rescale) != len(transforms):
-            raise NotImplementedError("DeviceCompose: RandomAffine (at most one), RandomFlip, RescaleIntensity (at most one)")
+        self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS + (OneOf,))]
+        if len(self.affine) > 1 or len(self.rescale) > 1 or \
+                len(self.affine) + len(self.flips) + len(self.rescale) + len(self.intensity) != len(transforms):
+            raise NotImplementedError(f"DeviceCompose: {_BUILT}; RandomMotion and anything else are not built")
         self.rng = np.random.default_rng(seed)
         self.last_params = None                                           # [(flip bits, affine params or None)] of the last call: tests, logging
+        # the intensity draws of the last call, one entry per sample: None or (class name, params) -- with several intensity transforms
+        # listed, a tuple of such entries in listed order
+        self.last_intensity = None
 
     def sample(self, B: int, shape):
         mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, 1, 1))
         flags = np.zeros(B, dtype=np.int32)
-        params = []
+        params, draws = [], []
         for b in range(B):
             aff = self.affine[0].sample(self.rng) if self.affine else None
             bits = 0
@@ -163,8 +295,40 @@ class DeviceCompose:
                 bits |= 8
             flags[b] = bits
             params.append((bits & 7, aff))
-        self.last_params = params
+            d = tuple(t.sample(self.rng) for t in self.intensity)
+            draws.append(d[0] if len(d) == 1 else (d or None))
+        self.last_params, self.last_intensity = params, draws
         return mats, flags
+
+    def _intensity_stage(self, x: torch.Tensor, draws) -> torch.Tensor:
+        """One listed intensity transform on the batch: draws[b] = None or (name, params).  At most one pointwise and one blur launch, each
+        only when a sample drew it; samples that drew nothing ride along as copies."""
+        B, dev = x.shape[0], x.device
+        names = [d[0] if d else None for d in draws]
+        if "RandomNoise" in names or "RandomBiasField" in names:
+            kind, noise = np.zeros(B, dtype=np.int32), np.zeros((B, 2), dtype=np.float32)
+            seeds, coeff = np.zeros(B, dtype=np.uint64), np.zeros((B, ops.BIAS_COEFFS), dtype=np.float32)
+            order = max([d[1]["order"] for d in draws if d and d[0] == "RandomBiasField"], default=0)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomNoise":
+                    kind[b], noise[b], seeds[b] = ops.INTENSITY_NOISE, (d[1]["std"], d[1]["mean"]), d[1]["seed"]
+                elif d and d[0] == "RandomBiasField":
+                    c = bias_coefficients(d[1]["coefficients"], d[1]["order"], order)
+                    kind[b], coeff[b, :len(c)] = ops.INTENSITY_BIAS, c
+            y = torch.empty_like(x)
+            ops.intensity_pointwise(x, y, torch.from_numpy(kind).to(dev), torch.from_numpy(noise).to(dev), torch.from_numpy(seeds.view(np.int64)).to(dev),
+                                    torch.from_numpy(coeff).to(dev), order)
+            x = y
+        if "RandomBlur" in names:
+            sig = np.zeros((B, 3), dtype=np.float64)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomBlur":
+                    sig[b] = d[1]["std"]
+            weights, radius = blur_tables(sig)
+            y, scratch = torch.empty_like(x), torch.empty_like(x)
+            ops.gaussian_blur3d(x, y, scratch, torch.from_numpy(weights).to(dev), torch.from_numpy(radius).to(dev), int(radius.max()))
+            x = y
+        return x
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:
@@ -173,13 +337,15 @@ class DeviceCompose:
             x = x.float().contiguous()
         B, shape = x.shape[0], tuple(x.shape[-3:])
         part = ops.minmax_partials(B, x.device)
-        if self.affine or self.flips:
+        if self.affine or self.flips or self.intensity:
             mats, flags = self.sample(B, shape)
             if flags.any():
                 ops.volume_minmax(x, part)                                # pad value of the resampling = the input volume's minimum
                 out = torch.empty_like(x)
                 ops.spatial_transform(x, out, torch.from_numpy(mats).to(x.device), torch.from_numpy(flags).to(x.device), part)
                 x = out
+            for s in range(len(self.intensity)):
+                x = self._intensity_stage(x, [d if len(self.intensity) == 1 else (d[s] if d else None) for d in self.last_intensity])
         if self.rescale:
             ops.volume_minmax(x, part)
             y = torch.empty_like(x)
@@ -188,9 +354,13 @@ class DeviceCompose:
         return x
 
 
-def train_transforms(seed: Optional[int] = None) -> DeviceCompose:
-    """train.py:38-52 (the intensity_augment dict of 43-48 is dead code there: its OneOf line is commented out)."""
-    return DeviceCompose([RandomAffine(degrees=15, p=0.5), RandomFlip(axes=(0,), flip_probability=0.5), RescaleIntensity((0, 1))], seed)
+def train_transforms(seed: Optional[int] = None, intensity: bool = False) -> DeviceCompose:
+    """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
+    line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device: the
+    reference's dict minus RandomMotion (not built), its 0.25 weight redistributed over the other three."""
+    spatial = [RandomAffine(degrees=15, p=0.5), RandomFlip(axes=(0,), flip_probability=0.5)]
+    one_of = [OneOf({RandomNoise(): 1, RandomBiasField(): 1, RandomBlur(std=(0, 1.5)): 1}, p=0.75)] if intensity else []
+    return DeviceCompose(spatial + one_of + [RescaleIntensity((0, 1))], seed)
 
 
 def eval_transforms() -> DeviceCompose:
@@ -200,11 +370,13 @@ def eval_transforms() -> DeviceCompose:
 
 class DataPreprocessor:
     """train.py:33-78: same CSV columns (`subset`, `mri_path`, `kl_grade`), same loaders and return tuple; the transforms are the
-    device-side `train_transforms` / `val_transforms` attributes to call on each batch after `.to(device)`."""
+    device-side `train_transforms` / `val_transforms` attributes to call on each batch after `.to(device)`.  config['data']['intensity_augment']
+    (default False) adds the intensity OneOf of `train_transforms(intensity=True)`."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
-        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed), eval_transforms(), eval_transforms()
+        intensity = bool(config["data"].get("intensity_augment", False))
+        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity), eval_transforms(), eval_transforms()
 
     def preprocess(self, df=None):
         import pandas as pd

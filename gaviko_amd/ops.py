@@ -1151,6 +1151,41 @@ def spatial_transform(x, out, mats, flags, partials) -> None:
             "gvk_spatial_transform")
 
 
+BLUR_MAX_RADIUS, BLUR_TAPS, BIAS_COEFFS = 16, 33, 20                     # GVK_BLUR_MAX_RADIUS, its table row length, GVK_BIAS_COEFFS
+INTENSITY_COPY, INTENSITY_NOISE, INTENSITY_BIAS = 0, 1, 2                # kind[b] of intensity_pointwise
+
+
+def gaussian_blur3d(x, out, scratch, weights, radius, max_radius) -> None:
+    """out = scipy.ndimage.gaussian_filter(x[b], sigma_b) per sample (mode='reflect', truncate=4): weights f32 [B][3][33] and radius i32
+    [B][3] are device tables built on the host (data.blur_tables), max_radius their largest radius; scratch is a third buffer of x's size."""
+    _chk(x, torch.float32, "gaussian_blur3d in")
+    _chk(out, torch.float32, "gaussian_blur3d out", x.numel())
+    _chk(scratch, torch.float32, "gaussian_blur3d scratch", x.numel())
+    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != B * D * H * W:
+        raise L.GavikoHipError("gaussian_blur3d in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    _chk(weights, torch.float32, "gaussian_blur3d weights", 3 * BLUR_TAPS * B)
+    _chk(radius, torch.int32, "gaussian_blur3d radius", 3 * B)
+    L.check(L.load().gvk_gaussian_blur3d(L.ptr(x), L.ptr(out), L.ptr(scratch), L.ptr(weights), L.ptr(radius), int(max_radius), B, D, H, W,
+                                         L.stream_ptr()), "gvk_gaussian_blur3d")
+
+
+def intensity_pointwise(x, y, kind, noise, seeds, coeff, order=3) -> None:
+    """y[b] = x[b] (kind 0), x[b] + (std z + mean) (kind 1: noise f32 [B][2] = (std, mean), seeds i64 [B] holding the uint64 bit patterns) or
+    x[b] exp(P) (kind 2: coeff f32 [B][20], polynomial order <= 3 for the launch); kind i32 [B].  y may be x."""
+    _chk(x, torch.float32, "intensity_pointwise x")
+    _chk(y, torch.float32, "intensity_pointwise y", x.numel())
+    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != B * D * H * W:
+        raise L.GavikoHipError("intensity_pointwise x: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    _chk(kind, torch.int32, "intensity_pointwise kind", B)
+    _chk(noise, torch.float32, "intensity_pointwise noise", 2 * B)
+    _chk(seeds, torch.int64, "intensity_pointwise seeds", B)
+    _chk(coeff, torch.float32, "intensity_pointwise coeff", BIAS_COEFFS * B)
+    L.check(L.load().gvk_intensity_pointwise(L.ptr(x), L.ptr(y), L.ptr(kind), L.ptr(noise), L.ptr(seeds), L.ptr(coeff), int(order), B, D, H, W,
+                                             L.stream_ptr()), "gvk_intensity_pointwise")
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

@@ -651,6 +651,28 @@ int gvk_spatial_transform(const float* in, float* out, const float* mats, const 
 int gvk_eval_rows(const float* logits, const void* target, float* proba, int32_t* pred, void* confusion, int N, int K, void* stream);
 int gvk_ovr_auc_counts(const float* proba, const void* target, void* counts, int N, int K, void* stream);
 
+/* ---- intensity augmentation (csrc/intensity.hip): the intensity group of train.py:43-48 minus RandomMotion --------------------
+ * Volumes are float32 [B][D][H][W], one channel, resident in HBM; every table below is a DEVICE array with one row per sample, so one
+ * launch serves a batch in which each sample drew a different transform or none.  Parity with torchio itself is unpinned.
+ * gvk_gaussian_blur3d: tio.RandomBlur = scipy.ndimage.gaussian_filter(x, sigma=(s0, s1, s2)) with scipy's defaults: mode='reflect' (any
+ *   radius, also above the axis length), truncate = 4.0.  The HOST builds the taps: radius [B][3] = int(4 sigma + 0.5) (0 on an axis with
+ *   sigma <= 1e-15, which scipy skips), weights [B][3][2 GVK_BLUR_MAX_RADIUS + 1] = exp(-0.5 k^2 / sigma^2) normalised to sum 1 in float64,
+ *   rounded to float32, taps 0..2r of an axis at the start of its row (radius 0: the single weight 1).  max_radius states the largest entry
+ *   of radius; above GVK_BLUR_MAX_RADIUS (sigma above 4) the call is rejected, and the kernels clamp what they read to that cap.  fp32
+ *   accumulation.  Two passes over HBM: H and W together through LDS into scratch [B][D*H*W] (caller-provided), then D down coalesced
+ *   columns into out.  in, out and scratch are three different buffers.  A sample with radius (0, 0, 0) comes back bit-identical.
+ * gvk_intensity_pointwise: one streaming pass, y may be x.  kind [B]: 0 copy; 1 tio.RandomNoise, y = x + (std z(i) + mean) with noise
+ *   [B][2] = (std, mean), seeds uint64 [B] and z(i) = sqrtf(-2 logf(u1)) cosf(2 pi u2), u1 = ((h(seed, 2i) >> 8) + 1) 2^-24,
+ *   u2 = (h(seed, 2i+1) >> 8) 2^-24, h = the element hash of gvk_dropout_rows, i = voxel index inside the volume; 2 tio.RandomBiasField,
+ *   y = x expf(P(c0, c1, c2)), ck = (k - (n_k - 1)/2) / ((n_k - 1)/2) along array axis k (0 when n_k = 1), P = sum of coeff[j] c0^a c1^b c2^c
+ *   over a in 0..order, b in 0..order-a, c in 0..order-a-b nested in that order with j counting up; coeff [B][GVK_BIAS_COEFFS], order <= 3 for
+ *   the whole launch.  All three tables must be valid pointers whatever the kinds.  16-byte aligned volumes, D*H*W a multiple of 4. */
+enum { GVK_BLUR_MAX_RADIUS = 16, GVK_BIAS_COEFFS = 20 };
+int gvk_gaussian_blur3d(const float* in, float* out, float* scratch, const float* weights, const int32_t* radius, int max_radius, int B, int D, int H,
+                        int W, void* stream);
+int gvk_intensity_pointwise(const float* x, float* y, const int32_t* kind, const float* noise, const void* seeds, const float* coeff, int order, int B,
+                            int D, int H, int W, void* stream);
+
 /* ---- nn.Dropout as its own pass (sites without a producing kernel to fuse into) ------------------------------------------
  * Replaces vision_transformer.py:157 (emb_dropout), vpt.py:129,148,152 (prompt_dropout) and carries the masks of the
  * Linear+Dropout pairs (vision_transformer.py:34,54) onto the gradient side.  out32 / out16 (either may be NULL, out32 may alias x)
