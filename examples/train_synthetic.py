@@ -43,12 +43,14 @@ def make_dataset(root, n, num_classes, seed=0):
     return csv
 
 
-def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False):
+def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False,
+        motion_augment=False):
     dev = torch.device("cuda:0")
     K = 5
     csv = make_dataset(os.path.join(out, "data"), samples, K, seed)
     config = {"data": dict(data_path=csv, image_folder=os.path.join(out, "data"), batch_size=batch_size, num_workers=0,
-                           intensity_augment=intensity_augment),         # train.py:43-51: the OneOf(intensity_augment) stage, on the device
+                           intensity_augment=intensity_augment,          # train.py:43-51: the OneOf(intensity_augment) stage, on the device
+                           motion_augment=motion_augment),               # ... with tio.RandomMotion as its fourth member (needs the stage)
               "model": dict(method=method, backbone=backbone, image_size=160, image_patch_size=16, frames=120, frame_patch_size=12, num_classes=K,
                             channels=1, pool="cls", dim_head=64, dropout=0.1, emb_dropout=0.1, freeze_vit=True, num_prompts=8, prompt_dim=64,
                             prompt_dropout=0.1, deep_prompt=method == "deep_vpt", prompt_latent_dim=20, local_dim=20, local_k=(6, 6, 6),
@@ -100,7 +102,8 @@ if __name__ == "__main__":
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--out", default="/tmp/gaviko_run")
     ap.add_argument("--intensity-augment", action="store_true", help="add noise / bias field / blur (one of, p=0.75) to the train transforms")
+    ap.add_argument("--motion-augment", action="store_true", help="with --intensity-augment: add k-space motion as the fourth member of that group")
     a = ap.parse_args()
-    res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment)
+    res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment)
     print("checkpoint:", res["checkpoint"])
     print("results   :", res["results_csv"])

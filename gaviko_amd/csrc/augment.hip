@@ -6,11 +6,10 @@
 // oracle (oracle/data_ref.py) is a numpy restatement of the same -- parity with torchio itself is unpinned.
 // All three kernels are HBM-bound streams: 12.3 MB per (120,160,160) volume and pass.
 #include "common.hpp"
+#include "resample.hpp"
 #include "../../include/gaviko_hip.h"
 
 namespace gvk {
-
-constexpr int kMmSlabs = 256;     // partial (min, max) pairs per volume (= the block size of the kernels that reduce them)
 
 // stage 1: slab x volume -> (min, max); float4 loads, 256 threads
 __global__ __launch_bounds__(256) void volume_minmax_kernel(const float* __restrict__ x, float* __restrict__ part, long long V) {
@@ -49,20 +48,6 @@ __global__ __launch_bounds__(256) void volume_minmax_kernel(const float* __restr
     __syncthreads();
   }
   if (tid == 0) { part[((size_t)b * kMmSlabs + slab) * 2] = smin[0]; part[((size_t)b * kMmSlabs + slab) * 2 + 1] = smax[0]; }
-}
-
-// every thread of a 256-thread block calls this (block-uniform): thread t brings partial t, the block reduces through LDS
-__device__ __forceinline__ void reduce_partials(const float* part, int b, float& lo, float& hi) {
-  __shared__ float rlo[256], rhi[256];
-  const int tid = threadIdx.x;
-  rlo[tid] = part[((size_t)b * kMmSlabs + tid) * 2];
-  rhi[tid] = part[((size_t)b * kMmSlabs + tid) * 2 + 1];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) { rlo[tid] = fminf(rlo[tid], rlo[tid + s]); rhi[tid] = fmaxf(rhi[tid], rhi[tid + s]); }
-    __syncthreads();
-  }
-  lo = rlo[0]; hi = rhi[0];
 }
 
 // stage 2: y = ((x - min) / (max - min)) * (out_max - out_min) + out_min, the four float32 steps of torchio in that order
@@ -122,26 +107,7 @@ __global__ __launch_bounds__(256) void spatial_kernel(const float* __restrict__ 
   const float* m = mats + (size_t)b * 12;                  // row-major 3x4, array-axis order (axis 0 = depth)
   for (int z = 0; z < D; ++z) {
     const float qz = (float)((fl & 1) ? D - 1 - z : z), qy = (float)my, qx = (float)mx;
-    const float pz = m[0] * qz + m[1] * qy + m[2] * qx + m[3];
-    const float py = m[4] * qz + m[5] * qy + m[6] * qx + m[7];
-    const float px = m[8] * qz + m[9] * qy + m[10] * qx + m[11];
-    const float fz = floorf(pz), fy = floorf(py), fx = floorf(px);
-    const int iz = (int)fz, iy = (int)fy, ix = (int)fx;
-    const float wz = pz - fz, wy = py - fy, wx = px - fx;
-    float acc = 0.f;
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-          const int zz = iz + dz, yy = iy + dy, xx = ix + dx;
-          const bool ok = zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W;
-          const float v = ok ? src[((size_t)zz * H + yy) * W + xx] : pad;
-          const float w = (dz ? wz : 1.f - wz) * (dy ? wy : 1.f - wy) * (dx ? wx : 1.f - wx);
-          acc += w * v;
-        }
-    dst[((size_t)z * H + y) * W + x] = acc;
+    dst[((size_t)z * H + y) * W + x] = trilinear_sample(src, m, qz, qy, qx, D, H, W, pad);
   }
 }
 

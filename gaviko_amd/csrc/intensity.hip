@@ -1,5 +1,5 @@
 // Intensity augmentation on the device: the intensity group train.py:43-48 declares (tio.RandomNoise, tio.RandomBiasField,
-// tio.RandomBlur; RandomMotion is k-space compositing and is not built) applied to a batch of fp32 volumes [B][D][H][W] already in HBM.
+// tio.RandomBlur; RandomMotion, the fourth, is csrc/motion.hip) applied to a batch of fp32 volumes [B][D][H][W] already in HBM.
 // Every kernel takes per-sample parameters, so one launch serves a batch in which each sample drew a different transform or none.
 // torchio (0.20.16, requirements.txt:6) is not installed in this image: the arithmetic follows its published algorithm and is pinned
 // against scipy.ndimage.gaussian_filter and a numpy restatement (tests/intensity_ref.py) -- parity with torchio itself is unpinned

@@ -16,12 +16,16 @@ torchio 0.20.16 (requirements.txt:6) and its SimpleITK backend are not installed
   axis naming, not the same voxels for the same seed.  Parity vs torchio is UNPINNED; the kernels are pinned against
   `oracle/data_ref.py` (numpy) and scipy.ndimage.affine_transform.
 
-The intensity group train.py:43-48 declares (RandomNoise, RandomBiasField, RandomBlur; its OneOf line is commented out in the shipped
-script) is built too, as two more kernels (`csrc/intensity.hip`): `train_transforms(intensity=True)` puts `OneOf` of the three between the
-spatial pass and RescaleIntensity.  RandomMotion (k-space compositing, a 3-D FFT of the whole volume) is not built.  The parameter
-sampling is torchio's; the noise field comes from this package's counter hash, not torch's generator, and the bias-field axes are the
-array axes: same distributions, not the same voxels for the same seed.  Parity vs torchio is UNPINNED here as well; the kernels are pinned
-against scipy.ndimage.gaussian_filter and a numpy restatement (`tests/intensity_ref.py`).
+The intensity group train.py:43-48 declares (RandomNoise, RandomBiasField, RandomBlur, RandomMotion; its OneOf line is commented out in
+the shipped script) is built too: `train_transforms(intensity=True)` puts `OneOf` of the first three (two kernels, `csrc/intensity.hip`)
+between the spatial pass and RescaleIntensity, `motion=True` makes it the reference's four-member dict.  RandomMotion (k-space
+compositing of rigidly moved copies) is one fused kernel (`csrc/motion.hip`) and needs no FFT: torchio's slabs lie along the last array
+axis only, so a real circular convolution along W per moved image is all that is left (`motion_tables`).  The parameter
+sampling is torchio's; the noise field comes from this package's counter hash, not torch's generator, the bias-field axes are the
+array axes, and RandomMotion's movements use this module's RandomAffine conventions, translate in voxels (the reference's arrays have
+spacing 1) and are not demeaned: same distributions, not the same voxels for the same seed.  Parity vs torchio is UNPINNED here as well;
+the kernels are pinned against scipy.ndimage.gaussian_filter, a numpy restatement (`tests/intensity_ref.py`) and torchio's compositing
+written literally with np.fft (`tests/motion_ref.py`).
 """
 from __future__ import annotations
 
@@ -142,7 +146,7 @@ class RescaleIntensity:
     def __init__(self, out_min_max=(0, 1)):
         self.out_min, self.out_max = float(out_min_max[0]), float(out_min_max[1])
 
-# ---- intensity transforms: train.py:43-48 minus RandomMotion ----------------------------------------------------------------------
+# ---- intensity transforms: train.py:43-48 --------------------------------------------------------------------------------------------
 # Each `sample(rng)` returns None (not applied) or (class name, params) and draws, in this order: one uniform for p, then the
 # parameters as listed in its docstring.  Parity with torchio itself is unpinned (module docstring).
 class RandomNoise:
@@ -202,8 +206,34 @@ class RandomBlur:
         return "RandomBlur", dict(std=rng.uniform(self.std[0], self.std[1], 3))
 
 
-INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur)
-_BUILT = "RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, OneOf of the last three, RescaleIntensity (at most one)"
+class RandomMotion:
+    """tio.RandomMotion(degrees=10, translation=10, num_transforms=2, image_interpolation='linear', p=1): k-space compositing of the volume
+    with num_transforms rigidly moved copies (`motion_tables`, `csrc/motion.hip`).  Draws: degrees [K][3], translation [K][3] (voxels: the
+    reference's arrays have spacing 1), then K perturbations ~ U(-0.3 step, 0.3 step) of the times step (1..K), step = 1 / (K + 1).  The
+    movements follow `affine_matrix` (this module's axis conventions, about the image centre) and are not demeaned."""
+
+    def __init__(self, degrees=10, translation=10, num_transforms: int = 2, image_interpolation: str = "linear", p: float = 1.0):
+        if image_interpolation != "linear":
+            raise NotImplementedError("RandomMotion: only image_interpolation='linear' is built")
+        if not 1 <= int(num_transforms) <= ops.MOTION_MAX_TRANSFORMS:
+            raise NotImplementedError(f"RandomMotion: num_transforms 1..{ops.MOTION_MAX_TRANSFORMS} are built")
+        self.degrees, self.translation = _pair(degrees, "degrees"), _pair(translation, "translation")
+        self.num_transforms, self.p = int(num_transforms), float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        K = self.num_transforms
+        degrees = rng.uniform(self.degrees[0], self.degrees[1], (K, 3))
+        translation = rng.uniform(self.translation[0], self.translation[1], (K, 3))
+        step = 1.0 / (K + 1)
+        times = step * np.arange(1, K + 1) + rng.uniform(-0.3 * step, 0.3 * step, K)
+        return "RandomMotion", dict(degrees=degrees, translation=translation, times=times)
+
+
+INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion)
+_BUILT = ("RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, RandomMotion, OneOf of the last four, "
+          "RescaleIntensity (at most one)")
 
 
 class OneOf:
@@ -217,7 +247,7 @@ class OneOf:
             raise ValueError("OneOf: at least one transform")
         for t, w in items:
             if not isinstance(t, INTENSITY_TRANSFORMS):
-                raise NotImplementedError(f"OneOf: {type(t).__name__} is not built on the device ({_BUILT}; RandomMotion is not built)")
+                raise NotImplementedError(f"OneOf: {type(t).__name__} is not built on the device ({_BUILT})")
             if w < 0:
                 raise ValueError("OneOf: weights are non-negative")
         total = float(sum(w for _, w in items))
@@ -261,6 +291,32 @@ def bias_coefficients(coefficients, order: int, to_order: int) -> np.ndarray:
     return np.array([have.get(t, 0.0) for t in bias_terms(to_order)], dtype=np.float64)
 
 
+def motion_tables(times, W: int):
+    """Host half of `ops.motion_artifact` for sorted times [B][K] in (0, 1): (ctab float32 [B][K+1][W], src int64 [B][K+1]).  torchio fills
+    the shifted spectrum along the last axis in K+1 slabs [e_j, e_j+1), e = [0, int(W t_1), .., int(W t_K), W]; slab j comes from image
+    src[j], where src is [0, 1, .., K] (0 = the unmoved volume) with entries 0 and i swapped, i = the first index with t_i > 0.5 or K if
+    there is none (its sort_spectra: the unmoved volume fills the centre of k-space).  Row s of ctab is the real circular convolution kernel
+    that slab stands for, c_s[m] = (1/W) sum_{j in the slab of s} cos(2 pi (j - W//2) m / W), in float64 and then rounded; the rows sum to
+    the unit impulse."""
+    t = np.asarray(times, dtype=np.float64)
+    t = t.reshape(1, -1) if t.ndim == 1 else t
+    B, K = t.shape
+    W = int(W)
+    ctab, src = np.zeros((B, K + 1, W), dtype=np.float32), np.zeros((B, K + 1), dtype=np.int64)
+    m = np.arange(W, dtype=np.float64)
+    for b in range(B):
+        edges = [0] + [int(W * v) for v in t[b]] + [W]
+        order = list(range(K + 1))
+        late = np.nonzero(t[b] > 0.5)[0]
+        i = int(late[0]) if len(late) else K
+        order[0], order[i] = order[i], order[0]
+        for j, s in enumerate(order):
+            freq = np.arange(edges[j], edges[j + 1], dtype=np.float64) - W // 2
+            ctab[b, s] = np.cos(2.0 * np.pi * freq[:, None] * m[None, :] / W).sum(axis=0) / W
+        src[b] = order
+    return ctab, src
+
+
 class DeviceCompose:
     """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Spatial transforms are merged
     into one resampling pass (affine first, flips on its output), the intensity transforms (singly or inside OneOf) follow in listed
@@ -274,7 +330,7 @@ class DeviceCompose:
         self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS + (OneOf,))]
         if len(self.affine) > 1 or len(self.rescale) > 1 or \
                 len(self.affine) + len(self.flips) + len(self.rescale) + len(self.intensity) != len(transforms):
-            raise NotImplementedError(f"DeviceCompose: {_BUILT}; RandomMotion and anything else are not built")
+            raise NotImplementedError(f"DeviceCompose: {_BUILT}; anything else is not built")
         self.rng = np.random.default_rng(seed)
         self.last_params = None                                           # [(flip bits, affine params or None)] of the last call: tests, logging
         # the intensity draws of the last call, one entry per sample: None or (class name, params) -- with several intensity transforms
@@ -301,8 +357,8 @@ class DeviceCompose:
         return mats, flags
 
     def _intensity_stage(self, x: torch.Tensor, draws) -> torch.Tensor:
-        """One listed intensity transform on the batch: draws[b] = None or (name, params).  At most one pointwise and one blur launch, each
-        only when a sample drew it; samples that drew nothing ride along as copies."""
+        """One listed intensity transform on the batch: draws[b] = None or (name, params).  At most one pointwise, one blur and one motion
+        launch, each only when a sample drew it; samples that drew nothing ride along as copies."""
         B, dev = x.shape[0], x.device
         names = [d[0] if d else None for d in draws]
         if "RandomNoise" in names or "RandomBiasField" in names:
@@ -327,6 +383,22 @@ class DeviceCompose:
             weights, radius = blur_tables(sig)
             y, scratch = torch.empty_like(x), torch.empty_like(x)
             ops.gaussian_blur3d(x, y, scratch, torch.from_numpy(weights).to(dev), torch.from_numpy(radius).to(dev), int(radius.max()))
+            x = y
+        if "RandomMotion" in names:
+            shape, W = tuple(x.shape[-3:]), x.shape[-1]
+            K = max(len(d[1]["times"]) for d in draws if d and d[0] == "RandomMotion")
+            mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, K, 1, 1))
+            ctab, live = np.zeros((B, K + 1, W), dtype=np.float32), np.zeros(B, dtype=np.int32)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomMotion":
+                    k = len(d[1]["times"])                                 # fewer movements than the launch's: the other rows stay zero
+                    ctab[b, :k + 1], live[b] = motion_tables(d[1]["times"], W)[0][0], 1
+                    for j in range(k):
+                        mats[b, j] = affine_matrix((1, 1, 1), d[1]["degrees"][j], d[1]["translation"][j], shape).astype(np.float32)
+            part = ops.minmax_partials(B, dev)
+            ops.volume_minmax(x, part)                                    # pad value of the movements = this stage's input minimum
+            y = torch.empty_like(x)
+            ops.motion_artifact(x, y, torch.from_numpy(mats).to(dev), torch.from_numpy(ctab).to(dev), torch.from_numpy(live).to(dev), part, K)
             x = y
         return x
 
@@ -354,12 +426,18 @@ class DeviceCompose:
         return x
 
 
-def train_transforms(seed: Optional[int] = None, intensity: bool = False) -> DeviceCompose:
+def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False) -> DeviceCompose:
     """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
-    line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device: the
-    reference's dict minus RandomMotion (not built), its 0.25 weight redistributed over the other three."""
+    line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device, with
+    the three members this package had first (RandomMotion's 0.25 spread over them); motion=True as well makes it the reference's dict
+    as declared, four members at 0.25."""
+    if motion and not intensity:
+        raise ValueError("train_transforms: motion=True adds RandomMotion to the intensity group and needs intensity=True")
     spatial = [RandomAffine(degrees=15, p=0.5), RandomFlip(axes=(0,), flip_probability=0.5)]
-    one_of = [OneOf({RandomNoise(): 1, RandomBiasField(): 1, RandomBlur(std=(0, 1.5)): 1}, p=0.75)] if intensity else []
+    group = {RandomNoise(): 1, RandomBiasField(): 1, RandomBlur(std=(0, 1.5)): 1}
+    if motion:
+        group = {RandomNoise(): 0.25, RandomBiasField(): 0.25, RandomBlur(std=(0, 1.5)): 0.25, RandomMotion(): 0.25}
+    one_of = [OneOf(group, p=0.75)] if intensity else []
     return DeviceCompose(spatial + one_of + [RescaleIntensity((0, 1))], seed)
 
 
@@ -371,12 +449,14 @@ def eval_transforms() -> DeviceCompose:
 class DataPreprocessor:
     """train.py:33-78: same CSV columns (`subset`, `mri_path`, `kl_grade`), same loaders and return tuple; the transforms are the
     device-side `train_transforms` / `val_transforms` attributes to call on each batch after `.to(device)`.  config['data']['intensity_augment']
-    (default False) adds the intensity OneOf of `train_transforms(intensity=True)`."""
+    (default False) adds the intensity OneOf of `train_transforms(intensity=True)`, config['data']['motion_augment'] (default False)
+    RandomMotion to it (`motion=True`)."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
         intensity = bool(config["data"].get("intensity_augment", False))
-        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity), eval_transforms(), eval_transforms()
+        motion = bool(config["data"].get("motion_augment", False))
+        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity, motion), eval_transforms(), eval_transforms()
 
     def preprocess(self, df=None):
         import pandas as pd

@@ -1186,6 +1186,27 @@ def intensity_pointwise(x, y, kind, noise, seeds, coeff, order=3) -> None:
                                              L.stream_ptr()), "gvk_intensity_pointwise")
 
 
+MOTION_MAX_TRANSFORMS, MOTION_MAX_W = 4, 256                             # GVK_MOTION_MAX_TRANSFORMS, GVK_MOTION_MAX_W
+
+
+def motion_artifact(x, out, mats, ctab, live, partials, K) -> None:
+    """tio.RandomMotion in one fused pass: out[b] = sum over the K+1 images (x[b] and x[b] resampled through mats f32 [B][K][12], the maps of
+    `data.affine_matrix`) of the circular convolution along the last axis with ctab f32 [B][K+1][W] (data.motion_tables).  live i32 [B]: a
+    sample with 0 is copied bit for bit; partials = volume_minmax of x (the pad value).  out must not overlap x."""
+    _chk(x, torch.float32, "motion_artifact in")
+    _chk(out, torch.float32, "motion_artifact out", x.numel())
+    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != B * D * H * W:
+        raise L.GavikoHipError("motion_artifact in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    K = int(K)
+    _chk(mats, torch.float32, "motion_artifact mats", 12 * max(K, 0) * B)
+    _chk(ctab, torch.float32, "motion_artifact ctab", (max(K, 0) + 1) * W * B)
+    _chk(live, torch.int32, "motion_artifact live", B)
+    _chk(partials, torch.float32, "motion_artifact partials", B * L.load().gvk_minmax_partials())
+    L.check(L.load().gvk_motion_artifact(L.ptr(x), L.ptr(out), L.ptr(mats), L.ptr(ctab), L.ptr(live), L.ptr(partials), K, B, D, H, W, L.stream_ptr()),
+            "gvk_motion_artifact")
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

@@ -651,7 +651,7 @@ int gvk_spatial_transform(const float* in, float* out, const float* mats, const 
 int gvk_eval_rows(const float* logits, const void* target, float* proba, int32_t* pred, void* confusion, int N, int K, void* stream);
 int gvk_ovr_auc_counts(const float* proba, const void* target, void* counts, int N, int K, void* stream);
 
-/* ---- intensity augmentation (csrc/intensity.hip): the intensity group of train.py:43-48 minus RandomMotion --------------------
+/* ---- intensity augmentation (csrc/intensity.hip): the intensity group of train.py:43-48 (RandomMotion: next section) ---------
  * Volumes are float32 [B][D][H][W], one channel, resident in HBM; every table below is a DEVICE array with one row per sample, so one
  * launch serves a batch in which each sample drew a different transform or none.  Parity with torchio itself is unpinned.
  * gvk_gaussian_blur3d: tio.RandomBlur = scipy.ndimage.gaussian_filter(x, sigma=(s0, s1, s2)) with scipy's defaults: mode='reflect' (any
@@ -672,6 +672,22 @@ int gvk_gaussian_blur3d(const float* in, float* out, float* scratch, const float
                         int W, void* stream);
 int gvk_intensity_pointwise(const float* x, float* y, const int32_t* kind, const float* noise, const void* seeds, const float* coeff, int order, int B,
                             int D, int H, int W, void* stream);
+
+/* ---- tio.RandomMotion (csrc/motion.hip): the fourth member of that group, k-space motion ghosting, in one fused pass -------------
+ * torchio composites the shifted 3-D spectra of the volume and of K rigidly moved copies in K+1 slabs along the LAST array axis.  The slab
+ * masks do not depend on the other two frequency axes, so the transforms over D and H cancel and a real circular convolution along W is
+ * left per image -- no FFT:  out[b][d][h][w] = sum_{s=0..K} sum_{w'} ctab[b][s][(w - w') mod W] * img_s[b][d][h][w'],
+ * img_0 = in[b], img_k = in[b] resampled through mats[b][k-1] (row-major 3x4, output voxel -> input position, exactly the arithmetic and
+ * pad rule of gvk_spatial_transform with the affine live: trilinear, neighbours outside read the volume minimum taken from partials =
+ * gvk_volume_minmax of in).  ctab [B][K+1][W] is built on the host in float64 (data.motion_tables): row s = (1/W) sum over the
+ * frequencies j of the slabs that image s fills of cos(2 pi (j - W/2) m / W), W/2 the integer quotient (W//2, also for odd W); the rows sum to the unit impulse.  The moved images never
+ * reach HBM: a workgroup gathers 32 (d, h) lines of one image into LDS and multiplies them by the circulant of its ctab row on the f32-input
+ * matrix cores (fp32 operands, fp32 accumulation, a fixed order: the same bits on every run), image after image into the same accumulators.
+ * live [B]: a sample with live[b] == 0 is copied, bit for bit.  K in 1..GVK_MOTION_MAX_TRANSFORMS, W in 2..GVK_MOTION_MAX_W, in and out must
+ * not overlap; no divisibility or alignment requirement on D, H, W. */
+enum { GVK_MOTION_MAX_TRANSFORMS = 4, GVK_MOTION_MAX_W = 256 };
+int gvk_motion_artifact(const float* in, float* out, const float* mats, const float* ctab, const int32_t* live, const float* partials, int K, int B,
+                        int D, int H, int W, void* stream);
 
 /* ---- nn.Dropout as its own pass (sites without a producing kernel to fuse into) ------------------------------------------
  * Replaces vision_transformer.py:157 (emb_dropout), vpt.py:129,148,152 (prompt_dropout) and carries the masks of the
