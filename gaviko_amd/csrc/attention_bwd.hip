@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
   int bh, kblk;
   xcd_group_block(blockIdx.x, (T + 127) / 128, gridDim.x / ((T + 127) / 128), bh, kblk);   // all key blocks of a (batch, head) on one XCD
   const int b = bh / H, head = bh - b * H, k0 = kblk * 128;
-  if (k0 >= need_rows) return;                     // (gvk_attention_bwd_bf16_rows: dk, dv of the first need_rows tokens only -- the whole workgroup leaves)
+  if (k0 >= need_rows) return;                     // (gvk_attention_desc.need_rows: dk, dv of the first need_rows tokens only -- the whole workgroup leaves)
   const int lane = lane_id(), wave = wave_id();
   const int r31 = lane & 31, hh = lane >> 5;
   const int inner = H * 64;
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16* __restr
   }
   del = half_sum(del);                                    // the two half-waves hold the two halves of the 64-wide row
   if (hh == 0 && q < T) delta[((size_t)b * H + head) * T + q] = del;
-  if (q0 >= need_rows) return;                            // (gvk_attention_bwd_bf16_rows: delta of every row, dq of the first need_rows tokens only)
+  if (q0 >= need_rows) return;                            // (gvk_attention_desc.need_rows: delta of every row, dq of the first need_rows tokens only)
   [[maybe_unused]] unsigned int akey = 0u, qoff = 0u;
   if constexpr (DROP) {
     akey = attn_key(dr.seed + *dr.seed_ptr, b * H + head);
@@ -807,8 +807,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused_kernel(const bf16* __re
 }
 
 template <int KB, bool DROP>
-static int launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int T, int H,
-                           int ld_qkv, int ld_out, float scale, AttnDrop dr, hipStream_t s, int need_rows = 1 << 30) {
+static int launch_attn_bwd(const gvk_attention_desc& d, hipStream_t s) {
+  const int B = d.B, T = d.T, H = d.H;
+  const AttnDrop dr = attn_drop(d);
+  const int need_rows = d.need_rows > 0 ? d.need_rows : 1 << 30;      // 0: all rows
   const float dk_scale = 0.69314718055994530942f;      // dK = scale . dS^T.Q = dS^T.Q' / log2(e)
   const dim3 grid(((T + 127) / 128) * H * B);
   constexpr unsigned lds_kv = 2 * (2 * KB * 128 + 2 * 128 * 4), lds_q = 2 * 2 * KB * 128;
@@ -819,38 +821,16 @@ static int launch_attn_bwd(const void* qkv, const void* out, const void* dout, c
     if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(attn_bwd): %s", hipGetErrorString(e));
     attr = true;
   }
-  GVK_LAUNCH((attn_bwd_dq_kernel<KB, DROP>), grid, dim3(256), lds_q, s, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, T, H,
-             ld_qkv, ld_out, scale, dr, need_rows);
+  GVK_LAUNCH((attn_bwd_dq_kernel<KB, DROP>), grid, dim3(256), lds_q, s, (const bf16*)d.qkv, (const bf16*)d.out, (const bf16*)d.dout, (const float*)d.lse,
+             (float*)d.delta, (bf16*)d.dqkv, T, H, d.ld_qkv, d.ld_out, d.scale, dr, need_rows);
   int rc = check_launch("attention_bwd/dq");
   if (rc) return rc;
-  GVK_LAUNCH((attn_bwd_dkdv_kernel<KB, DROP>), grid, dim3(256), lds_kv, s, (const bf16*)qkv, (const bf16*)dout, lse, (const float*)delta, (bf16*)dqkv, T, H,
-             ld_qkv, ld_out, dk_scale, dr, need_rows);
+  GVK_LAUNCH((attn_bwd_dkdv_kernel<KB, DROP>), grid, dim3(256), lds_kv, s, (const bf16*)d.qkv, (const bf16*)d.dout, (const float*)d.lse,
+             (const float*)d.delta, (bf16*)d.dqkv, T, H, d.ld_qkv, d.ld_out, dk_scale, dr, need_rows);
   return check_launch("attention_bwd/dkdv");
 }
 
 }  // namespace gvk
-
-extern "C" int gvk_attention_bwd_bf16_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                                              int T, int H, int ld_qkv, int ld_out, float scale, float drop_p, uint64_t seed, const void* seed_ptr,
-                                              void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv, "gvk_attention_bwd_bf16: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_bwd_bf16: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 8 == 0 && ld_out >= H * 64 && ld_out % 8 == 0,
-              "gvk_attention_bwd_bf16: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_bwd_bf16: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_bwd_bf16: the dropout mask index (query*T + key) is 32-bit");
-  GVK_REQUIRE((int64_t)B * T * ld_qkv * 2 < (int64_t)1 << 31, "gvk_attention_bwd_bf16: the qkv tensor must stay below 2 GiB (32-bit buffer offsets)");
-  const AttnDrop dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  hipStream_t s = (hipStream_t)stream;
-  // tile of 96 rows when it pads the sequence less than 128 does (T = 1033: 1056 against 1152)
-  int kb = ((T + 95) / 96 * 96 < (T + 127) / 128 * 128) ? 96 : 128;
-  if (getenv("GAVIKO_HIP_ATTN_KB") && (atoi(getenv("GAVIKO_HIP_ATTN_KB")) == 96 || atoi(getenv("GAVIKO_HIP_ATTN_KB")) == 128)) kb = atoi(getenv("GAVIKO_HIP_ATTN_KB"));
-  if (drop_p > 0.f)      // the dropout variants carry the mask arithmetic: 96-row tiles only (the 128-row form would spill registers)
-    return launch_attn_bwd<96, true>(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, dr, s);
-  return kb == 96 ? launch_attn_bwd<96, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, dr, s)
-                  : launch_attn_bwd<128, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, dr, s);
-}
 
 // workspace of the one-pass backward: [progress words: cap lines of 128 B, one word each | XCD table: cap int32, together padded to 256 B | status word, 256 B | running
 // dQ sums: cap slabs of 8 KB].
@@ -867,21 +847,16 @@ extern "C" size_t gvk_attention_bwd_ws_bytes(int B, int T, int H) {
 }
 extern "C" size_t gvk_attention_bwd_status_offset(size_t ws_bytes) { return fused_status_off(ws_bytes); }
 
-extern "C" int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, void* ws,
-                                            size_t ws_bytes, int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream) {
+// the one-pass backward of a validated bf16 descriptor with a workspace
+static int launch_attn_bwd_fused(const gvk_attention_desc& d, hipStream_t s) {
   using namespace gvk;
-  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv && ws, "gvk_attention_bwd_bf16_fused: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_bwd_bf16_fused: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 8 == 0 && ld_out >= H * 64 && ld_out % 8 == 0,
-              "gvk_attention_bwd_bf16_fused: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
-  GVK_REQUIRE((int64_t)B * T * ld_qkv * 2 < (int64_t)1 << 31, "gvk_attention_bwd_bf16_fused: the qkv tensor must stay below 2 GiB (32-bit buffer offsets)");
-  const size_t need = gvk_attention_bwd_ws_bytes(B, T, H);
-  GVK_REQUIRE(ws_bytes >= need && ((uintptr_t)ws & 255) == 0, "gvk_attention_bwd_bf16_fused: workspace of %zu bytes (256-byte aligned) needed, %zu given", need, ws_bytes);
-  GVK_REQUIRE(fused_ws_cap(ws_bytes) >= fused_slabs(B, T, H), "gvk_attention_bwd_bf16_fused: workspace layout cannot hold %zu slabs", fused_slabs(B, T, H));
+  const int B = d.B, T = d.T, H = d.H;
+  const size_t ws_bytes = d.ws_bytes, need = gvk_attention_bwd_ws_bytes(B, T, H);
+  GVK_REQUIRE(ws_bytes >= need && ((uintptr_t)d.ws & 255) == 0, "gvk_attention_bwd: workspace of %zu bytes (256-byte aligned) needed, %zu given", need, ws_bytes);
+  GVK_REQUIRE(fused_ws_cap(ws_bytes) >= fused_slabs(B, T, H), "gvk_attention_bwd: workspace layout cannot hold %zu slabs", fused_slabs(B, T, H));
   const size_t off_status = fused_status_off(ws_bytes), off_acc = off_status + 256;
   const size_t nsub = (size_t)((T + kFusedQT - 1) / kFusedQT) * (kFusedQT / 32);
-  GVK_REQUIRE(nsub * 8192 < ((size_t)1 << 31) && (T + 127) / 128 <= 256, "gvk_attention_bwd_bf16_fused: sequence too long (32-bit slab offsets, 256 key blocks)");
-  hipStream_t s = (hipStream_t)stream;
+  GVK_REQUIRE(nsub * 8192 < ((size_t)1 << 31) && (T + 127) / 128 <= 256, "gvk_attention_bwd: sequence too long (32-bit slab offsets, 256 key blocks)");
   constexpr unsigned lds = 2 * (2 * kFusedQT * 128 + 2 * 128 * 4) + 2 * (kFusedQT / 32) * 128 * 64 + 1024;
   static bool attr = false;
   if (!attr) {
@@ -897,15 +872,16 @@ extern "C" int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, co
     attr = true;
   }
   const int M = B * T;
-  GVK_LAUNCH(attn_delta_kernel, dim3((unsigned)(((size_t)M * H * 8 + 255) / 256)), dim3(256), 0, s, (const bf16*)out, (const bf16*)dout, delta, M, T, H, ld_out);
+  GVK_LAUNCH(attn_delta_kernel, dim3((unsigned)(((size_t)M * H * 8 + 255) / 256)), dim3(256), 0, s, (const bf16*)d.out, (const bf16*)d.dout, (float*)d.delta, M, T, H, d.ld_out);
   int rc = check_launch("attention_bwd/delta");
   if (rc) return rc;
   const float dk_scale = 0.69314718055994530942f;      // dK = scale . dS^T.Q = dS^T.Q' / log2(e)
-  char* w = (char*)ws;
+  char* w = (char*)d.ws;
   const dim3 grid(((T + 127) / 128) * H * B);
 #define GVK_FUSED(V)                                                                                                                          \
-  GVK_LAUNCH((attn_bwd_fused_kernel<kFusedQT, V>), grid, dim3(256), lds, s, (const bf16*)qkv, (const bf16*)dout, lse, (const float*)delta, \
-             (bf16*)dqkv, (float*)(w + off_acc), (int*)w, (int*)w + fused_ws_cap(ws_bytes) * 32, (int*)(w + off_status), T, H, ld_qkv, ld_out, scale, dk_scale)
+  GVK_LAUNCH((attn_bwd_fused_kernel<kFusedQT, V>), grid, dim3(256), lds, s, (const bf16*)d.qkv, (const bf16*)d.dout, (const float*)d.lse,   \
+             (const float*)d.delta, (bf16*)d.dqkv, (float*)(w + off_acc), (int*)w, (int*)w + fused_ws_cap(ws_bytes) * 32, (int*)(w + off_status), T, H,  \
+             d.ld_qkv, d.ld_out, d.scale, dk_scale)
 #ifdef GVK_DIAG
   const int var = diag_env("GAVIKO_HIP_ATTN_VAR") ? atoi(diag_env("GAVIKO_HIP_ATTN_VAR")) : 0;      // timing ablations (wrong results)
   if (var == 1) GVK_FUSED(1); else if (var == 3) GVK_FUSED(3); else if (var == 7) GVK_FUSED(7); else if (var == 8) GVK_FUSED(8);
@@ -916,21 +892,12 @@ extern "C" int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, co
   return check_launch("attention_bwd/fused");
 }
 
-extern "C" int gvk_attention_bwd_bf16_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                                           int T, int H, int ld_qkv, int ld_out, float scale, int need_rows, void* stream) {
+extern "C" int gvk_attention_bwd(const gvk_attention_desc* d, void* stream) {
   using namespace gvk;
-  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv, "gvk_attention_bwd_bf16_rows: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0 && need_rows > 0, "gvk_attention_bwd_bf16_rows: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 8 == 0 && ld_out >= H * 64 && ld_out % 8 == 0,
-              "gvk_attention_bwd_bf16_rows: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
-  GVK_REQUIRE((int64_t)B * T * ld_qkv * 2 < (int64_t)1 << 31, "gvk_attention_bwd_bf16_rows: the qkv tensor must stay below 2 GiB (32-bit buffer offsets)");
-  const AttnDrop dr{0, nullptr, 0u, 1.f};
-  const int kb = ((T + 95) / 96 * 96 < (T + 127) / 128 * 128) ? 96 : 128;        // the same tile choice as gvk_attention_bwd_bf16: the same bits
-  return kb == 96 ? launch_attn_bwd<96, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, dr, (hipStream_t)stream, need_rows)
-                  : launch_attn_bwd<128, false>(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, dr, (hipStream_t)stream, need_rows);
-}
-
-extern "C" int gvk_attention_bwd_bf16(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                                      int T, int H, int ld_qkv, int ld_out, float scale, void* stream) {
-  return gvk_attention_bwd_bf16_dropout(qkv, out, dout, lse, delta, dqkv, B, T, H, ld_qkv, ld_out, scale, 0.f, 0, nullptr, stream);
+  if (int rc = attn_validate(d, true, "gvk_attention_bwd")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (d->f32) return launch_attn_bwd_f32(*d, s);
+  if (d->ws) return launch_attn_bwd_fused(*d, s);
+  if (d->drop_p > 0.f) return launch_attn_bwd<96, true>(*d, s);   // the dropout variants carry the mask arithmetic: 96-row tiles only (the 128-row form would spill registers)
+  return attn_key_tile(d->T) == 96 ? launch_attn_bwd<96, false>(*d, s) : launch_attn_bwd<128, false>(*d, s);
 }

@@ -1,7 +1,6 @@
 // Helpers shared by the bf16 flash-attention forward and backward kernels (attention_fwd.hip, attention_bwd.hip).
 #pragma once
-#include "common.hpp"
-#include "dropout.hpp"
+#include "attention_desc.hpp"
 
 namespace gvk {
 
@@ -31,10 +30,6 @@ __device__ __forceinline__ void lds_dma4(__amdgpu_buffer_rsrc_t r, const void* l
 // (s_waitcnt vmcnt(7) ... vmcnt(0) in front of their first uses), where -- blind to the DMA requests -- they drain the prefetch on
 // every iteration.
 #define GVK_LOADS_LANDED() __builtin_amdgcn_s_waitcnt(0x0F70)
-
-// attention-probability dropout (vision_transformer.py:68, live for the unfrozen-backbone methods): the softmax statistics are taken
-// of the undropped scores, the dropped and rescaled P feeds the P.V product; mask element (b*H + head, query, key) -- dropout.hpp
-struct AttnDrop { unsigned long long seed; const unsigned long long* seed_ptr; unsigned int thresh; float inv_keep; };
 
 // Row constants on the matrix pipe.  A score tile needs  S - c[row or column]  (running maximum / log-sum-exp) and a mask; as VALU work
 // that is a v_fma and a v_cndmask per score.  Instead the constant rides an extra MFMA over an "augmented" contraction of 16 slots

@@ -15,14 +15,9 @@
 //     probabilities never move between lanes.
 // Per 32 x 32 block a wave issues 64 (forward), 96 (dQ pass) or 128 (dK / dV pass) MFMAs of 64 cycles each beside ~50 LDS reads and
 // ~100 VALU instructions: the kernels are bound by the matrix pipe.
-#include "common.hpp"
-#include "dropout.hpp"
-#include "../../include/gaviko_hip.h"
+#include "attention_desc.hpp"
 
 namespace gvk {
-
-// attention-probability dropout (thresh = 0: off): same mask function as the bf16 kernels, element (b*H + h, query, key)
-struct AttnDropF { unsigned long long seed; const unsigned long long* seed_ptr; unsigned int thresh; float inv_keep; };
 
 constexpr int kRows = 128;        // rows per workgroup (4 waves x 32)
 constexpr int kTile = 32;         // rows of the streamed operand per LDS tile
@@ -89,7 +84,7 @@ __device__ __forceinline__ float pair_sum(float v) {
 // ---- forward: vision_transformer.py:63-71
 template <bool DROP>
 __global__ __launch_bounds__(2 * kRows) void attn_f32_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
-                                                                 int T, int H, int ld_qkv, int ld_out, float scale, AttnDropF dr) {
+                                                                 int T, int H, int ld_qkv, int ld_out, float scale, AttnDrop dr) {
   __shared__ __attribute__((aligned(16))) float sK[kTile * kLd], sV[kTile * kLd];
   const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kRows;
   const int lane = lane_id(), wave = wave_id(), r31 = lane & 31, hh = lane >> 5;
@@ -148,7 +143,7 @@ template <bool DROP>
 __global__ __launch_bounds__(2 * kRows) void attn_f32_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                                     const float* __restrict__ dout, const float* __restrict__ lse,
                                                                     float* __restrict__ delta, float* __restrict__ dqkv, int T, int H,
-                                                                    int ld_qkv, int ld_out, float scale, AttnDropF dr) {
+                                                                    int ld_qkv, int ld_out, float scale, AttnDrop dr) {
   __shared__ __attribute__((aligned(16))) float sK[kTile * kLd], sV[kTile * kLd];
   const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kRows;
   const int lane = lane_id(), wave = wave_id(), r31 = lane & 31, hh = lane >> 5;
@@ -198,7 +193,7 @@ template <bool DROP>
 __global__ __launch_bounds__(2 * kRows) void attn_f32_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                     const float* __restrict__ lse, const float* __restrict__ delta,
                                                                     float* __restrict__ dqkv, int T, int H, int ld_qkv, int ld_out, float scale,
-                                                                    AttnDropF dr) {
+                                                                    AttnDrop dr) {
   __shared__ __attribute__((aligned(16))) float sQ[kTile * kLd], sD[kTile * kLd];
   __shared__ float sL[kTile], sDl[kTile];
   const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kRows;
@@ -249,42 +244,31 @@ __global__ __launch_bounds__(2 * kRows) void attn_f32_bwd_kv_kernel(const float*
   }
 }
 
-}  // namespace gvk
-
-extern "C" int gvk_attention_fwd_f32_dropout(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                             float drop_p, uint64_t seed, const void* seed_ptr, void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_fwd_f32_dropout: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_fwd_f32_dropout: the dropout mask index (query*T + key) is 32-bit");
-  const AttnDropF dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  GVK_REQUIRE(qkv && out, "gvk_attention_fwd_f32_dropout: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_fwd_f32_dropout: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 4 == 0 && ld_out >= H * 64 && ld_out % 4 == 0,
-              "gvk_attention_fwd_f32_dropout: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
-  const dim3 grid((T + kRows - 1) / kRows, H, B), block(2 * kRows);
-  if (drop_p > 0.f) GVK_LAUNCH((attn_f32_fwd_kernel<true>), grid, block, 0, (hipStream_t)stream, qkv, out, lse, T, H, ld_qkv, ld_out, scale, dr);
-  else GVK_LAUNCH((attn_f32_fwd_kernel<false>), grid, block, 0, (hipStream_t)stream, qkv, out, lse, T, H, ld_qkv, ld_out, scale, dr);
-  return check_launch("attention_fwd_f32_dropout");
+// the fp32 side of gvk_attention_fwd / gvk_attention_bwd (attention_desc.hpp): d is validated and has f32 = 1
+int launch_attn_fwd_f32(const gvk_attention_desc& d, hipStream_t s) {
+  const AttnDrop dr = attn_drop(d);
+  const float* qkv = (const float*)d.qkv;
+  float *out = (float*)d.out, *lse = (float*)d.lse;
+  const dim3 grid((d.T + kRows - 1) / kRows, d.H, d.B), block(2 * kRows);
+  if (d.drop_p > 0.f) GVK_LAUNCH((attn_f32_fwd_kernel<true>), grid, block, 0, s, qkv, out, lse, d.T, d.H, d.ld_qkv, d.ld_out, d.scale, dr);
+  else GVK_LAUNCH((attn_f32_fwd_kernel<false>), grid, block, 0, s, qkv, out, lse, d.T, d.H, d.ld_qkv, d.ld_out, d.scale, dr);
+  return check_launch("attention_fwd_f32");
 }
 
-extern "C" int gvk_attention_bwd_f32_dropout(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
-                                             int B, int T, int H, int ld_qkv, int ld_out, float scale, float drop_p, uint64_t seed,
-                                             const void* seed_ptr, void* stream) {
-  using namespace gvk;
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_bwd_f32_dropout: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_bwd_f32_dropout: the dropout mask index (query*T + key) is 32-bit");
-  const AttnDropF dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  GVK_REQUIRE(qkv && out && dout && lse && delta && dqkv, "gvk_attention_bwd_f32_dropout: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_bwd_f32_dropout: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 4 == 0 && ld_out >= H * 64 && ld_out % 4 == 0,
-              "gvk_attention_bwd_f32_dropout: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d", ld_qkv, ld_out, H);
-  const dim3 grid((T + kRows - 1) / kRows, H, B), block(2 * kRows);
-  hipStream_t s = (hipStream_t)stream;
-  if (drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_dq_kernel<true>), grid, block, 0, s, qkv, out, dout, lse, delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
+int launch_attn_bwd_f32(const gvk_attention_desc& d, hipStream_t s) {
+  const AttnDrop dr = attn_drop(d);
+  const float *qkv = (const float*)d.qkv, *out = (const float*)d.out, *dout = (const float*)d.dout, *lse = (const float*)d.lse;
+  float *delta = (float*)d.delta, *dqkv = (float*)d.dqkv;
+  const int T = d.T, H = d.H, ld_qkv = d.ld_qkv, ld_out = d.ld_out;
+  const float scale = d.scale;
+  const dim3 grid((T + kRows - 1) / kRows, H, d.B), block(2 * kRows);
+  if (d.drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_dq_kernel<true>), grid, block, 0, s, qkv, out, dout, lse, delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
   else GVK_LAUNCH((attn_f32_bwd_dq_kernel<false>), grid, block, 0, s, qkv, out, dout, lse, delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
-  int rc = check_launch("attention_bwd_f32_dropout/dq");
+  int rc = check_launch("attention_bwd_f32/dq");
   if (rc) return rc;
-  if (drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_kv_kernel<true>), grid, block, 0, s, qkv, dout, lse, (const float*)delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
+  if (d.drop_p > 0.f) GVK_LAUNCH((attn_f32_bwd_kv_kernel<true>), grid, block, 0, s, qkv, dout, lse, (const float*)delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
   else GVK_LAUNCH((attn_f32_bwd_kv_kernel<false>), grid, block, 0, s, qkv, dout, lse, (const float*)delta, dqkv, T, H, ld_qkv, ld_out, scale, dr);
-  return check_launch("attention_bwd_f32_dropout/dkdv");
+  return check_launch("attention_bwd_f32/dkdv");
 }
+
+}  // namespace gvk

@@ -288,7 +288,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16* __restrict
 namespace gvk {
 // diagnostics (tools/bench_attn.py): kernel variant forced by the environment; the library default is what launch_attn_fwd picks
 static int attn_var() { return diag_env("GAVIKO_HIP_ATTN_VAR") ? atoi(diag_env("GAVIKO_HIP_ATTN_VAR")) : -1; }   // read per launch: one process can A/B
-static int attn_kb() { return getenv("GAVIKO_HIP_ATTN_KB") ? atoi(getenv("GAVIKO_HIP_ATTN_KB")) : 0; }
 
 template <int KB, bool DROP, int VAR>
 static int launch_attn_fwd_t(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale, AttnDrop dr, hipStream_t stream) {
@@ -314,10 +313,7 @@ constexpr int kAttnVarDefault = 0;
 
 template <bool DROP>
 static int launch_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale, AttnDrop dr, hipStream_t stream) {
-  // key tile: the size that pads the sequence less (T = 1033: 11 x 96 = 1056 against 9 x 128 = 1152); ties go to the larger tile
-  const int p96 = (T + 95) / 96 * 96, p128 = (T + 127) / 128 * 128;
-  int kb = p96 < p128 ? 96 : 128;
-  if (attn_kb() == 96 || attn_kb() == 128) kb = attn_kb();
+  const int kb = attn_key_tile(T);
   if constexpr (DROP) {
     if (kb == 96) return launch_attn_fwd_t<96, true, kAttnVarDefault>(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, dr, stream);
     return launch_attn_fwd_t<128, true, kAttnVarDefault>(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, dr, stream);
@@ -330,7 +326,7 @@ static int launch_attn_fwd(const void* qkv, void* out, float* lse, int B, int T,
     GVK_ATTN_CASE(128, 0) GVK_ATTN_CASE(128, 1) GVK_ATTN_CASE(128, 2) GVK_ATTN_CASE(128, 3)
 #endif
 #undef GVK_ATTN_CASE
-    return set_error(-2, "gvk_attention_fwd_bf16: no kernel variant %d for key tile %d", var, kb);
+    return set_error(-2, "gvk_attention_fwd: no kernel variant %d for key tile %d", var, kb);
   }
 }
 }  // namespace gvk
@@ -359,22 +355,11 @@ extern "C" int gvk_qkv_prescale_bf16(void* qkv, int rows, int H, int ld_qkv, flo
   return check_launch("qkv_prescale_bf16");
 }
 
-extern "C" int gvk_attention_fwd_bf16_dropout(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                              float drop_p, uint64_t seed, const void* seed_ptr, void* stream) {
+extern "C" int gvk_attention_fwd(const gvk_attention_desc* d, void* stream) {
   using namespace gvk;
-  GVK_REQUIRE(qkv && out, "gvk_attention_fwd_bf16: null pointer");
-  GVK_REQUIRE(B > 0 && T > 0 && H > 0, "gvk_attention_fwd_bf16: empty shape");
-  GVK_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 8 == 0 && ld_out >= H * 64 && ld_out % 8 == 0,
-              "gvk_attention_fwd_bf16: head dim is fixed at 64; ld_qkv=%d ld_out=%d inconsistent with H=%d (16-byte rows)", ld_qkv, ld_out, H);
-  GVK_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed_ptr != nullptr), "gvk_attention_fwd_bf16: drop_p in [0,1) and a seed word");
-  GVK_REQUIRE(drop_p == 0.f || (int64_t)T * T < (int64_t)1 << 32, "gvk_attention_fwd_bf16: the dropout mask index (query*T + key) is 32-bit");
-  GVK_REQUIRE((int64_t)B * T * ld_qkv * 2 < (int64_t)1 << 31, "gvk_attention_fwd_bf16: the qkv tensor must stay below 2 GiB (32-bit buffer offsets)");
-  const AttnDrop dr{seed, (const unsigned long long*)seed_ptr, drop_threshold_u32(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
-  if (drop_p > 0.f) return launch_attn_fwd<true>(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, dr, (hipStream_t)stream);
-  return launch_attn_fwd<false>(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, dr, (hipStream_t)stream);
-}
-
-extern "C" int gvk_attention_fwd_bf16(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                      void* stream) {
-  return gvk_attention_fwd_bf16_dropout(qkv, out, lse, B, T, H, ld_qkv, ld_out, scale, 0.f, 0, nullptr, stream);
+  if (int rc = attn_validate(d, false, "gvk_attention_fwd")) return rc;
+  if (d->f32) return launch_attn_fwd_f32(*d, (hipStream_t)stream);
+  const AttnDrop dr = attn_drop(*d);
+  if (d->drop_p > 0.f) return launch_attn_fwd<true>(d->qkv, d->out, (float*)d->lse, d->B, d->T, d->H, d->ld_qkv, d->ld_out, d->scale, dr, (hipStream_t)stream);
+  return launch_attn_fwd<false>(d->qkv, d->out, (float*)d->lse, d->B, d->T, d->H, d->ld_qkv, d->ld_out, d->scale, dr, (hipStream_t)stream);
 }

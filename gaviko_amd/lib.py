@@ -26,7 +26,7 @@ if os.environ.get("GPU_MAX_HW_QUEUES") is None:
     except Exception:
         pass
 
-ABI_VERSION = 13                                  # gvk_abi_version() of the library these declarations describe
+ABI_VERSION = 14                                  # gvk_abi_version() of the library these declarations describe
 # GAVIKO_HIP_DIAG=1 (tools/ only): load the measurement build libgaviko_hip_diag.so (`python -m gaviko_amd.build --diag`) -- the product
 # library ignores every A/B switch of the kernel sources and exports no diagnostics (include/gaviko_hip_diag.h)
 DIAG = os.environ.get("GAVIKO_HIP_DIAG", "0") == "1"
@@ -89,6 +89,8 @@ DropoutDesc = _struct("DropoutDesc", ["x", "out32", "out16", "seed_ptr"], ["M", 
 RowProjDesc = _struct("RowProjDesc", ["w", "bias", "y", "z", "y_split"], ["L", "w_layout", "act", "ld_split", "col_split"])
 LnBwdDesc = _struct("LnBwdDesc", ["dy", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
                     ["M", "C", "groups", "rows_per_group", "group_stride", "dy_bf16"])
+AttentionDesc = _struct("AttentionDesc", ["qkv", "out", "lse", "dout", "delta", "dqkv", "seed_ptr", "ws"],
+                        ["B", "T", "H", "ld_qkv", "ld_out", "f32", "need_rows"], ["scale", "drop_p"], ["seed", "ws_bytes"])
 ReduceJob = _struct("ReduceJob", ["a", "b", "out", "a2"], ["M", "J", "L", "accumulate", "M2"])
 PgradOuter = _struct("PgradOuter", ["narrow", "wide", "narrow2", "wide2", "lat_override", "mean", "rstd", "out", "colsum",
                                     "aff_w", "aff_gamma", "aff_beta", "aff_dgamma", "aff_dbeta", "aff_dbias"],
@@ -122,12 +124,10 @@ SIGNATURES = {
     "gvk_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "gvk_layernorm_bwd": [C.POINTER(LnBwdDesc), _P],
     "gvk_layernorm_bwd_affine": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "gvk_attention_fwd_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "gvk_attention_fwd": [C.POINTER(AttentionDesc), _P],
+    "gvk_attention_bwd": [C.POINTER(AttentionDesc), _P],
     "gvk_qkv_prescale_bf16": [_P, _I, _I, _I, _F, _P],
     "gvk_prompt_up_fix_stats": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "gvk_attention_bwd_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "gvk_attention_bwd_bf16_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "gvk_attention_bwd_bf16_fused": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _F, _P],
     "gvk_attention_colsum_bf16": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "gvk_rollout_step": [_P, _P, _P, _I, _I, _I, _P],
     "gvk_attention_gradcolsum_bf16": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -136,10 +136,6 @@ SIGNATURES = {
     "gvk_patch_reduce_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_evp_highpass_sign": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_evp_highpass_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "gvk_attention_fwd_f32_dropout": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
-    "gvk_attention_bwd_f32_dropout": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
-    "gvk_attention_fwd_bf16_dropout": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
-    "gvk_attention_bwd_bf16_dropout": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P, _P],
     "gvk_skinny_down": [C.POINTER(SkinnyDownDesc), _P],
     "gvk_skinny_up": [C.POINTER(SkinnyUpDesc), _P],
     "gvk_outer_reduce": [C.POINTER(OuterDesc), _P],
@@ -224,7 +220,7 @@ NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, [
              "gvk_plan_set_timing": (C.c_int, [C.c_int]),
              "gvk_plan_event_elapsed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)])}
 STRUCTS = {"gvk_gemm_desc": GemmDesc, "gvk_skinny_down_desc": SkinnyDownDesc, "gvk_skinny_up_desc": SkinnyUpDesc,
-           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
+           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_attention_desc": AttentionDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
            "gvk_feature_topk_desc": FeatureTopkDesc}
 
 # diag library only (include/gaviko_hip_diag.h): bound when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so

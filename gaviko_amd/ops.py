@@ -508,7 +508,7 @@ LOG2E = 1.4426950408889634
 
 
 def qkv_prescale(qkv, rows, H, scale):
-    """In place: q block of a raw bf16 to_qkv output -> q * scale * log2(e), the form gvk_attention_*_bf16 take (the engine gets it from the
+    """In place: q block of a raw bf16 to_qkv output -> q * scale * log2(e), the form the bf16 attention kernels take (the engine gets it from the
     qkv projection's epilogue instead: gemm_nt(scale_cols=H*64, col_scale=scale*LOG2E))."""
     _chk(qkv, torch.bfloat16, "qkv_prescale qkv", rows * 3 * H * 64)
     L.check(L.load().gvk_qkv_prescale_bf16(L.ptr(qkv), rows, H, qkv.shape[-1], scale, L.stream_ptr()), "gvk_qkv_prescale_bf16")
@@ -524,30 +524,20 @@ def attention_fwd(qkv, out, lse, B, T, H, scale, drop_p=0.0, seed=0, seed_ptr=No
     """qkv bf16 [pad(B*T), 3*H*64] -> out bf16 [pad(B*T), H*64], lse f32 [B,H,T].  drop_p > 0: dropout on the probabilities (bf16 path).
     bf16 path: the kernels take the q block pre-scaled by scale*log2(e) (include/gaviko_hip.h); q_prescaled=False (tests, tools) makes a
     scaled copy of a raw qkv first -- an allocation and one more rounding of q, never on the engine's path."""
-    inner = H * 64
-    if qkv.dtype == torch.float32:
-        _chk(qkv, torch.float32, "attn qkv", B * T * 3 * inner)
-        _chk(out, torch.float32, "attn out", B * T * inner)
-        _chk(lse, torch.float32, "attn lse", B * H * T)
-        L.check(L.load().gvk_attention_fwd_f32_dropout(L.ptr(qkv), L.ptr(out), L.ptr(lse), B, T, H, 3 * inner, inner, scale, float(drop_p), int(seed),
-                                                       L.ptr(seed_ptr) if drop_p > 0 else None, L.stream_ptr()), "gvk_attention_fwd_f32_dropout")
-        return
-    _chk(qkv, torch.bfloat16, "attn qkv", pad_rows(B * T) * 3 * inner)
-    _chk(out, torch.bfloat16, "attn out", B * T * inner)
-    _chk(lse, torch.float32, "attn lse", B * H * T)
-    if not q_prescaled:
+    inner, f32, drop = H * 64, qkv.dtype == torch.float32, drop_p > 0
+    dt, rows = (torch.float32, B * T) if f32 else (torch.bfloat16, pad_rows(B * T))
+    for t, n, dtype, elems in ((qkv, "qkv", dt, rows * 3 * inner), (out, "out", dt, B * T * inner), (lse, "lse", torch.float32, B * H * T)):
+        _chk(t, dtype, "attn " + n, elems)
+    if not f32 and not q_prescaled:
         qkv = _prescaled_copy(qkv, B * T, H, scale)
-    if drop_p > 0:
-        L.check(L.load().gvk_attention_fwd_bf16_dropout(L.ptr(qkv), L.ptr(out), L.ptr(lse), B, T, H, 3 * inner, inner, scale, float(drop_p),
-                                                        int(seed), L.ptr(seed_ptr), L.stream_ptr()), "gvk_attention_fwd_bf16_dropout")
-        return
-    L.check(L.load().gvk_attention_fwd_bf16(L.ptr(qkv), L.ptr(out), L.ptr(lse), B, T, H, 3 * inner, inner, scale, L.stream_ptr()),
-            "gvk_attention_fwd_bf16")
+    d = L.AttentionDesc(qkv=L.ptr(qkv), out=L.ptr(out), lse=L.ptr(lse), seed_ptr=L.ptr(seed_ptr) if drop else None, B=B, T=T, H=H,
+                        ld_qkv=3 * inner, ld_out=inner, f32=int(f32), scale=scale, drop_p=float(drop_p), seed=int(seed) if drop else 0)
+    L.check(L.load().gvk_attention_fwd(C.byref(d), L.stream_ptr()), "gvk_attention_fwd")
 
 
 def attention_colsum(qkv, lse, w, out, B, T, H, q0=0, q1=None):
     """out f32 [B,H,T] = sum_{q0 <= i < q1} w[b,i] * P[b,h,i,:] -- the weighted rows of the attention probabilities, recomputed from the
-    bf16 forward's qkv (q block pre-scaled, gvk_attention_fwd_bf16's layout) and lse f32 [B,H,T].  w f32 [B, >= T] (row stride = its last dim)."""
+    bf16 forward's qkv (q block pre-scaled, gvk_attention_desc's layout) and lse f32 [B,H,T].  w f32 [B, >= T] (row stride = its last dim)."""
     q1 = T if q1 is None else q1
     _chk(qkv, torch.bfloat16, "colsum qkv", pad_rows(B * T) * 3 * H * 64)
     _chk(lse, torch.float32, "colsum lse", B * H * T)
@@ -816,7 +806,7 @@ def head_bwd(**kw):
 
 
 def attention_bwd_workspace(B, T, H, device):
-    """Zeroed workspace of the one-pass bf16 backward (gvk_attention_bwd_bf16_fused): progress words + the running dQ sums of the
+    """Zeroed workspace of the one-pass bf16 backward (gvk_attention_desc.ws): progress words + the running dQ sums of the
     ordered hand-off.  One per stream that issues the call (launches sharing it must be ordered)."""
     n = int(L.load().gvk_attention_bwd_ws_bytes(B, T, H))
     return torch.zeros((n + 3) // 4, dtype=torch.int32, device=device)
@@ -828,42 +818,32 @@ def attention_bwd_timeouts(ws) -> int:
 
 
 def attention_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, scale, drop_p=0.0, seed=0, seed_ptr=None, q_prescaled=False, ws=None, need_rows=None):
-    """ws (attention_bwd_workspace): run the one-pass kernel (five products, ordered dQ hand-off); without it, or with attention
-    dropout, the two-pass kernels.  need_rows (bf16, no dropout): gradients of the first need_rows tokens of every sample only."""
-    inner = H * 64
-    if qkv.dtype == torch.float32:
-        for t, n, k in ((qkv, "qkv", 3), (out, "out", 1), (dout, "dout", 1), (dqkv, "dqkv", 3)):
-            _chk(t, torch.float32, "attn_bwd " + n, B * T * k * inner)
-        _chk(lse, torch.float32, "attn_bwd lse", B * H * T)
-        _chk(delta, torch.float32, "attn_bwd delta", B * H * T)
-        L.check(L.load().gvk_attention_bwd_f32_dropout(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, H,
-                                                       3 * inner, inner, scale, float(drop_p), int(seed), L.ptr(seed_ptr) if drop_p > 0 else None,
-                                                       L.stream_ptr()), "gvk_attention_bwd_f32_dropout")
-        return
-    _chk(qkv, torch.bfloat16, "attn_bwd qkv", pad_rows(B * T) * 3 * inner)
-    _chk(out, torch.bfloat16, "attn_bwd out", pad_rows(B * T) * inner)
-    _chk(dout, torch.bfloat16, "attn_bwd dout", pad_rows(B * T) * inner)
-    _chk(dqkv, torch.bfloat16, "attn_bwd dqkv", B * T * 3 * inner)
-    _chk(lse, torch.float32, "attn_bwd lse", B * H * T)
-    _chk(delta, torch.float32, "attn_bwd delta", B * H * T)
-    if not q_prescaled:                                      # see attention_fwd
-        qkv = _prescaled_copy(qkv, B * T, H, scale)
-    if drop_p > 0:
-        L.check(L.load().gvk_attention_bwd_bf16_dropout(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, H,
-                                                        3 * inner, inner, scale, float(drop_p), int(seed), L.ptr(seed_ptr), L.stream_ptr()),
-                "gvk_attention_bwd_bf16_dropout")
-        return
-    if need_rows is not None:
-        L.check(L.load().gvk_attention_bwd_bf16_rows(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, H,
-                                                     3 * inner, inner, scale, int(need_rows), L.stream_ptr()), "gvk_attention_bwd_bf16_rows")
-        return
+    """Gradients [dq | dk | dv] of the unscaled q, k, v into dqkv; delta is scratch.  One form runs per call, by this precedence:
+      fp32 operands:          the plain two-pass kernels -- need_rows and ws are ignored;
+      drop_p > 0:             the two-pass dropout kernels -- need_rows and ws are ignored;
+      need_rows (not None):   the two-pass kernels on the first need_rows tokens of every sample only -- ws is ignored;
+      ws (attention_bwd_workspace): the one-pass kernel (five products, ordered dQ hand-off);
+      otherwise:              the two-pass kernels.
+    The library refuses a descriptor that asks for two of these at once; the engine passes drop_p and need_rows together
+    (_attn_block_bwd), so the choice is made here, once, before the descriptor is filled."""
+    inner, f32, drop = H * 64, qkv.dtype == torch.float32, drop_p > 0
+    need_rows = 0 if f32 or drop or need_rows is None else int(need_rows)
+    if f32 or drop or need_rows:
+        ws = None
+    dt, rows = (torch.float32, B * T) if f32 else (torch.bfloat16, pad_rows(B * T))
+    for t, n, dtype, elems in ((qkv, "qkv", dt, rows * 3 * inner), (out, "out", dt, rows * inner), (dout, "dout", dt, rows * inner),
+                               (dqkv, "dqkv", dt, B * T * 3 * inner), (lse, "lse", torch.float32, B * H * T),
+                               (delta, "delta", torch.float32, B * H * T)):
+        _chk(t, dtype, "attn_bwd " + n, elems)
     if ws is not None:
         _chk(ws, torch.int32, "attn_bwd ws", (int(L.load().gvk_attention_bwd_ws_bytes(B, T, H)) + 3) // 4)
-        L.check(L.load().gvk_attention_bwd_bf16_fused(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), L.ptr(ws),
-                                                      ws.numel() * 4, B, T, H, 3 * inner, inner, scale, L.stream_ptr()), "gvk_attention_bwd_bf16_fused")
-        return
-    L.check(L.load().gvk_attention_bwd_bf16(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dqkv), B, T, H,
-                                            3 * inner, inner, scale, L.stream_ptr()), "gvk_attention_bwd_bf16")
+    if not f32 and not q_prescaled:                          # see attention_fwd
+        qkv = _prescaled_copy(qkv, B * T, H, scale)
+    d = L.AttentionDesc(qkv=L.ptr(qkv), out=L.ptr(out), lse=L.ptr(lse), dout=L.ptr(dout), delta=L.ptr(delta), dqkv=L.ptr(dqkv),
+                        seed_ptr=L.ptr(seed_ptr) if drop else None, ws=L.ptr(ws), B=B, T=T, H=H, ld_qkv=3 * inner, ld_out=inner, f32=int(f32),
+                        need_rows=need_rows, scale=scale, drop_p=float(drop_p), seed=int(seed) if drop else 0,
+                        ws_bytes=ws.numel() * 4 if ws is not None else 0)
+    L.check(L.load().gvk_attention_bwd(C.byref(d), L.stream_ptr()), "gvk_attention_bwd")
 
 
 def small_linear_fwd(x, w, b, out, R, K, C_):

@@ -22,7 +22,7 @@ extern "C" {
 const char* gvk_last_error(void);
 /* returns 950 when the code object loaded on the current device is gfx950, else <0 */
 int gvk_device_check(void);
-int gvk_abi_version(void);   /* 12 */
+int gvk_abi_version(void);   /* 14 */
 
 /* ------------------------------------------------------------------ launch plans
  * The reference drives its step from the Python interpreter (train.py:296-319: one autograd node per op).  Here one
@@ -95,7 +95,7 @@ typedef struct gvk_gemm_desc {
   uint64_t seed;
   int32_t scale_cols; /* GVK_EPI_STORE_BF16 (bf16 entry point) only: columns n < scale_cols (a multiple of 8) are multiplied by col_scale in fp32 */
   float col_scale;    /* before the ONE rounding to bf16 -- the q block of a qkv projection leaves the GEMM as q * scale * log2(e), the form
-                         the attention kernels take (gvk_attention_*_bf16); 0 columns = off */
+                         the bf16 attention kernels take (gvk_attention_desc); 0 columns = off */
   /* LayerNorm folded into its consumer (GVK_EPI_STORE_BF16, bf16 entry point): a = the RAW rows x as bf16, w = gamma o W; with ln_mean /
      ln_rstd f32 [M] and ln_c1 f32 [N] = row sums of w (of its bf16 values) the epilogue stores rstd[m]*(acc - mean[m]*c1[n]) + bias[n],
      bias[n] = sum_c beta[c] W[n][c] -- LayerNorm(x) . W^T (vision_transformer.py:49,61-62) without the LayerNorm launch.  NULL = off */
@@ -137,15 +137,8 @@ int gvk_gemm_stat_parts(int N);
  * meet.  These entry points mirror their bf16 namesakes argument for argument -- same descriptor, same epilogue table,
  * same layouts -- with every 16-bit slot (A, W, bf16 outputs, aux) carrying float.  GELU is the exact erf form.
  * gvk_gemm_nt_f32: v_mfma_f32_16x16x4_f32 (exact fp32 products), N % 64 == 0, K % 16 == 0.
- * gvk_attention_*_f32: flash-style fp32 VALU kernels; delta f32 [B][H][T] is scratch written by the backward. */
+ * fp32 attention is gvk_attention_fwd / gvk_attention_bwd with gvk_attention_desc.f32 = 1 (below). */
 int gvk_gemm_nt_f32(const gvk_gemm_desc* d, void* stream);
-/* fp32 attention, with or without dropout (drop_p = 0: seed / seed_ptr unused): the counterparts of gvk_attention_fwd/bwd_bf16 and of their
- * _dropout forms (same mask function, so the two precisions drop the same elements) */
-int gvk_attention_fwd_f32_dropout(const float* qkv, float* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                  float drop_p, uint64_t seed, const void* seed_ptr, void* stream);
-int gvk_attention_bwd_f32_dropout(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
-                                  int B, int T, int H, int ld_qkv, int ld_out, float scale, float drop_p, uint64_t seed, const void* seed_ptr,
-                                  void* stream);
 int gvk_patchify_f32(const float* img, float* out, int B, int D, int H, int W, int pd, int ph, int pw, void* stream);
 int gvk_transpose_f32(const float* in, float* out, int rows, int cols, void* stream);
 int gvk_transpose_bf16(const void* in, void* out, int rows, int cols, void* stream);   /* operand transposes of the unfrozen-backbone wgrad GEMMs */
@@ -221,33 +214,49 @@ int gvk_layernorm_bwd_up(const float* dy, const float* x, const float* mean, con
                          float* dx, void* dx_bf16, const float* lat, const float* w, int w_layout, int M, int C, int L, void* stream);
 
 /* ------------------------------------------------------------------ multi-head self-attention, head dim 64
+ * One descriptor, one forward and one backward entry point for every form of the flash-style attention (vision_transformer.py:62-71).
  * qkv bf16 [B*T (padded)][ld_qkv]: columns [q' | k | v], each (head, 64) -- the to_qkv output (vision_transformer.py:62-63) with the q
  * block PRE-SCALED: q' = q * scale * log2(e), multiplied in fp32 before the one rounding to bf16.  gvk_gemm_nt_bf16 does it in the
  * projection's epilogue (gvk_gemm_desc.scale_cols = H*64, col_scale = scale * log2(e)); gvk_qkv_prescale_bf16 converts a raw qkv buffer
  * in place.  The forward and both backward passes then read bit-identical score operands (P of the backward is recomputed against the
- * forward's lse) and no kernel spends a multiply per score.  out bf16 [B*T][ld_out] in 'b n (h d)' order (vision_transformer.py:71), lse f32 [B][H][T]
- * = log sum_j exp(scale * q.k_j) (natural log), saved for the backward.  scale = dim_head^-0.5 (vision_transformer.py:47,65). */
-int gvk_attention_fwd_bf16(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                           void* stream);
-/* q block of a raw to_qkv output -> q * scale * log2(e), in place (rows = B*T) */
-int gvk_qkv_prescale_bf16(void* qkv, int rows, int H, int ld_qkv, float scale, void* stream);
-
-/* backward: dqkv bf16 [B*T][ld_qkv] = [dq | dk | dv] in the qkv layout -- gradients of the UNSCALED q, k, v (what the to_qkv dgrad
- * consumes) -- from qkv (q block pre-scaled as above), out (forward output, for delta = rowsum(dout*out)), dout and lse.  delta f32 [B][H][T] is scratch.  Deterministic (no atomics). */
-int gvk_attention_bwd_bf16(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                           int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream);
-/* ONE-PASS form of the same backward (round 5; ABI 10): five MFMA products per (query, key) block instead of seven and one exponential
- * per score instead of two -- each workgroup owns dK / dV of its 128 keys and also forms dQ's share of those keys; the shares of a
- * (batch, head)'s key blocks are summed by an ordered hand-off between the workgroups (fixed order per query tile: bitwise reproducible,
- * no float atomics).  ws: at least gvk_attention_bwd_ws_bytes(B, T, H) bytes, 256-byte aligned, ZERO at allocation (the kernel leaves its
- * progress words zero); its layout depends on ws_bytes only, so ONE workspace sized for the longest sequence serves shorter ones too.
- * The int32 at byte gvk_attention_bwd_status_offset(ws_bytes) counts hand-off waits that ran into their bound and stays 0.  Calls that
- * share a workspace must be ordered by their stream.  Same arguments and results as gvk_attention_bwd_bf16 otherwise (delta f32
- * [B][H][T] is written by a small kernel in front). */
+ * forward's lse) and no kernel spends a multiply per score.  scale = dim_head^-0.5 (vision_transformer.py:47,65).
+ *   fwd: reads qkv; writes out bf16 [B*T][ld_out] in 'b n (h d)' order (vision_transformer.py:71) and lse f32 [B][H][T] = log sum_j
+ *     exp(scale * q.k_j) (natural log), saved for the backward.  dout, delta, dqkv and need_rows are ignored; ws must be NULL.
+ *   bwd: reads qkv, out (for delta = rowsum(dout * out)), dout, lse; writes dqkv bf16 [B*T][ld_qkv] = [dq | dk | dv] in the qkv layout --
+ *     gradients of the UNSCALED q, k, v (what the to_qkv dgrad consumes) -- and delta f32 [B][H][T] (scratch).  Two passes, no atomics,
+ *     bitwise reproducible.
+ * ld_qkv >= 3*H*64, ld_out >= H*64, every row pitch a multiple of 16 bytes; a bf16 qkv tensor stays below 2 GiB.
+ * Four optional features.  They exclude each other where stated: a contradictory descriptor is an error, never resolved by precedence.
+ *   f32 = 1: every 16-bit slot (qkv, out, dout, dqkv) carries float and q is NOT pre-scaled (the kernels multiply by scale): the fp32
+ *     compute path, products on the fp32 matrix cores, 1e-5 against float64.  Plain two-pass backward only: no need_rows, no ws;
+ *   drop_p > 0: nn.Dropout(drop_p) on the attention probabilities (vision_transformer.py:52,68 -- live in training for the methods that
+ *     do not freeze the backbone): softmax statistics of the undropped scores, out = (P * mask / (1 - drop_p)) . V; the backward
+ *     regenerates mask(seed + *seed_ptr; b*H + head, query, key), the same function in both precisions.  0 <= drop_p < 1, T*T < 2^32.
+ *     drop_p = 0: seed and seed_ptr are unused;
+ *   need_rows > 0 (bwd, bf16, no dropout, no ws): only the FIRST need_rows tokens of every sample carry a consumer (the bottom layer of a
+ *     frozen backbone: of its input only the prompt rows hold a trainable tensor, gaviko.py:540-548): dq, dk, dv of tokens < need_rows
+ *     (rounded up to 128) are written -- the very bits the full call writes there, at whichever key tile -- the other rows of dqkv are
+ *     left untouched; delta is complete.  0: all rows.  need_rows <= T;
+ *   ws != NULL (bwd, bf16, no dropout, no need_rows): the ONE-PASS backward (round 5; ABI 10): five MFMA products per (query, key) block
+ *     instead of seven and one exponential per score instead of two -- each workgroup owns dK / dV of its 128 keys and also forms dQ's
+ *     share of those keys; the shares of a (batch, head)'s key blocks are summed by an ordered hand-off between the workgroups (fixed
+ *     order per query tile: bitwise reproducible, no float atomics); delta is written by a small kernel in front.  ws: ws_bytes >=
+ *     gvk_attention_bwd_ws_bytes(B, T, H) bytes, 256-byte aligned, ZERO at allocation (the kernel leaves its progress words zero); its
+ *     layout depends on ws_bytes only, so ONE workspace sized for the longest sequence serves shorter ones too.  The int32 at byte
+ *     gvk_attention_bwd_status_offset(ws_bytes) counts hand-off waits that ran into their bound and stays 0.  Calls that share a
+ *     workspace must be ordered by their stream.  NULL: the two-pass backward. */
+typedef struct gvk_attention_desc {
+  const void* qkv; void* out; void* lse; const void* dout; void* delta; void* dqkv; const void* seed_ptr; void* ws;
+  int32_t B, T, H, ld_qkv, ld_out, f32, need_rows;
+  float scale, drop_p;
+  uint64_t seed, ws_bytes;
+} gvk_attention_desc;
+int gvk_attention_fwd(const gvk_attention_desc* d, void* stream);
+int gvk_attention_bwd(const gvk_attention_desc* d, void* stream);
 size_t gvk_attention_bwd_ws_bytes(int B, int T, int H);
 size_t gvk_attention_bwd_status_offset(size_t ws_bytes);
-int gvk_attention_bwd_bf16_fused(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, void* ws,
-                                 size_t ws_bytes, int B, int T, int H, int ld_qkv, int ld_out, float scale, void* stream);
+/* q block of a raw bf16 to_qkv output -> q * scale * log2(e), in place (rows = B*T) */
+int gvk_qkv_prescale_bf16(void* qkv, int rows, int H, int ld_qkv, float scale, void* stream);
 /* attention maps for explanations (csrc/attention_map.hip; what a forward hook on the reference's `attend` softmax sees,
  * vision_transformer.py:50,67): the probabilities P = softmax(scale q.k^T) of qkv / lse in the layout above, row-weighted and summed --
  *   out f32 [B][H][T]  out[b][h][j] = sum_{q0 <= i < q1} w[b][i] * P[b][h][i][j]   for j < T (nothing else is written)
@@ -284,19 +293,6 @@ int gvk_evp_highpass_sign(const float* img, const float* hp, const int32_t* dept
                           void* stream);
 int gvk_evp_highpass_linear(const float* x, const float* op, const int32_t* depth_mask, float* out, int accumulate, int B, int D, int H, int W,
                             void* stream);
-/* gvk_attention_bwd_bf16 when only the FIRST need_rows tokens of every sample carry a consumer (the bottom layer of a frozen backbone: of its
- * input only the prompt rows hold a trainable tensor, gaviko.py:540-548): dq, dk, dv of tokens < need_rows (rounded up to 128) are written --
- * the very bits the full call writes there -- the other rows of dqkv are left untouched; delta is complete. */
-int gvk_attention_bwd_bf16_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                                int B, int T, int H, int ld_qkv, int ld_out, float scale, int need_rows, void* stream);
-/* the same with nn.Dropout(drop_p) on the attention probabilities (vision_transformer.py:52,68 -- live in training for the methods
- * that do not freeze the backbone): softmax statistics of the undropped scores, out = (P * mask / (1 - drop_p)) . V; the backward
- * regenerates mask(seed + *seed_ptr; b*H + head, query, key).  drop_p = 0 is the plain call. */
-int gvk_attention_fwd_bf16_dropout(const void* qkv, void* out, float* lse, int B, int T, int H, int ld_qkv, int ld_out, float scale,
-                                   float drop_p, uint64_t seed, const void* seed_ptr, void* stream);
-int gvk_attention_bwd_bf16_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                                   int B, int T, int H, int ld_qkv, int ld_out, float scale, float drop_p, uint64_t seed, const void* seed_ptr,
-                                   void* stream);
 
 /* ------------------------------------------------------------------ rank-L ("skinny") fp32 projections of the trainable
  * side paths, L in {4, 8, 16, 20, 32}.  GAViKO: gaviko.py:231-232,242 (MWSA norm/proj_down/qkv/proj_up) and

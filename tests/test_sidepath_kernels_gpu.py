@@ -722,11 +722,10 @@ def test_param_grads_hand_off_beside_a_stream_that_dirties_the_caches(dev):
     assert int(tick.abs().max()) == 0
 
 
-def test_attention_bwd_first_rows_only(dev):
-    """gvk_attention_bwd_bf16_rows: dq, dk, dv of the first need_rows tokens of every sample (rounded up to the 128-row blocks) carry the
-    very bits of the full call, every other row of dqkv is left untouched, delta is complete."""
+def _rows_form_case(dev, B, T, H, need_rows, sentinel=3.0):
+    """The full backward and its need_rows form on the same inputs, dqkv of the latter pre-filled with a sentinel:
+    -> (delta full, delta part, dqkv full [B,T,3*inner], dqkv part [B,T,3*inner])."""
     from gaviko_amd import ops
-    B, T, H = 2, 1033, 3
     inner = H * 64
     qkv = ops.act_zeros(B * T, 3 * inner, torch.bfloat16, dev)
     qkv[: B * T] = _rand((B * T, 3 * inner), 71, 1.0).bfloat16().to(dev)
@@ -737,12 +736,76 @@ def test_attention_bwd_first_rows_only(dev):
     DO = ops.act_zeros(B * T, inner, torch.bfloat16, dev)
     DO[: B * T] = _rand((B * T, inner), 72, 1.0).bfloat16().to(dev)
     full, part = ops.act_zeros(B * T, 3 * inner, torch.bfloat16, dev), ops.act_zeros(B * T, 3 * inner, torch.bfloat16, dev)
-    part.fill_(3.0)
+    part.fill_(sentinel)
     d_full, d_part = torch.zeros((B, H, T), device=dev), torch.zeros((B, H, T), device=dev)
     ops.attention_bwd(qkv, O, DO, lse, d_full, full, B, T, H, 0.125, q_prescaled=True)
-    ops.attention_bwd(qkv, O, DO, lse, d_part, part, B, T, H, 0.125, q_prescaled=True, need_rows=32)
+    ops.attention_bwd(qkv, O, DO, lse, d_part, part, B, T, H, 0.125, q_prescaled=True, need_rows=need_rows)
     torch.cuda.synchronize()
+    return d_full, d_part, full[: B * T].view(B, T, -1), part[: B * T].view(B, T, -1)
+
+
+def test_attention_bwd_first_rows_only(dev):
+    """gvk_attention_bwd with gvk_attention_desc.need_rows: dq, dk, dv of the first need_rows tokens of every sample (rounded up to the
+    128-row blocks) carry the very bits of the full call, every other row of dqkv is left untouched, delta is complete."""
+    d_full, d_part, f, p = _rows_form_case(dev, 2, 1033, 3, 32)
     assert torch.equal(d_full, d_part)
-    f, p = full[: B * T].view(B, T, -1), part[: B * T].view(B, T, -1)
     assert torch.equal(f[:, :128], p[:, :128])
     assert bool((p[:, 128:] == 3.0).all())
+
+
+@pytest.mark.parametrize("kb", [96, 128])
+def test_attention_bwd_first_rows_forced_tile(dev, monkeypatch, kb):
+    """The rows form takes its key tile from the same place as the full call, the GAVIKO_HIP_ATTN_KB hook included (T = 200: two key
+    blocks at either tile size): under a forced tile rows < 128 of every sample are still the full call's bits, rows >= 128 keep the
+    sentinel bit for bit, delta is identical everywhere."""
+    monkeypatch.setenv("GAVIKO_HIP_ATTN_KB", str(kb))
+    d_full, d_part, f, p = _rows_form_case(dev, 2, 200, 2, 5)
+    assert torch.equal(d_full, d_part)
+    assert torch.equal(f[:, :128].view(torch.int16), p[:, :128].view(torch.int16))
+    rest = p[:, 128:].contiguous().view(torch.int16)
+    assert torch.equal(rest, torch.full_like(p[:, 128:], 3.0).contiguous().view(torch.int16))
+
+
+def test_attention_contradictory_descriptors_are_refused(dev):
+    """gvk_attention_bwd / gvk_attention_fwd refuse a descriptor that asks for two exclusive forms at once -- they do not pick one -- with a
+    message that names the conflict, and launch nothing: dqkv and out keep their sentinel.  Every buffer is real and large enough for its
+    dtype (workspace and seed word included), so a check that wrongly let a descriptor through would run an ordinary valid launch."""
+    import ctypes
+    from gaviko_amd import lib, ops
+    B, T, H, inner = 1, 64, 1, 64
+    l = lib.load()
+    ws = ops.attention_bwd_workspace(B, T, H, dev)
+    seed = torch.zeros(1, dtype=torch.int64, device=dev)
+    lse, delta = torch.zeros((B, H, T), device=dev), torch.zeros((B, H, T), device=dev)
+    bufs = {}
+    for f32, dt in ((0, torch.bfloat16), (1, torch.float32)):
+        qkv = ops.act_zeros(B * T, 3 * inner, dt, dev)
+        qkv[: B * T] = _rand((B * T, 3 * inner), 81, 1.0).to(dt).to(dev)
+        dout = ops.act_zeros(B * T, inner, dt, dev)
+        dout[: B * T] = _rand((B * T, inner), 82, 1.0).to(dt).to(dev)
+        out, dqkv = ops.act_zeros(B * T, inner, dt, dev), ops.act_zeros(B * T, 3 * inner, dt, dev)
+        out.fill_(3.0)
+        dqkv.fill_(3.0)
+        bufs[f32] = dict(qkv=qkv, out=out, dout=dout, dqkv=dqkv)
+    drop = dict(drop_p=0.1, seed=7, seed_ptr=lib.ptr(seed))
+    wsf = dict(ws=lib.ptr(ws), ws_bytes=ws.numel() * 4)
+    cases = [("bwd", 0, dict(need_rows=5, **drop), ("need_rows", "drop_p")),
+             ("bwd", 0, dict(need_rows=5, **wsf), ("need_rows", "ws")),
+             ("bwd", 0, dict(**wsf, **drop), ("ws", "drop_p")),
+             ("bwd", 1, dict(**wsf), ("ws", "f32")),
+             ("bwd", 1, dict(need_rows=5), ("need_rows", "f32")),
+             ("bwd", 0, dict(need_rows=-1), ("need_rows",)),
+             ("bwd", 0, dict(need_rows=T + 1), ("need_rows",)),
+             ("fwd", 0, dict(**wsf), ("ws", "forward"))]
+    for which, f32, extra, words in cases:
+        t = bufs[f32]
+        d = lib.AttentionDesc(qkv=lib.ptr(t["qkv"]), out=lib.ptr(t["out"]), lse=lib.ptr(lse), dout=lib.ptr(t["dout"]), delta=lib.ptr(delta),
+                              dqkv=lib.ptr(t["dqkv"]), B=B, T=T, H=H, ld_qkv=3 * inner, ld_out=inner, f32=f32, scale=0.125, **extra)
+        fn = l.gvk_attention_bwd if which == "bwd" else l.gvk_attention_fwd
+        rc = fn(ctypes.byref(d), lib.stream_ptr())
+        msg = l.gvk_last_error().decode()
+        assert rc != 0, f"{which} f32={f32} {extra}: accepted"
+        assert all(w in msg for w in words), f"{which} f32={f32} {extra}: message {msg!r} does not name {words}"
+    torch.cuda.synchronize()
+    for t in bufs.values():
+        assert bool((t["dqkv"] == 3.0).all()) and bool((t["out"] == 3.0).all())

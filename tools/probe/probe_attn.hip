@@ -2,8 +2,7 @@
 //   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 -ffp-contract=off -shared tools/probe/probe_attn.hip \
 //         -Lgaviko_amd -lgaviko_hip -Wl,-rpath,'$ORIGIN/../../gaviko_amd' -o tools/probe/libprobe_attn.so
 #define GVK_STAMPS 1
-#define gvk_attention_fwd_bf16_dropout probe_unused_fwd_dropout
-#define gvk_attention_fwd_bf16 probe_unused_fwd
+#define gvk_attention_fwd probe_unused_fwd
 #define gvk_qkv_prescale_bf16 probe_unused_prescale
 #include "../../gaviko_amd/csrc/attention_fwd.hip"
 
