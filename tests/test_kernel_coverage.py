@@ -4,6 +4,7 @@ The whole-model golden tests run every kernel, but only at a handful of shapes a
 subtly wrong can hide there.  This file parses the C ABI (include/gaviko_hip.h), maps every ops.py wrapper -- and every name of the
 thin host modules below -- to the gvk_* symbols it reaches, and collects what the test files call.  The symbols no test reaches
 must equal UNCOVERED exactly: a new kernel without a direct test fails here, and so does a kernel that gained one but is still listed.
+A second ledger does the same for the GEMM descriptor: every ops.gemm_nt parameter the engine passes must be a keyword of a direct test.
 """
 import ast
 import os
@@ -160,3 +161,99 @@ def test_uncovered_kernels_match_the_allow_list():
     stale = sorted(set(UNCOVERED) - untested)
     assert not new, f"kernels with no direct test (add one, or list them in UNCOVERED with a reason): {new}"
     assert not stale, f"kernels listed in UNCOVERED that a test now calls (remove them from the list): {stale}"
+
+
+# ---- the GEMM descriptor: every ops.gemm_nt parameter the engine passes is a keyword of some direct test --------------------------
+# (the entry points gvk_gemm_nt_bf16 / gvk_gemm_nt_f32 are covered above by any one call; their features are what the engine composes)
+
+# dict-valued names the engine splices into its GEMM calls with **: their keys come from the dict(...) literals assigned to them, and from
+# the literals _panels returns (pk, top and bot carry a _panels(...) result or {})
+PANEL_CARRIERS = {"pk", "top", "bot"}
+
+# gemm_nt parameters the engine passes that no test passes directly, each with its reason
+GEMM_PARAMS_UNCOVERED = {}
+
+
+def _gemm_nt_parameters():
+    tree = ast.parse(open(os.path.join(PKG, "ops.py")).read())
+    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "gemm_nt")
+    return {a.arg for a in fn.args.args + fn.args.kwonlyargs}
+
+
+def _dict_literal_keys(node):
+    """keyword names of every dict(...) call inside an expression"""
+    return {k.arg for sub in ast.walk(node) if isinstance(sub, ast.Call) and isinstance(sub.func, ast.Name) and sub.func.id == "dict"
+            for k in sub.keywords if k.arg}
+
+
+def _is_gemm_call(node, names):
+    """a call of ops.gemm_nt, or of self._gemm (the engine's wrapper around it)"""
+    if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name)):
+        return False
+    return (node.func.value.id, node.func.attr) in names
+
+
+def engine_gemm_parameters():
+    """gemm_nt parameter names the engine modules pass: keywords of self._gemm / ops.gemm_nt calls, and the keys of the dict(...) literals
+    behind every **name of those calls (looked up in the enclosing function; a spliced name with no literal must be a panel carrier)."""
+    params = _gemm_nt_parameters()
+    passed, unresolved = set(), set()
+    for f in sorted(os.listdir(PKG)):
+        if not (f.startswith("engine") and f.endswith(".py")):
+            continue
+        tree = ast.parse(open(os.path.join(PKG, f)).read())
+        panel_keys = set()
+        for fn in ast.walk(tree):
+            if isinstance(fn, ast.FunctionDef) and fn.name == "_panels":
+                for sub in ast.walk(fn):
+                    if isinstance(sub, ast.Return) and sub.value is not None:
+                        panel_keys |= _dict_literal_keys(sub.value)
+        passed |= panel_keys
+        for fn in ast.walk(tree):
+            if not isinstance(fn, ast.FunctionDef) or fn.name == "_gemm":      # (the wrapper itself forwards **kw)
+                continue
+            assigned = {}
+            for sub in ast.walk(fn):
+                if isinstance(sub, ast.Assign):
+                    for t in sub.targets:
+                        if isinstance(t, ast.Name):
+                            assigned.setdefault(t.id, set()).update(_dict_literal_keys(sub.value))
+            for sub in ast.walk(fn):
+                if not _is_gemm_call(sub, {("self", "_gemm"), ("ops", "gemm_nt")}):
+                    continue
+                for k in sub.keywords:
+                    if k.arg is not None:
+                        passed.add(k.arg)
+                    elif isinstance(k.value, ast.Name) and (assigned.get(k.value.id) or k.value.id in PANEL_CARRIERS):
+                        passed |= assigned.get(k.value.id, set())
+                    else:
+                        unresolved.add(f"{f}:{sub.lineno}")
+    assert not unresolved, f"GEMM calls that splice something this ledger cannot read: {sorted(unresolved)}"
+    return passed & params
+
+
+def gemm_parameters_in_tests():
+    """keywords of the ops.gemm_nt calls in the test files"""
+    used = set()
+    for f in sorted(os.listdir(TESTS)):
+        if f.startswith("test_") and f.endswith(".py"):
+            tree = ast.parse(open(os.path.join(TESTS, f)).read())
+            for node in ast.walk(tree):
+                if _is_gemm_call(node, {("ops", "gemm_nt")}):
+                    used |= {k.arg for k in node.keywords if k.arg}
+    return used
+
+
+def test_engine_gemm_parameter_scan_is_sane():
+    got = engine_gemm_parameters()
+    assert got >= {"epilogue", "bias", "res", "aux", "ldo", "ldaux", "K", "drop_p", "aux_is_grad", "m_panels", "m_stride", "stat_part", "stat_pivot",
+                   "ln_mean", "scale_cols", "rows_in"}
+    assert "alg_k" not in got                                 # the engine wrapper's own argument, not a gemm_nt parameter
+
+
+def test_every_gemm_parameter_the_engine_passes_has_a_direct_test():
+    untested = engine_gemm_parameters() - gemm_parameters_in_tests()
+    new = sorted(untested - set(GEMM_PARAMS_UNCOVERED))
+    stale = sorted(set(GEMM_PARAMS_UNCOVERED) - untested)
+    assert not new, f"ops.gemm_nt parameters the engine passes that no test passes (add a test, or list them in GEMM_PARAMS_UNCOVERED): {new}"
+    assert not stale, f"parameters listed in GEMM_PARAMS_UNCOVERED that a test now passes, or the engine no longer does: {stale}"
