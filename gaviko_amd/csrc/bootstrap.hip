@@ -1,0 +1,166 @@
+// Bootstrap replicates of the evaluation metrics (gaviko_amd.metrics.bootstrap / compare): replicate b resamples the N rows of an
+// evaluation set with replacement and leaves what csrc/metrics.hip leaves for the full sample -- the K x K confusion counts and the
+// one-vs-rest AUC pair counts of every class -- as exact integers.  A resample is a vector of integer multiplicities w_i on the rows:
+//   confusion[t][p]   = sum of w_i over the rows with (label, prediction) = (t, p)
+//   2*greater + ties  = sum over positives i and negatives j of  w_i w_j (2 [p_i > p_j] + [p_i == p_j])
+// With the rows of class column c sorted once per call (order, and the tie group [gstart, gend) of every sorted position), the pair sum of a
+// replicate is a prefix sum: P = inclusive scan of the negatives' weights in sorted order, and a positive at sorted position s adds
+//   w (2 P[gstart - 1] + (P[gend - 1] - P[gstart - 1])) = w (P[gstart - 1] + P[gend - 1]),     P[-1] = 0
+// -- O(N) per class and replicate, against O(N^2) for counting pairs.  Everything is an integer: the order of the atomics changes nothing.
+#include "common.hpp"
+#include "dropout.hpp"
+#include "../../include/gaviko_hip.h"
+
+namespace gvk {
+
+constexpr int kBootMaxN = GVK_BOOTSTRAP_MAX_ROWS;               // multiplicities stay below 2^24 (the label shares their LDS word), two N-entry LDS arrays
+constexpr int kBootMaxK = GVK_BOOTSTRAP_MAX_CLASSES;            // the label takes the 8 bits above them; K x K counters in LDS
+constexpr int kBootTile = 1024;                                  // scan tile: 256 threads x 4 consecutive entries (one 16-byte LDS access each)
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One 256-thread workgroup per replicate.  LDS (dynamic): wl[Npad] | P[Npad] | conf[K * K], Npad = N rounded up to the scan tile.
+//   wl[row] = label << 24 | multiplicity: the label is laid down first, the N draws of the replicate add 1 each (32-bit LDS atomics; a
+//   multiplicity is at most N <= 8192, so it never reaches the label), and every later pass gets both from one LDS read.
+// Per class c: P[s] = weight of the row at sorted position s if it is a negative, else 0; inclusive scan of P in tiles of 1024 (4 entries per
+// thread, wave64 shuffle scan of the thread totals, the 4 wave totals and the running carry through LDS); the positives' sums; a block
+// reduction; plain stores.  Every index read from a table is clamped or tested before it addresses LDS: the tables are the caller's contract
+// (ops.bootstrap_counts builds them), a broken one gives wrong counts, never an access outside the arrays.
+__global__ __launch_bounds__(256) void bootstrap_counts_kernel(const long long* __restrict__ labels, const int* __restrict__ pred,
+                                                               const int* __restrict__ order, const int* __restrict__ gstart,
+                                                               const int* __restrict__ gend, const int* __restrict__ class_rows,
+                                                               const int* __restrict__ class_off, long long* __restrict__ confusion,
+                                                               long long* __restrict__ auc_counts, int N, int K, int Npad,
+                                                               unsigned long long seed, int stratified) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int boot_lds[];
+  __shared__ unsigned int s_wave[4];
+  __shared__ unsigned long long s_red[8];
+  unsigned int* wl = boot_lds;
+  unsigned int* P = boot_lds + Npad;
+  unsigned int* conf = boot_lds + 2 * Npad;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned long long b = blockIdx.x;
+
+  for (int i = t; i < N; i += 256) {
+    const long long y = labels[i];
+    wl[i] = (y >= 0 && y < K) ? (unsigned int)y << 24 : 0xFF000000u;      // a label outside [0, K) (the caller rejects it) matches no class
+  }
+  for (int i = t; i < K * K; i += 256) conf[i] = 0u;
+  __syncthreads();
+  for (int n = t; n < N; n += 256) {
+    const unsigned long long h = hash_u32(seed, b * (unsigned long long)N + (unsigned long long)n);
+    int j;
+    if (stratified) {
+      const long long y = labels[n];
+      const int c = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);
+      const int o0 = class_off[c], nc = class_off[c + 1] - o0;
+      int q = o0 + (int)((h * (unsigned long long)(nc > 0 ? nc : 0)) >> 32);
+      q = q < 0 ? 0 : (q >= N ? N - 1 : q);
+      j = class_rows[q];
+      j = j < 0 ? 0 : (j >= N ? N - 1 : j);
+    } else {
+      j = (int)((h * (unsigned long long)N) >> 32);                       // < N: h < 2^32
+    }
+    atomicAdd(&wl[j], 1u);
+  }
+  __syncthreads();
+  for (int i = t; i < N; i += 256) {
+    const unsigned int v = wl[i], y = v >> 24, w = v & 0xFFFFFFu;
+    const int p = pred[i];
+    if (w && y < (unsigned int)K && p >= 0 && p < K) atomicAdd(&conf[y * K + p], w);
+  }
+  __syncthreads();
+  for (int i = t; i < K * K; i += 256) confusion[b * K * K + i] = (long long)conf[i];
+
+  for (int c = 0; c < K; ++c) {
+    const int* oc = order + (size_t)c * N;
+    for (int s = t; s < Npad; s += 256) {
+      unsigned int w = 0u;
+      if (s < N) {
+        int row = oc[s];
+        row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+        const unsigned int v = wl[row];
+        w = (v >> 24) != (unsigned int)c ? (v & 0xFFFFFFu) : 0u;
+      }
+      P[s] = w;
+    }
+    __syncthreads();
+    unsigned int carry = 0u;                                              // sum of the tiles before this one: the same in every thread
+    for (int s0 = 0; s0 < Npad; s0 += kBootTile) {
+      u32x4 v = *(const u32x4*)(P + s0 + 4 * t);
+      v.y += v.x; v.z += v.y; v.w += v.z;
+      const unsigned int tot = v.w;
+      unsigned int inc = tot;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+      }
+      if (lane == 63) s_wave[wave] = inc;
+      __syncthreads();
+      const unsigned int w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
+      const unsigned int base = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + (inc - tot);
+      v.x += base; v.y += base; v.z += base; v.w += base;
+      *(u32x4*)(P + s0 + 4 * t) = v;
+      carry += w0 + w1 + w2 + w3;
+      __syncthreads();                                                    // P is complete for the reads below; s_wave is free for the next tile
+    }
+    unsigned long long acc = 0ull, npos = 0ull;
+    for (int s = t; s < N; s += 256) {
+      int row = oc[s];
+      row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+      const unsigned int v = wl[row], w = v & 0xFFFFFFu;
+      if ((v >> 24) == (unsigned int)c && w) {
+        int gs = gstart[(size_t)c * N + s], ge = gend[(size_t)c * N + s];
+        gs = gs < 0 ? 0 : (gs > N ? N : gs);
+        ge = ge < 1 ? 1 : (ge > N ? N : ge);
+        const unsigned int below = gs > 0 ? P[gs - 1] : 0u;               // negatives' weight strictly below the tie group
+        acc += (unsigned long long)w * ((unsigned long long)below + (unsigned long long)P[ge - 1]);
+        npos += w;
+      }
+    }
+    acc = wave_sum_u64(acc);
+    npos = wave_sum_u64(npos);
+    if (lane == 0) { s_red[wave] = acc; s_red[4 + wave] = npos; }
+    __syncthreads();
+    if (t == 0) {
+      const unsigned long long a = s_red[0] + s_red[1] + s_red[2] + s_red[3], np = s_red[4] + s_red[5] + s_red[6] + s_red[7];
+      long long* out = auc_counts + (b * K + c) * 3;
+      out[0] = (long long)a;
+      out[1] = (long long)np;
+      out[2] = (long long)carry;                                          // the scan's total: the negatives' weight
+    }
+    __syncthreads();                                                      // P and s_red are rewritten by the next class
+  }
+}
+
+}  // namespace gvk
+
+extern "C" int gvk_bootstrap_counts(const void* labels, const int32_t* pred, const int32_t* order, const int32_t* gstart, const int32_t* gend,
+                                    const int32_t* class_rows, const int32_t* class_off, int64_t* confusion, int64_t* auc_counts, int N, int K, int R,
+                                    uint64_t seed, int stratified, void* stream) {
+  using namespace gvk;
+  GVK_REQUIRE(labels && pred && order && gstart && gend && confusion && auc_counts, "gvk_bootstrap_counts: bad arguments");
+  GVK_REQUIRE(N >= 1 && N <= kBootMaxN, "gvk_bootstrap_counts: N = %d rows outside [1, %d] (one workgroup keeps the multiplicities and the scan in LDS)", N,
+              kBootMaxN);
+  GVK_REQUIRE(K >= 2 && K <= kBootMaxK, "gvk_bootstrap_counts: K = %d classes outside [2, %d]", K, kBootMaxK);
+  GVK_REQUIRE(R >= 1, "gvk_bootstrap_counts: R = %d replicates (at least 1)", R);
+  GVK_REQUIRE(stratified == 0 || stratified == 1, "gvk_bootstrap_counts: stratified = %d (0 or 1)", stratified);
+  GVK_REQUIRE(!stratified || (class_rows && class_off), "gvk_bootstrap_counts: the stratified rule needs class_rows and class_off");
+  const int Npad = (N + kBootTile - 1) / kBootTile * kBootTile;
+  const size_t lds = sizeof(unsigned int) * ((size_t)2 * Npad + (size_t)K * K);
+  static size_t granted = 64 * 1024 - 256;                                // what a launch may ask for without the attribute (the static arrays take a little)
+  if (lds > granted) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bootstrap_counts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(bootstrap_counts): %s", hipGetErrorString(e));
+    granted = lds;
+  }
+  GVK_LAUNCH(bootstrap_counts_kernel, dim3((unsigned)R), dim3(256), (unsigned)lds, (hipStream_t)stream, (const long long*)labels, (const int*)pred,
+             (const int*)order, (const int*)gstart, (const int*)gend, (const int*)class_rows, (const int*)class_off, (long long*)confusion,
+             (long long*)auc_counts, N, K, Npad, (unsigned long long)seed, stratified);
+  return check_launch("bootstrap_counts");
+}

@@ -201,6 +201,7 @@ SIGNATURES = {
     "gvk_tta_volumes": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_predictive_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gvk_calibration_bins": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_bootstrap_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_uint64, _I, _P],
     "gvk_token_pool": [_P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_l2_normalize_rows": [_P, _P, _P, _I, _I, _F, _P],
     "gvk_feature_topk": [C.POINTER(FeatureTopkDesc), _P],

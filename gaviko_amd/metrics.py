@@ -8,7 +8,7 @@ reference logs -- accuracy, quadratic-weighted Cohen kappa, macro one-vs-rest RO
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -72,6 +72,185 @@ def calibration(proba: torch.Tensor, labels: torch.Tensor, bins: int = 15) -> Di
             "nll": float(r["nll"].item()) / float(N), "bin_count": count, "bin_accuracy": acc, "bin_confidence": conf}
 
 
+def _ratio(num: np.ndarray, den: np.ndarray) -> np.ndarray:
+    """num / den in float64 with 0 where den == 0 (sklearn's zero_division=0)."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape), where=den != 0)
+
+
+def _class_stats(confusion: np.ndarray) -> Dict[str, np.ndarray]:
+    """Per-class figures of confusion matrices [..., K, K] (rows = labels, columns = predictions), float64, empty denominators -> 0:
+    support, recall, specificity, precision, f1 = 2 tp / (2 tp + fp + fn) (sklearn's form of 2 P R / (P + R)), each [..., K]; and
+    balanced_accuracy (mean recall over the classes with support), macro_f1 (mean F1 over the classes in labels or predictions), each [...]."""
+    c = np.asarray(confusion, dtype=np.int64)
+    tp = np.diagonal(c, axis1=-2, axis2=-1)
+    support, predicted = c.sum(-1), c.sum(-2)
+    fn, fp = support - tp, predicted - tp
+    tn = c.sum((-2, -1))[..., None] - support - fp
+    has_label, present = support > 0, (support + predicted) > 0
+    recall, f1 = _ratio(tp, support), _ratio(2 * tp, 2 * tp + fp + fn)
+    return {"support": support, "recall": recall, "specificity": _ratio(tn, tn + fp), "precision": _ratio(tp, predicted), "f1": f1,
+            "balanced_accuracy": _ratio((recall * has_label).sum(-1), has_label.sum(-1)), "macro_f1": _ratio((f1 * present).sum(-1), present.sum(-1))}
+
+
+def classification_report(confusion) -> Dict[str, object]:
+    """Host only, float64, from one K x K confusion matrix (rows = labels): per-class `support` (int64), `recall` (sensitivity), `specificity`,
+    `precision` and `f1` as [K] arrays, with sklearn's zero_division=0 for an empty denominator; `balanced_accuracy` = mean recall over the
+    classes that occur in the labels (balanced_accuracy_score), `macro_f1` = mean F1 over the classes that occur in the labels or the
+    predictions (f1_score(average='macro', zero_division=0))."""
+    c = np.asarray(confusion)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 1:
+        raise ValueError(f"classification_report: expected a K x K confusion matrix, got {c.shape}")
+    s = _class_stats(c)
+    return dict(s, balanced_accuracy=float(s["balanced_accuracy"]), macro_f1=float(s["macro_f1"]))
+
+
+def kappa_quadratic_batch(confusion: np.ndarray) -> np.ndarray:
+    """kappa_quadratic of R confusion matrices [R, K, K] at once, float64 [R], its absent-class squeeze included: a class that occurs in neither
+    the labels nor the predictions of a replicate has an empty row and column there, so it adds nothing to either sum and only has to be left
+    out of the numbering behind the (i - j)^2 weights -- the weights use each class's rank among the classes present in that replicate."""
+    c = np.asarray(confusion, dtype=np.float64)
+    rows, cols = c.sum(2), c.sum(1)
+    present = (rows + cols) > 0
+    rank = np.cumsum(present, 1) - 1
+    w = (rank[:, :, None] - rank[:, None, :]).astype(np.float64) ** 2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        expected = rows[:, :, None] * cols[:, None, :] / c.sum((1, 2))[:, None, None]
+        k = 1.0 - (w * c).sum((1, 2)) / (w * expected).sum((1, 2))
+    return np.where(present.sum(1) < 2, np.nan, k)
+
+
+BOOTSTRAP_METRICS = ("accuracy", "quadratic_kappa", "auc", "balanced_accuracy", "macro_f1")
+
+
+def metrics_from_counts(confusion: np.ndarray, auc_counts: np.ndarray) -> Dict[str, np.ndarray]:
+    """BOOTSTRAP_METRICS of R replicates, float64 [R] each, from confusion int64 [R, K, K] and auc_counts int64 [R, K, 3].  A replicate in
+    which some class has no positive or no negative row has no one-vs-rest AUC: its `auc` is NaN (where macro_ovr_auc raises)."""
+    conf = np.asarray(confusion, dtype=np.int64)
+    cnt = np.asarray(auc_counts, dtype=np.float64)
+    s = _class_stats(conf)
+    defined = ((cnt[:, :, 1] > 0) & (cnt[:, :, 2] > 0)).all(1)
+    auc = np.full(conf.shape[0], np.nan)
+    d = cnt[defined]
+    auc[defined] = (d[:, :, 0] / (2.0 * d[:, :, 1] * d[:, :, 2])).mean(1)
+    return {"accuracy": _ratio(np.trace(conf, axis1=1, axis2=2), conf.sum((1, 2))), "quadratic_kappa": kappa_quadratic_batch(conf),
+            "auc": auc, "balanced_accuracy": s["balanced_accuracy"], "macro_f1": s["macro_f1"]}
+
+
+class BootstrapResult(NamedTuple):
+    point: Dict[str, float]                # BOOTSTRAP_METRICS on the full sample (auc NaN where it is undefined)
+    replicates: Dict[str, np.ndarray]      # float64 [R] per metric
+    ci: Dict[str, Tuple[float, float]]     # percentile interval: np.nanquantile(rep, [(1 - level) / 2, (1 + level) / 2])
+    stderr: Dict[str, float]               # np.nanstd(rep, ddof=1)
+    undefined: Dict[str, int]              # NaN replicates per metric
+    confusion: np.ndarray                  # int64 [R, K, K]
+    auc_counts: np.ndarray                 # int64 [R, K, 3]
+    seed: int
+    stratified: bool
+    level: float
+
+
+class Comparison(NamedTuple):
+    delta_point: Dict[str, float]          # a - b on the full sample
+    delta: Dict[str, np.ndarray]           # float64 [R], a - b per replicate (the same multiplicities on both sides)
+    ci: Dict[str, Tuple[float, float]]     # percentile interval of delta
+    p_value: Dict[str, float]              # two-sided, paired_p_value(delta)
+    a: BootstrapResult
+    b: BootstrapResult
+    seed: int
+    stratified: bool
+    level: float
+
+
+def _interval(rep: np.ndarray, level: float) -> Tuple[float, float]:
+    if np.isnan(rep).all():
+        return (float("nan"), float("nan"))
+    lo, hi = np.nanquantile(rep, [(1.0 - level) / 2.0, (1.0 + level) / 2.0])
+    return (float(lo), float(hi))
+
+
+def _stderr(rep: np.ndarray) -> float:
+    return float(np.nanstd(rep, ddof=1)) if (~np.isnan(rep)).sum() > 1 else float("nan")
+
+
+def paired_p_value(delta) -> float:
+    """Two-sided bootstrap p-value of 'no difference' from paired replicate differences, over the R_def replicates that are not NaN:
+    min(1, 2 min((#{delta <= 0} + 1) / (R_def + 1), (#{delta >= 0} + 1) / (R_def + 1)))."""
+    d = np.asarray(delta, dtype=np.float64)
+    d = d[~np.isnan(d)]
+    n = d.size + 1.0
+    return float(min(1.0, 2.0 * min(((d <= 0).sum() + 1.0) / n, ((d >= 0).sum() + 1.0) / n)))
+
+
+def bootstrap(proba: torch.Tensor, labels: torch.Tensor, *, replicates: int = 2000, seed: int = 0, stratified: bool = False, level: float = 0.95,
+              pred: Optional[torch.Tensor] = None) -> BootstrapResult:
+    """Bootstrap confidence intervals of the evaluation metrics: proba f32 [N, K] on the device (what gvk_eval_rows wrote), labels [N] within
+    [0, K).  gvk_bootstrap_counts resamples the N rows `replicates` times and leaves every replicate's confusion matrix and one-vs-rest AUC
+    pair counts as exact integers; BOOTSTRAP_METRICS are finished from them in float64 on the host.
+      plain:       draw n of replicate b takes row  (hash_u32(seed, b N + n) * N) >> 32
+      stratified:  draw n takes the  ((hash_u32(seed, b N + n) * n_c) >> 32)-th row (ascending) of the class c of row n, which has n_c rows:
+                   every class keeps its size, so the AUC is always defined
+    A replicate that lost a class (no positive, or no negative row for it) has auc = NaN and counts in undefined["auc"]; the interval and the
+    standard error skip NaN.  `pred` i32 [N] (optional): the predictions, where they are not the argmax of proba (lowest index on a tie).
+    N <= 8192, 2 <= K <= 64."""
+    if not isinstance(proba, torch.Tensor) or not proba.is_cuda:
+        raise GavikoHipError("bootstrap: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    if proba.dim() != 2:
+        raise GavikoHipError(f"bootstrap: expected proba [N, K], got {tuple(proba.shape)}")
+    N, K = proba.shape
+    labels = torch.as_tensor(labels).to(proba.device).to(torch.int64).contiguous()
+    if labels.numel() != N or N < 1:
+        raise GavikoHipError(f"bootstrap: {labels.numel()} labels for {N} rows of probabilities")
+    if N > ops.BOOTSTRAP_MAX_ROWS or not 2 <= K <= ops.BOOTSTRAP_MAX_CLASSES:
+        raise GavikoHipError(f"bootstrap: N = {N}, K = {K} outside N <= {ops.BOOTSTRAP_MAX_ROWS}, 2 <= K <= {ops.BOOTSTRAP_MAX_CLASSES}")
+    if int(labels.min()) < 0 or int(labels.max()) >= K:
+        raise GavikoHipError(f"bootstrap: labels outside [0, {K})")
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1:
+        raise GavikoHipError(f"bootstrap: replicates = {replicates!r} (an integer >= 1)")
+    if not 0.0 < float(level) < 1.0:
+        raise GavikoHipError(f"bootstrap: level = {level!r} outside (0, 1)")
+    proba = proba.detach().float().contiguous()
+    if bool(torch.isnan(proba).any()):
+        raise GavikoHipError("bootstrap: NaN probabilities have no rank")
+    if pred is None:
+        pred = torch.argmax(proba, dim=1)
+    pred = pred.to(proba.device).to(torch.int32).contiguous()
+    if pred.numel() != N:
+        raise GavikoHipError(f"bootstrap: {pred.numel()} predictions for {N} rows")
+    conf_d, cnt_d = ops.bootstrap_counts(labels, pred, ops.bootstrap_tables(proba, labels), replicates, seed, bool(stratified))
+    full = torch.zeros(3 * K, dtype=torch.int64, device=proba.device)
+    ops.ovr_auc_counts(proba, labels, full)
+    conf0 = torch.bincount(labels * K + pred.clamp(0, K - 1).to(torch.int64), minlength=K * K).view(1, K, K)
+    conf, cnt = conf_d.cpu().numpy(), cnt_d.cpu().numpy()
+    point = {k: float(v[0]) for k, v in metrics_from_counts(conf0.cpu().numpy(), full.cpu().numpy().reshape(1, K, 3)).items()}
+    conf0 = conf0.cpu().numpy()[0]
+    point["accuracy"], point["quadratic_kappa"] = float(np.trace(conf0)) / float(N), kappa_quadratic(conf0)    # as Evaluator.compute takes them
+    if not np.isnan(point["auc"]):
+        point["auc"] = macro_ovr_auc(full.cpu().numpy())
+    rep = metrics_from_counts(conf, cnt)
+    return BootstrapResult(point=point, replicates=rep, ci={k: _interval(v, float(level)) for k, v in rep.items()},
+                           stderr={k: _stderr(v) for k, v in rep.items()}, undefined={k: int(np.isnan(v).sum()) for k, v in rep.items()},
+                           confusion=conf, auc_counts=cnt, seed=int(seed), stratified=bool(stratified), level=float(level))
+
+
+def compare(proba_a: torch.Tensor, proba_b: torch.Tensor, labels: torch.Tensor, *, replicates: int = 2000, seed: int = 0, stratified: bool = False,
+            level: float = 0.95) -> Comparison:
+    """Paired bootstrap comparison of two models on the same rows: both are resampled with the same multiplicities (the rule depends on
+    (seed, replicate, draw, labels) alone), so delta = a - b per replicate is the paired difference.  Per metric: delta_point, delta [R], its
+    percentile interval, and paired_p_value(delta) over the replicates where both sides are defined."""
+    if not isinstance(proba_a, torch.Tensor) or not isinstance(proba_b, torch.Tensor) or tuple(proba_a.shape) != tuple(proba_b.shape):
+        raise GavikoHipError("compare: the two models' probabilities must be device tensors of one shape [N, K]")
+    a = bootstrap(proba_a, labels, replicates=replicates, seed=seed, stratified=stratified, level=level)
+    b = bootstrap(proba_b, labels, replicates=replicates, seed=seed, stratified=stratified, level=level)
+    delta = {k: a.replicates[k] - b.replicates[k] for k in BOOTSTRAP_METRICS}
+    return Comparison(delta_point={k: a.point[k] - b.point[k] for k in BOOTSTRAP_METRICS}, delta=delta,
+                      ci={k: _interval(v, float(level)) for k, v in delta.items()}, p_value={k: paired_p_value(v) for k, v in delta.items()},
+                      a=a, b=b, seed=int(seed), stratified=bool(stratified), level=float(level))
+
+
+_bootstrap = bootstrap                                     # Evaluator.compute has a parameter of that name
+
+
 class Evaluator:
     def __init__(self, num_classes: int, device):
         self.K, self.device = num_classes, device
@@ -82,7 +261,9 @@ class Evaluator:
         self._logits.append(outputs.detach().float())
         self._labels.append(labels.detach().to(torch.int64))
 
-    def compute(self) -> Dict[str, object]:
+    def compute(self, bootstrap: Optional[int] = None, seed: int = 0, stratified: bool = False) -> Dict[str, object]:
+        """bootstrap = R adds "bootstrap" (the BootstrapResult of R replicates with this seed and rule, on the probabilities and predictions
+        computed here) and "report" (classification_report of the confusion matrix); None returns the keys eval.py needs and "calibration"."""
         logits = torch.cat(self._logits).contiguous()
         labels = torch.cat(self._labels).contiguous().to(self.device)
         N, K = logits.shape
@@ -101,9 +282,13 @@ class Evaluator:
             cal: Optional[dict] = calibration(proba, labels)
         except GavikoHipError:                               # labels outside [0, K): the confusion counts skip them, calibration has no term for them
             cal = None
-        return {"accuracy": float(np.trace(conf)) / float(N), "quadratic_kappa": kappa_quadratic(conf), "auc": auc, "confusion": conf,
-                "y_pred": pred.cpu().numpy(), "y_pred_proba": proba.cpu().numpy(), "y_test": labels.cpu().numpy(),
-                "calibration": cal}
+        out = {"accuracy": float(np.trace(conf)) / float(N), "quadratic_kappa": kappa_quadratic(conf), "auc": auc, "confusion": conf,
+               "y_pred": pred.cpu().numpy(), "y_pred_proba": proba.cpu().numpy(), "y_test": labels.cpu().numpy(),
+               "calibration": cal}
+        if bootstrap is not None:
+            out["bootstrap"] = _bootstrap(proba, labels, replicates=bootstrap, seed=seed, stratified=stratified, pred=pred)
+            out["report"] = classification_report(conf)
+        return out
 
 
 def _versioned_csv(results_dir: str, method: str, backbone: str, kind: str, mri_paths, y_pred):

@@ -1304,6 +1304,69 @@ def calibration_bins(proba: torch.Tensor, target: torch.Tensor, nbins: int, out:
     return out
 
 
+# ---- bootstrap replicates of the evaluation metrics (csrc/bootstrap.hip) ----
+BOOTSTRAP_MAX_ROWS = 8192       # gvk_bootstrap_counts: one workgroup keeps the multiplicities and the scan of a replicate in LDS
+BOOTSTRAP_MAX_CLASSES = 64
+
+
+def bootstrap_tables(proba: torch.Tensor, labels: torch.Tensor) -> dict:
+    """The per-call tables of gvk_bootstrap_counts, built with torch on the device (plumbing: once per call, not per replicate).
+    proba f32 [N, K], labels i64 [N] within [0, K) -> order / gstart / gend i32 [K, N] (the rows in ascending order of every class column,
+    stable; per sorted position the bounds of its group of equal scores), class_rows i32 [N], class_off i32 [K + 1] (rows grouped by label)."""
+    N, K = proba.shape
+    vals, order = torch.sort(proba.t().contiguous(), dim=1, stable=True)
+    pos = torch.arange(N, device=proba.device).expand(K, N)
+    step = vals[:, 1:] != vals[:, :-1]
+    edge = torch.ones((K, 1), dtype=torch.bool, device=proba.device)
+    gstart = torch.cummax(torch.where(torch.cat([edge, step], 1), pos, torch.zeros_like(pos)), 1).values
+    gend = torch.cummin(torch.where(torch.cat([step, edge], 1), pos + 1, torch.full_like(pos, N)).flip(1), 1).values.flip(1)
+    off = torch.zeros(K + 1, dtype=torch.int64, device=proba.device)
+    off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
+    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
+    return {"order": i32(order), "gstart": i32(gstart), "gend": i32(gend),
+            "class_rows": i32(torch.sort(labels, stable=True).indices), "class_off": i32(off)}
+
+
+def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, replicates: int, seed: int, stratified: bool,
+                     confusion: torch.Tensor = None, auc_counts: torch.Tensor = None):
+    """R = replicates resamples of the N rows -> (confusion i64 [R, K, K], auc_counts i64 [R, K, 3]), exact integers (include/gaviko_hip.h states
+    the two resampling rules).  labels i64 [N] within [0, K) and pred i32 [N] (the caller's contract, as the tables' values are: the kernel
+    clamps what it reads), tables = bootstrap_tables(proba, labels).  2 <= K <= 64, N <= 8192."""
+    _chk(labels, torch.int64, "bootstrap_counts labels")
+    N = labels.numel()
+    order = tables.get("order")
+    if order is None or order.dim() != 2 or order.shape[1] != N:
+        raise L.GavikoHipError(f"bootstrap_counts order: expected an int32 [K, {N}] table, got {None if order is None else tuple(order.shape)}")
+    K = order.shape[0]
+    _tab(order, "bootstrap_counts order", K * N)
+    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
+        raise L.GavikoHipError(f"bootstrap_counts: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+    if not 2 <= K <= BOOTSTRAP_MAX_CLASSES:
+        raise L.GavikoHipError(f"bootstrap_counts: K = {K} classes outside [2, {BOOTSTRAP_MAX_CLASSES}]")
+    R = replicates
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise L.GavikoHipError(f"bootstrap_counts: replicates = {R!r} (an integer >= 1)")
+    _tab(pred, "bootstrap_counts pred", N)
+    _tab(tables.get("gstart"), "bootstrap_counts gstart", K * N)
+    _tab(tables.get("gend"), "bootstrap_counts gend", K * N)
+    _tab(tables.get("class_rows"), "bootstrap_counts class_rows", N)
+    _tab(tables.get("class_off"), "bootstrap_counts class_off", K + 1)
+    dev = labels.device
+    if confusion is None:
+        confusion = torch.empty((R, K, K), dtype=torch.int64, device=dev)
+    if auc_counts is None:
+        auc_counts = torch.empty((R, K, 3), dtype=torch.int64, device=dev)
+    _chk(confusion, torch.int64, "bootstrap_counts confusion")
+    _chk(auc_counts, torch.int64, "bootstrap_counts auc_counts")
+    if confusion.numel() != R * K * K or auc_counts.numel() != R * K * 3:
+        raise L.GavikoHipError(f"bootstrap_counts: expected confusion [{R}, {K}, {K}] and auc_counts [{R}, {K}, 3], got {tuple(confusion.shape)} and "
+                               f"{tuple(auc_counts.shape)}")
+    L.check(L.load().gvk_bootstrap_counts(L.ptr(labels), L.ptr(pred), L.ptr(tables["order"]), L.ptr(tables["gstart"]), L.ptr(tables["gend"]),
+                                          L.ptr(tables["class_rows"]), L.ptr(tables["class_off"]), L.ptr(confusion), L.ptr(auc_counts), N, K, R,
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0, L.stream_ptr()), "gvk_bootstrap_counts")
+    return confusion, auc_counts
+
+
 # ---- feature embeddings and kNN probes (csrc/features.hip) ----
 FEATURE_MAX_DIM = 1024          # gvk_token_pool / gvk_feature_topk: C % 4 == 0, C <= 1024
 TOPK_MAX_K = 32                 # gvk_feature_topk / gvk_knn_vote: sorted lists of at most 32 entries

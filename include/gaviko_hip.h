@@ -748,6 +748,29 @@ int gvk_predictive_stats(const float* member_logits, float* probs, int32_t* pred
 int gvk_calibration_bins(const float* proba, const void* target, int64_t* count, int64_t* correct, double* conf_sum, double* brier, double* nll,
                          int N, int K, int nbins, void* stream);
 
+/* ---- bootstrap replicates of the evaluation metrics (csrc/bootstrap.hip; gaviko_amd.metrics.bootstrap / compare) ----
+ * gvk_bootstrap_counts: R resamples (with replacement) of the N rows of an evaluation set, each left as the exact integers gvk_eval_rows and
+ *   gvk_ovr_auc_counts leave for the full sample, with integer multiplicities w on the rows:
+ *     confusion int64 [R][K][K]     confusion[b][t][p] = sum of w[b][i] over the rows with (labels[i], pred[i]) = (t, p)
+ *     auc_counts int64 [R][K][3]    {sum over positives i, negatives j of w_i w_j (2 [p_i > p_j] + [p_i == p_j]), weighted n_pos, weighted n_neg}
+ *   Both are written, not accumulated.  Resampling rule, for replicate b and draw n in [0, N), hash_u32 of csrc/dropout.hpp, 64-bit products:
+ *     plain (stratified = 0):       j = (hash_u32(seed, b*N + n) * N) >> 32;                                         w[b][j] += 1
+ *     stratified (stratified = 1):  c = labels[n], n_c = class_off[c+1] - class_off[c],
+ *                                   j = class_rows[class_off[c] + ((hash_u32(seed, b*N + n) * n_c) >> 32)];           w[b][j] += 1
+ *   so every replicate has N draws, the stratified one exactly n_c of them in every class, and a replicate depends on (seed, b, labels) only.
+ *   The scores enter through their order alone, computed once per call by the caller (DEVICE tables, int32):
+ *     order [K][N]                  the rows in ascending order of the class column (a stable sort: equal scores in row order)
+ *     gstart, gend [K][N]           per sorted position, the first and one-past-last sorted position of its group of equal scores
+ *     class_rows [N], class_off [K+1]   the rows grouped by label in ascending row order, and where each class starts (stratified = 1 only)
+ *   labels int64 [N] within [0, K), pred int32 [N] within [0, K) (rows outside are not counted).  One 256-thread workgroup per replicate:
+ *   multiplicities by 32-bit LDS atomics, per class an inclusive scan of the negatives' weights in sorted order and one pass over the
+ *   positives -- O(R K N).  All integer arithmetic: bit-reproducible.  1 <= N <= GVK_BOOTSTRAP_MAX_ROWS, 2 <= K <= GVK_BOOTSTRAP_MAX_CLASSES,
+ *   R >= 1 (one workgroup each; the grid's x dimension).  LDS: 8 * ceil(N / 1024) * 1024 + 4 K^2 bytes. */
+enum { GVK_BOOTSTRAP_MAX_ROWS = 8192, GVK_BOOTSTRAP_MAX_CLASSES = 64 };
+int gvk_bootstrap_counts(const void* labels, const int32_t* pred, const int32_t* order, const int32_t* gstart, const int32_t* gend,
+                         const int32_t* class_rows, const int32_t* class_off, int64_t* confusion, int64_t* auc_counts, int N, int K, int R,
+                         uint64_t seed, int stratified, void* stream);
+
 /* ---- feature embeddings and kNN probes (csrc/features.hip; gaviko_amd/features.py) ----
  * All fp32, no atomics, every sum in a fixed order: two runs are bit-identical.
  * gvk_token_pool: out f32 [B][C], out[b][c] = (1/R) sum_{r in [r0, r0+R)} g[b][r][c] of a token stream g f32 [B][T][C] (row pitch C).
