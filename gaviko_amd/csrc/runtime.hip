@@ -20,6 +20,13 @@ int set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+// A failed HIP API call stays in the runtime's per-thread error word until somebody reads it, and check_launch reads that word after
+// every launch: a path that reports a HIP failure itself drains it here, or the next, perfectly good, call would report it again.
+static int hip_error(hipError_t e, const char* fmt) {
+  (void)hipGetLastError();
+  return set_error(-1, fmt, hipGetErrorString(e));
+}
+
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(-1, "%s: launch failed: %s", what, hipGetErrorString(e));
@@ -153,19 +160,19 @@ extern "C" int gvk_plan_event_elapsed(int plan, int e0, int e1, float* ms) {
   Plan* p = g_plans[plan].get();
   GVK_REQUIRE(e0 >= 0 && e1 >= 0 && e0 < (int)p->events.size() && e1 < (int)p->events.size() && ms, "gvk_plan_event_elapsed: bad event ids");
   hipError_t e = hipEventElapsedTime(ms, p->events[e0], p->events[e1]);
-  if (e != hipSuccess) return set_error(-1, "hipEventElapsedTime: %s (timing needs GAVIKO_HIP_PLAN_TIMING=1 at record time)", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_error(e, "hipEventElapsedTime: %s (timing needs GAVIKO_HIP_PLAN_TIMING=1 at record time)");
   return 0;
 }
 
-static int plan_event_record_impl(void* stream, bool force_sys_fence);
-extern "C" int gvk_plan_event_record(void* stream) { return plan_event_record_impl(stream, false); }
+static int plan_event_record_impl(const char* who, void* stream, bool force_sys_fence);
+extern "C" int gvk_plan_event_record(void* stream) { return plan_event_record_impl("gvk_plan_event_record", stream, false); }
 // The same with the system-scope fence kept: for events that another DEVICE's reads are ordered behind (the gradient buckets an
 // all-reduce sends to peer GPUs over xGMI).
-extern "C" int gvk_plan_event_record_fenced(void* stream) { return plan_event_record_impl(stream, true); }
+extern "C" int gvk_plan_event_record_fenced(void* stream) { return plan_event_record_impl("gvk_plan_event_record_fenced", stream, true); }
 
-static int plan_event_record_impl(void* stream, bool force_sys_fence) {
+static int plan_event_record_impl(const char* who, void* stream, bool force_sys_fence) {
   using namespace gvk;
-  GVK_REQUIRE(g_rec != nullptr, "gvk_plan_event_record: only valid while a plan is being recorded");
+  GVK_REQUIRE(g_rec != nullptr, "%s: only valid while a plan is being recorded", who);
   static const bool env_timing = getenv("GAVIKO_HIP_PLAN_TIMING") != nullptr;  // diagnostics: tools/plan_marks.py
   hipEvent_t ev;
   // Plan events only order streams of ONE device: kernel boundaries already carry the device-scope release/acquire, so the
@@ -174,12 +181,12 @@ static int plan_event_record_impl(void* stream, bool force_sys_fence) {
   static const bool sys_fence = diag_env("GAVIKO_HIP_EVENT_FENCE") != nullptr;
   const unsigned flags = ((env_timing || g_plan_timing) ? hipEventDefault : hipEventDisableTiming) | ((sys_fence || force_sys_fence) ? 0u : hipEventDisableSystemFence);
   hipError_t e = hipEventCreateWithFlags(&ev, flags);
-  if (e != hipSuccess) return set_error(-1, "hipEventCreate: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_error(e, "hipEventCreate: %s");
   g_rec->events.push_back(ev);
   hipStream_t s = (hipStream_t)stream;
   g_rec->nodes.push_back([=]() { (void)hipEventRecord(ev, s); });
   e = hipEventRecord(ev, s);
-  if (e != hipSuccess) return set_error(-1, "hipEventRecord: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_error(e, "hipEventRecord: %s");
   return (int)g_rec->events.size() - 1;
 }
 
@@ -196,7 +203,7 @@ extern "C" int gvk_plan_event_stream_wait(int plan, int event, void* stream) {
     ev = p->events[event];
   }
   hipError_t e = hipStreamWaitEvent((hipStream_t)stream, ev, 0);
-  if (e != hipSuccess) return set_error(-1, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_error(e, "hipStreamWaitEvent: %s");
   return 0;
 }
 
@@ -208,7 +215,7 @@ extern "C" int gvk_plan_event_wait(void* stream, int event) {
   hipStream_t s = (hipStream_t)stream;
   g_rec->nodes.push_back([=]() { (void)hipStreamWaitEvent(s, ev, 0); });
   hipError_t e = hipStreamWaitEvent(s, ev, 0);
-  if (e != hipSuccess) return set_error(-1, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_error(e, "hipStreamWaitEvent: %s");
   return 0;
 }
 

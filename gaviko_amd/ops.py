@@ -141,7 +141,8 @@ def prompt_up_fix_stats(enh, lat, w, out, out16, part, mean, rstd, B, T, P, C_, 
 
 
 def copy_(dst: torch.Tensor, src: torch.Tensor) -> None:
-    """Stream-ordered device copy of src into dst (same dtype, contiguous; dst may be larger)."""
+    """Stream-ordered device copy of src into dst (same dtype, contiguous; dst may be larger): the library's copy kernel
+    (gvk_copy_async), recorded into a launch plan like any other launch."""
     if dst.dtype != src.dtype or not dst.is_contiguous() or not src.is_contiguous() or dst.numel() < src.numel():
         raise L.GavikoHipError("copy_: need contiguous tensors of one dtype with dst at least as large as src")
     L.check(L.load().gvk_copy_async(L.ptr(dst), L.ptr(src), src.numel() * src.element_size(), L.stream_ptr()), "gvk_copy_async")
@@ -186,7 +187,8 @@ def colsum_any(x, out, ones, zeros, junk, scratch, M, N, *, ld=None, rows_in=0, 
 
 
 def memset_zero(t: torch.Tensor) -> None:
-    """Stream-ordered zero fill (hipMemsetAsync through the library so that it is part of a recorded launch plan)."""
+    """Stream-ordered zero fill: the library's fill kernel (gvk_memset_async), recorded into a launch plan like any other launch.
+    The tensor must start 16-byte aligned and span a multiple of 4 bytes."""
     if not t.is_contiguous():
         raise L.GavikoHipError("memset_zero: tensor must be contiguous")
     L.check(L.load().gvk_memset_async(L.ptr(t), 0, t.numel() * t.element_size(), L.stream_ptr()), "gvk_memset_async")

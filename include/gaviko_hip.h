@@ -50,6 +50,7 @@ int gvk_plan_event_stream_wait(int plan, int event, void* stream);
 int gvk_plan_set_timing(int on);
 int gvk_plan_event_elapsed(int plan, int e0, int e1, float* ms);
 /* small stream-ordered utilities the step needs between kernels (recorded into a plan like any launch) */
+/* byte fill by a fill kernel, not a runtime memset: the low byte of `value`; ptr 16-byte aligned, bytes a multiple of 4; 0 does nothing */
 int gvk_memset_async(void* ptr, int value, size_t bytes, void* stream);
 int gvk_seed_advance(void* seed_u64, uint64_t inc, void* stream);   /* device-side dropout epoch += inc */
 int gvk_scale_f32(float* x, float alpha, long n, void* stream);
@@ -143,7 +144,8 @@ int gvk_patchify_f32(const float* img, float* out, int B, int D, int H, int W, i
 int gvk_transpose_f32(const float* in, float* out, int rows, int cols, void* stream);
 int gvk_transpose_bf16(const void* in, void* out, int rows, int cols, void* stream);   /* operand transposes of the unfrozen-backbone wgrad GEMMs */
 int gvk_copy_f32_strided(const float* in, float* out, int M, int C, int ld_in, void* stream);   /* out[M][C] = in[M][ld_in] cols 0..C */
-/* stream-ordered device-to-device copy (recorded into a launch plan like any launch) */
+/* stream-ordered device-to-device copy: a copy kernel, not a runtime memcpy, recorded into a launch plan like any launch.
+ * Both pointers 16-byte aligned, bytes a multiple of 4; bytes == 0 does nothing. */
 int gvk_copy_async(void* dst, const void* src, size_t bytes, void* stream);
 
 /* ------------------------------------------------------------------ casts / layout
