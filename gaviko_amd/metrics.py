@@ -248,6 +248,154 @@ def compare(proba_a: torch.Tensor, proba_b: torch.Tensor, labels: torch.Tensor, 
                       a=a, b=b, seed=int(seed), stratified=bool(stratified), level=float(level))
 
 
+class TemperatureFit(NamedTuple):
+    T: float                               # the fitted temperature, within [t_min, t_max]
+    nll_before: float                      # mean NLL of softmax(logits)
+    nll_after: float                       # mean NLL of softmax(logits / T)
+    ece_before: float                      # calibration(...)["ece"] of softmax(logits)
+    ece_after: float                       # ... of softmax(logits / T)
+    iterations: int                        # Newton / bisection steps taken (0 at a bound)
+    converged: bool
+    at_bound: bool                         # T is t_min or t_max: the NLL still falls (or already rises) at that end of the bracket
+
+    def apply(self, logits: torch.Tensor) -> torch.Tensor:
+        """logits / T: the calibrated logits (softmax of them = the calibrated probabilities; the argmax is the one of `logits`)."""
+        return logits / self.T
+
+
+class RiskCoverage(NamedTuple):
+    thresholds: np.ndarray                 # float32 [G]: the distinct scores, descending -- accept a row when its score >= threshold
+    coverage: np.ndarray                   # float64 [G]: accepted / N at every threshold (ascending, the last is 1)
+    risk: np.ndarray                       # float64 [G]: errors / accepted
+    accepted: np.ndarray                   # int64 [G]
+    errors: np.ndarray                     # int64 [G]
+    aurc: float                            # (1 / N) sum over the thresholds of (rows at the threshold) * risk
+    optimal_aurc: float                    # the aurc of a score that ranks every wrong row below every right one
+    eaurc: float                           # aurc - optimal_aurc
+    at: Dict[float, Tuple[float, float, float]]   # coverage asked for -> (threshold, achieved coverage, risk)
+    replicates: Optional[Dict[str, np.ndarray]]   # "aurc", "risk@<q>": float64 [R] (None without replicates, as ci and stderr are)
+    ci: Optional[Dict[str, Tuple[float, float]]]
+    stderr: Optional[Dict[str, float]]
+    seed: int
+    stratified: bool
+    level: float
+
+
+def optimal_aurc(N: int, E: int) -> float:
+    """The smallest aurc a set of N rows with E wrong ones can have (every wrong row ranked last, no ties): the first N - E thresholds have
+    risk 0, the j-th wrong row is accepted at risk j / (N - E + j):  (1 / N) sum_{j = 1..E} j / (N - E + j), in float64."""
+    j = np.arange(1, int(E) + 1, dtype=np.float64)
+    return float(np.sum(j / (float(N - E) + j)) / float(N))
+
+
+def coverage_need(coverages, N: int) -> List[int]:
+    """Accepted-row counts of the coverages asked for: min(N, max(1, ceil(q N))) with q read as the decimal it prints as, in exact rational
+    arithmetic -- 0.07 * 100 is 7 rows (the float product 7.000000000000001 would round up to 8)."""
+    from fractions import Fraction
+    return [min(int(N), max(1, -((-Fraction(repr(float(q))) * int(N)).__floor__()))) for q in coverages]
+
+
+def fit_temperature(logits: torch.Tensor, labels: torch.Tensor, *, t_min: float = 0.05, t_max: float = 20.0) -> TemperatureFit:
+    """Temperature scaling (Guo et al., 2017): the single T within [t_min, t_max] that minimises the mean NLL of softmax(logits / T), fitted
+    on the device by one launch of gvk_temperature_fit (safeguarded Newton on beta = 1 / T in float64; the NLL is convex in beta).  logits
+    f32 [N, K] on the device, all finite, 2 <= K <= 64; labels [N] within [0, K).  ece_before / ece_after are calibration(...)["ece"] of the
+    probabilities gvk_eval_rows writes for logits and logits / T.
+    Fit on VALIDATION rows and apply to test rows:  fit = fit_temperature(val_logits, val_labels);  test_proba = softmax(fit.apply(test_logits))
+    (or Evaluator.compute(temperature=fit.T)).  A T fitted on the rows it is judged on flatters its own ece_after.  T > 1 softens an
+    overconfident model, T < 1 sharpens an underconfident one; the argmax, and so the accuracy, does not change."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] < 1:
+        raise GavikoHipError(f"fit_temperature: expected logits [N, K], got {tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    N, K = logits.shape
+    if not 2 <= K <= ops.TEMPERATURE_MAX_CLASSES:
+        raise GavikoHipError(f"fit_temperature: K = {K} classes outside [2, {ops.TEMPERATURE_MAX_CLASSES}]")
+    if not 0.0 < float(t_min) < float(t_max) < float("inf"):
+        raise GavikoHipError(f"fit_temperature: need 0 < t_min < t_max, finite (got {t_min!r}, {t_max!r})")
+    if not logits.is_cuda:
+        raise GavikoHipError("fit_temperature: the logits must be a tensor on the HIP device (there is no CPU path)")
+    logits = logits.detach().float().contiguous()
+    labels = torch.as_tensor(labels).to(logits.device).to(torch.int64).contiguous()
+    if labels.numel() != N:
+        raise GavikoHipError(f"fit_temperature: {labels.numel()} labels for {N} rows of logits")
+    if int(labels.min()) < 0 or int(labels.max()) >= K:
+        raise GavikoHipError(f"fit_temperature: labels outside [0, {K})")
+    if not bool(torch.isfinite(logits).all()):
+        raise GavikoHipError("fit_temperature: non-finite logits have no likelihood")
+    st = ops.temperature_fit(logits, labels, t_min, t_max).cpu().numpy()
+    T, flags = float(st[0]), int(st[7])
+
+    def ece(z):
+        proba, pred = torch.empty_like(z), torch.empty(N, dtype=torch.int32, device=z.device)
+        ops.eval_rows(z, labels, proba, pred, torch.zeros(K * K, dtype=torch.int64, device=z.device))
+        return calibration(proba, labels)["ece"]
+
+    return TemperatureFit(T=T, nll_before=float(st[2]), nll_after=float(st[3]), ece_before=ece(logits), ece_after=ece((logits / T).contiguous()),
+                          iterations=int(st[6]), converged=bool(flags & 1), at_bound=bool(flags & 2))
+
+
+def risk_coverage(score: torch.Tensor, labels: torch.Tensor, pred: torch.Tensor, *, coverages=(0.5, 0.8, 0.9, 0.95, 1.0),
+                  replicates: Optional[int] = None, seed: int = 0, stratified: bool = False, level: float = 0.95) -> RiskCoverage:
+    """Selective prediction (Geifman & El-Yaniv, 2017): if the model abstains on its least confident rows, what error is left on the rest?
+    score f32 [N] on the device, HIGHER = MORE CONFIDENT, no NaN -- e.g. proba.max(1).values, -predictive.entropy or -predictive.mutual_info
+    (uncertainty.py); labels [N] >= 0 and pred [N]: a row is wrong when pred != label.  Rows are accepted from the highest score down, rows
+    with EQUAL scores together (nothing depends on the order inside a tie).  Per distinct score (threshold) g: accepted C_g, errors E_g,
+    coverage C_g / N, risk E_g / C_g.
+      aurc = (1 / N) sum_g c_g E_g / C_g  (c_g rows at threshold g: every row is charged the risk at its own threshold; without ties the
+      (1 / N) sum_n E_n / n of the paper),  optimal_aurc(N, E_G) the best any score could do with this many errors,  eaurc their difference
+      at[q] = (threshold, achieved coverage, risk) of the first threshold that accepts at least min(N, max(1, ceil(q N))) rows
+    replicates = R adds bootstrap replicates of aurc and of every risk@q, drawn by the rule of `bootstrap` (same seed and rule = the same
+    resamples, replicate for replicate: they pair with its accuracy / kappa / AUC replicates), with percentile intervals and standard errors.
+    gvk_risk_coverage computes all integers exactly on the device.  N <= 8192, labels < 64, at most 8 coverages, each in (0, 1], ascending."""
+    if not isinstance(score, torch.Tensor) or score.dim() != 1 or score.numel() < 1:
+        raise GavikoHipError(f"risk_coverage: expected score [N], got {tuple(score.shape) if isinstance(score, torch.Tensor) else type(score).__name__}")
+    N = score.numel()
+    if N > ops.BOOTSTRAP_MAX_ROWS:
+        raise GavikoHipError(f"risk_coverage: N = {N} outside N <= {ops.BOOTSTRAP_MAX_ROWS}")
+    cov = [float(q) for q in coverages]
+    if len(cov) > ops.RISK_COVERAGE_MAX_NEEDS:
+        raise GavikoHipError(f"risk_coverage: {len(cov)} coverages (at most {ops.RISK_COVERAGE_MAX_NEEDS})")
+    if any(not 0.0 < q <= 1.0 for q in cov) or any(a > b for a, b in zip(cov, cov[1:])):
+        raise GavikoHipError(f"risk_coverage: coverages = {coverages!r} (ascending, each within (0, 1])")
+    if replicates is not None and (isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1):
+        raise GavikoHipError(f"risk_coverage: replicates = {replicates!r} (None or an integer >= 1)")
+    if not 0.0 < float(level) < 1.0:
+        raise GavikoHipError(f"risk_coverage: level = {level!r} outside (0, 1)")
+    if bool(torch.isnan(score).any()):
+        raise GavikoHipError("risk_coverage: NaN scores have no rank")
+    if not score.is_cuda:
+        raise GavikoHipError("risk_coverage: the scores must be a tensor on the HIP device (there is no CPU path)")
+    score = score.detach().float().contiguous()
+    labels = torch.as_tensor(labels).to(score.device).to(torch.int64).contiguous()
+    pred = torch.as_tensor(pred).to(score.device).to(torch.int32).contiguous()
+    if labels.numel() != N or pred.numel() != N:
+        raise GavikoHipError(f"risk_coverage: {labels.numel()} labels and {pred.numel()} predictions for {N} scores")
+    if int(labels.min()) < 0 or int(labels.max()) >= ops.BOOTSTRAP_MAX_CLASSES:
+        raise GavikoHipError(f"risk_coverage: labels outside [0, {ops.BOOTSTRAP_MAX_CLASSES})")
+    need = coverage_need(cov, N)
+    tables = ops.selective_tables(score, labels)
+    full = ops.risk_coverage_counts(labels, pred, tables, need, resample=False)
+    rep_d = ops.risk_coverage_counts(labels, pred, tables, need, replicates, seed, bool(stratified)) if replicates is not None else None
+    sorted_score, gend = tables["sorted_score"].cpu().numpy(), tables["gend"].cpu().numpy()
+    acc_all, err_all = full["accepted"].cpu().numpy().astype(np.int64), full["errors"].cpu().numpy().astype(np.int64)
+    last = gend == np.arange(1, N + 1)                                    # the last position of every tie group: one entry per distinct score
+    accepted, errors = acc_all[last], err_all[last]
+    at0, E = full["at"].cpu().numpy()[0], int(full["total"].cpu().numpy()[0, 1])
+    aurc = float(full["aurc"].item())
+    opt = optimal_aurc(N, E)
+    # unit multiplicities: the group that first reaches need[q] ends at sorted position C_g - 1
+    at = {q: (float(sorted_score[int(c) - 1]), float(c) / float(N), float(e) / float(c)) for q, (c, e) in zip(cov, at0)}
+    rep = ci = se = None
+    if rep_d is not None:
+        at_r = rep_d["at"].cpu().numpy().astype(np.float64)
+        rep = {"aurc": rep_d["aurc"].cpu().numpy()}
+        for i, q in enumerate(cov):
+            rep[f"risk@{q}"] = at_r[:, i, 1] / at_r[:, i, 0]
+        ci = {k: _interval(v, float(level)) for k, v in rep.items()}
+        se = {k: _stderr(v) for k, v in rep.items()}
+    return RiskCoverage(thresholds=sorted_score[last], coverage=accepted / float(N), risk=errors / accepted.astype(np.float64), accepted=accepted,
+                        errors=errors, aurc=aurc, optimal_aurc=opt, eaurc=aurc - opt, at=at, replicates=rep, ci=ci, stderr=se, seed=int(seed),
+                        stratified=bool(stratified), level=float(level))
+
+
 _bootstrap = bootstrap                                     # Evaluator.compute has a parameter of that name
 
 
@@ -261,9 +409,13 @@ class Evaluator:
         self._logits.append(outputs.detach().float())
         self._labels.append(labels.detach().to(torch.int64))
 
-    def compute(self, bootstrap: Optional[int] = None, seed: int = 0, stratified: bool = False) -> Dict[str, object]:
+    def compute(self, bootstrap: Optional[int] = None, seed: int = 0, stratified: bool = False, *, selective: bool = False,
+                temperature: Optional[float] = None) -> Dict[str, object]:
         """bootstrap = R adds "bootstrap" (the BootstrapResult of R replicates with this seed and rule, on the probabilities and predictions
-        computed here) and "report" (classification_report of the confusion matrix); None returns the keys eval.py needs and "calibration"."""
+        computed here) and "report" (classification_report of the confusion matrix); None returns the keys eval.py needs and "calibration".
+        selective = True adds "selective": the RiskCoverage of the max-probability confidence, with R replicates of the same seed and rule
+        when bootstrap = R.  temperature = T > 0 (fit_temperature on validation rows) takes the probabilities, and with them "auc",
+        "calibration", "bootstrap" and "selective", from logits / T; the predictions and the confusion matrix stay those of the logits."""
         logits = torch.cat(self._logits).contiguous()
         labels = torch.cat(self._labels).contiguous().to(self.device)
         N, K = logits.shape
@@ -272,6 +424,11 @@ class Evaluator:
         confusion = torch.zeros(K * K, dtype=torch.int64, device=self.device)
         counts = torch.zeros(3 * K, dtype=torch.int64, device=self.device)
         ops.eval_rows(logits, labels, proba, pred, confusion)
+        if temperature is not None:
+            T = float(temperature)
+            if not 0.0 < T < float("inf"):
+                raise GavikoHipError(f"Evaluator.compute: temperature = {temperature!r} (a positive, finite number)")
+            ops.eval_rows((logits / T).contiguous(), labels, proba, torch.empty_like(pred), torch.zeros_like(confusion))
         ops.ovr_auc_counts(proba, labels, counts)
         conf = confusion.cpu().numpy().reshape(K, K)
         try:
@@ -288,6 +445,8 @@ class Evaluator:
         if bootstrap is not None:
             out["bootstrap"] = _bootstrap(proba, labels, replicates=bootstrap, seed=seed, stratified=stratified, pred=pred)
             out["report"] = classification_report(conf)
+        if selective:
+            out["selective"] = risk_coverage(proba.max(1).values, labels, pred, replicates=bootstrap, seed=seed, stratified=stratified)
         return out
 
 

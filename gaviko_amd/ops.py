@@ -1369,6 +1369,104 @@ def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, rep
     return confusion, auc_counts
 
 
+# ---- selective prediction and temperature scaling (csrc/selective.hip) ----
+RISK_COVERAGE_MAX_NEEDS = 8     # gvk_risk_coverage: accepted-row counts answered per launch
+TEMPERATURE_MAX_CLASSES = 64    # gvk_temperature_fit
+
+
+def selective_tables(score: torch.Tensor, labels: torch.Tensor) -> dict:
+    """The per-call tables of gvk_risk_coverage, built with torch on the device (plumbing: once per call, not per replicate).
+    score f32 [N] (higher = more confident, no NaN), labels i64 [N] >= 0 -> order i32 [N] (the rows by descending score, stable), gend i32 [N]
+    (per sorted position, one past the end of its group of equal scores), class_rows i32 [N] / class_off i32 [K + 1] (the rows grouped by
+    label, as ops.bootstrap_tables has them; K = the largest label + 1) and sorted_score f32 [N] (score[order], for the thresholds)."""
+    N = score.numel()
+    vals, order = torch.sort(score.reshape(N), descending=True, stable=True)
+    pos = torch.arange(N, device=score.device)
+    edge = torch.ones(1, dtype=torch.bool, device=score.device)
+    last = torch.cat([vals[1:] != vals[:-1], edge])
+    gend = torch.cummin(torch.where(last, pos + 1, torch.full_like(pos, N)).flip(0), 0).values.flip(0)
+    K = int(labels.max()) + 1 if N else 1
+    off = torch.zeros(K + 1, dtype=torch.int64, device=score.device)
+    off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
+    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
+    return {"order": i32(order), "gend": i32(gend), "class_rows": i32(torch.sort(labels, stable=True).indices), "class_off": i32(off),
+            "sorted_score": vals.contiguous()}
+
+
+def risk_coverage_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, need=(), replicates: int = 1, seed: int = 0,
+                         stratified: bool = False, resample: bool = True) -> dict:
+    """The risk-coverage integers of `replicates` resamples (resample=True: the multiplicities of gvk_bootstrap_counts for the same seed and
+    rule) or of the full sample (resample=False, replicates must be 1, which also writes the curve); include/gaviko_hip.h has the
+    definitions.  labels i64 [N], pred i32 [N], tables = selective_tables(score, labels); need: up to 8 host integers within [1, N], ascending
+    (accepted-row counts).  -> dict of device tensors: aurc f64 [R], at i32 [R, Q, 2], total i32 [R, 2] and, with resample=False, accepted /
+    errors i32 [N] (per sorted position the running (accepted, wrong) counts at the end of its tie group).  N <= 8192."""
+    N = labels.numel()
+    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
+        raise L.GavikoHipError(f"risk_coverage_counts: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+    R = replicates
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise L.GavikoHipError(f"risk_coverage_counts: replicates = {R!r} (an integer >= 1)")
+    if not resample and R != 1:
+        raise L.GavikoHipError(f"risk_coverage_counts: resample=False is the full sample, replicates = {R} must be 1")
+    need = [n for n in need]
+    Q = len(need)
+    if Q > RISK_COVERAGE_MAX_NEEDS:
+        raise L.GavikoHipError(f"risk_coverage_counts: Q = {Q} accepted-row counts (at most {RISK_COVERAGE_MAX_NEEDS} per launch)")
+    if any(isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= N for n in need) or any(a > b for a, b in zip(need, need[1:])):
+        raise L.GavikoHipError(f"risk_coverage_counts: need = {need!r} (ascending integers within [1, {N}])")
+    class_off = tables.get("class_off")
+    if class_off is None or class_off.numel() < 2:
+        raise L.GavikoHipError("risk_coverage_counts class_off: expected an int32 [K + 1] table, K >= 1")
+    K = class_off.numel() - 1
+    if K > BOOTSTRAP_MAX_CLASSES:
+        raise L.GavikoHipError(f"risk_coverage_counts: K = {K} classes outside [1, {BOOTSTRAP_MAX_CLASSES}]")
+    _chk(labels, torch.int64, "risk_coverage_counts labels")
+    _tab(pred, "risk_coverage_counts pred", N)
+    _tab(tables.get("order"), "risk_coverage_counts order", N)
+    _tab(tables.get("gend"), "risk_coverage_counts gend", N)
+    _tab(tables.get("class_rows"), "risk_coverage_counts class_rows", N)
+    _tab(class_off, "risk_coverage_counts class_off", K + 1)
+    dev = labels.device
+    out = {"aurc": torch.empty(R, dtype=torch.float64, device=dev), "at": torch.empty((R, Q, 2), dtype=torch.int32, device=dev),
+           "total": torch.empty((R, 2), dtype=torch.int32, device=dev)}
+    if not resample:
+        out["accepted"] = torch.empty(N, dtype=torch.int32, device=dev)
+        out["errors"] = torch.empty(N, dtype=torch.int32, device=dev)
+    need_d = torch.tensor(need, dtype=torch.int32, device=dev) if Q else None
+    L.check(L.load().gvk_risk_coverage(L.ptr(labels), L.ptr(pred), L.ptr(tables["order"]), L.ptr(tables["gend"]), L.ptr(tables["class_rows"]),
+                                       L.ptr(class_off), L.ptr(need_d), L.ptr(out["aurc"]), L.ptr(out["at"]) if Q else None, L.ptr(out["total"]),
+                                       L.ptr(out.get("accepted")), L.ptr(out.get("errors")), N, K, Q, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       1 if stratified else 0, 1 if resample else 0, L.stream_ptr()), "gvk_risk_coverage")
+    return out
+
+
+def temperature_fit(logits: torch.Tensor, target: torch.Tensor, t_min: float = 0.05, t_max: float = 20.0, state: torch.Tensor = None) -> torch.Tensor:
+    """logits f32 [N, K] (finite: the caller's contract), target i64 [N] within [0, K) -> state f64 [8] on the device = (T, beta = 1 / T,
+    nll_before, nll_after, f', f'', iterations, flags: bit 0 converged, bit 1 at_bound): the temperature within [t_min, t_max] that minimises
+    the mean NLL of softmax(logits / T), by one launch of gvk_temperature_fit (include/gaviko_hip.h).  2 <= K <= 64."""
+    if logits.dim() != 2 or logits.shape[0] < 1:
+        raise L.GavikoHipError(f"temperature_fit logits: expected [N, K], got {tuple(logits.shape)}")
+    N, K = logits.shape
+    if not 2 <= K <= TEMPERATURE_MAX_CLASSES:
+        raise L.GavikoHipError(f"temperature_fit: K = {K} classes outside [2, {TEMPERATURE_MAX_CLASSES}]")
+    if N >= 1 << 31:
+        raise L.GavikoHipError(f"temperature_fit: N = {N} rows exceed the kernel's 32-bit row index")
+    if target.numel() != N:
+        raise L.GavikoHipError(f"temperature_fit target: expected {N} labels, got {tuple(target.shape)}")
+    t_min, t_max = float(t_min), float(t_max)
+    if not 0.0 < t_min < t_max < float("inf"):
+        raise L.GavikoHipError(f"temperature_fit: need 0 < t_min < t_max, finite (got {t_min!r}, {t_max!r})")
+    _chk(logits, torch.float32, "temperature_fit logits")
+    _chk(target, torch.int64, "temperature_fit target")
+    if state is None:
+        state = torch.empty(8, dtype=torch.float64, device=logits.device)
+    _chk(state, torch.float64, "temperature_fit state")
+    if state.numel() != 8:
+        raise L.GavikoHipError(f"temperature_fit state: expected 8 entries, got {tuple(state.shape)}")
+    L.check(L.load().gvk_temperature_fit(L.ptr(logits), L.ptr(target), L.ptr(state), N, K, t_min, t_max, L.stream_ptr()), "gvk_temperature_fit")
+    return state
+
+
 # ---- feature embeddings and kNN probes (csrc/features.hip) ----
 FEATURE_MAX_DIM = 1024          # gvk_token_pool / gvk_feature_topk: C % 4 == 0, C <= 1024
 TOPK_MAX_K = 32                 # gvk_feature_topk / gvk_knn_vote: sorted lists of at most 32 entries

@@ -773,6 +773,46 @@ int gvk_bootstrap_counts(const void* labels, const int32_t* pred, const int32_t*
                          const int32_t* class_rows, const int32_t* class_off, int64_t* confusion, int64_t* auc_counts, int N, int K, int R,
                          uint64_t seed, int stratified, void* stream);
 
+/* ---- selective prediction and temperature scaling (csrc/selective.hip; gaviko_amd.metrics.risk_coverage / fit_temperature) ----
+ * gvk_risk_coverage: the risk-coverage curve of a confidence score (Geifman & El-Yaniv, 2017) for R replicates of the N rows of an
+ *   evaluation set.  labels int64 [N], pred int32 [N]: a row is WRONG when pred != label.  The scores enter through their order alone, computed
+ *   once per call by the caller (DEVICE tables, int32):
+ *     order [N]                     the rows by DESCENDING score (a stable sort: equal scores in row order)
+ *     gend [N]                      per sorted position, one past the last sorted position of its group of equal scores
+ *     class_rows [N], class_off [K+1]   the tables of gvk_bootstrap_counts, K = the number of label classes (read with resample = 1 and
+ *                                   stratified = 1 only; 1 <= K <= GVK_BOOTSTRAP_MAX_CLASSES there, labels clamped into [0, K))
+ *     need [Q]                      accepted-row counts within [1, N], ascending (clamped into [1, N]); 0 <= Q <= GVK_RISK_COVERAGE_MAX_NEEDS
+ *   Multiplicities w on the rows: resample = 1 draws replicate b exactly as gvk_bootstrap_counts does (hash_u32(seed, b*N + n), plain or
+ *   stratified, see above), so replicate b here and there is the same resample; resample = 0 requires R = 1 and gives every row w = 1.
+ *   Ties are accepted together.  For the sorted groups g = 1..G: c_g = summed w of group g, e_g = summed w of its wrong rows, C_g and E_g their
+ *   running sums; a group with c_g = 0 is not a threshold.  Written per replicate b, not accumulated:
+ *     aurc f64 [R]                  (1/N) sum over g with c_g > 0 of c_g E_g / C_g  -- every row is charged the risk at its own threshold; for
+ *                                   unit multiplicities and no ties (1/N) sum_n E_n / n.  Terms c_g E_g / C_g carry one rounding each and are
+ *                                   added in a fixed order (thread t the groups starting at t, t + 256, ..; a wave's xor butterfly; the 4 waves)
+ *     at int32 [R][Q][2]            (C_g, E_g) of the first group with C_g >= need[q]
+ *     total int32 [R][2]            (C_G, E_G); C_G = N
+ *     accepted, errors int32 [N]    resample = 0 only (else NULL; both or neither): per sorted position the (C_g, E_g) of its group
+ *   One 256-thread workgroup per replicate; multiplicities by 32-bit LDS atomics, no atomics on global memory; one packed inclusive scan
+ *   (w << 16 | wrong w) in tiles of 1024.  The integers are exact, aurc has the same bits on every run.  1 <= N <= GVK_BOOTSTRAP_MAX_ROWS,
+ *   R >= 1 (the grid's x dimension).  LDS: 8 * ceil(N / 1024) * 1024 bytes.
+ * gvk_temperature_fit: temperature scaling (Guo et al., 2017).  logits f32 [N][K], target int64 [N] within [0, K).  Minimises the mean NLL
+ *   f(beta) of softmax(beta z) over beta = 1 / T in [1 / t_max, 1 / t_min]; f is convex in beta:
+ *     f'(beta) = mean_n (sum_k p_nk z_nk - z_n,y)        f''(beta) = mean_n Var_{p_n}(z_n) >= 0
+ *   f'(1 / t_min) <= 0: the answer is t_min; else f'(1 / t_max) >= 0: the answer is t_max (both flagged at_bound).  Otherwise safeguarded
+ *   Newton from beta = 1 (clamped into the bracket): the sign of f' shrinks the bracket, a step that leaves it (or f'' = 0) is replaced by
+ *   a bisection step; stop at |delta beta| <= 2^-40 beta (the step taken, or the Newton step proposed next), at f' = 0, or after 64 iterations.
+ *     state f64 [8] = { T, beta, nll_before (beta = 1), nll_after, f', f'' (both at the returned beta), iterations, flags }
+ *     flags: bit 0 converged (set with at_bound too: the bound is the constrained minimiser), bit 1 at_bound
+ *   One 1024-thread workgroup, one launch, no host read between iterations.  All arithmetic in float64, the row maximum subtracted before
+ *   exp; every sum in a fixed order (thread t the rows t, t + 1024, ..; a wave's xor butterfly; the 16 waves in order): the same bits on
+ *   every run.  N >= 1, 2 <= K <= GVK_TEMPERATURE_MAX_CLASSES, 0 < t_min < t_max.  A row with a non-finite logit is the caller's contract
+ *   (the fit then ends after 64 iterations with a NaN state). */
+enum { GVK_RISK_COVERAGE_MAX_NEEDS = 8, GVK_TEMPERATURE_MAX_CLASSES = 64 };
+int gvk_risk_coverage(const void* labels, const int32_t* pred, const int32_t* order, const int32_t* gend, const int32_t* class_rows,
+                      const int32_t* class_off, const int32_t* need, double* aurc, int32_t* at, int32_t* total, int32_t* accepted,
+                      int32_t* errors, int N, int K, int Q, int R, uint64_t seed, int stratified, int resample, void* stream);
+int gvk_temperature_fit(const float* logits, const void* target, double* state, int N, int K, double t_min, double t_max, void* stream);
+
 /* ---- feature embeddings and kNN probes (csrc/features.hip; gaviko_amd/features.py) ----
  * All fp32, no atomics, every sum in a fixed order: two runs are bit-identical.
  * gvk_token_pool: out f32 [B][C], out[b][c] = (1/R) sum_{r in [r0, r0+R)} g[b][r][c] of a token stream g f32 [B][T][C] (row pitch C).
