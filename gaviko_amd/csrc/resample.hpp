@@ -1,5 +1,5 @@
-// Resampling arithmetic shared by the kernels that read a volume through a 3x4 map (augment.hip: gvk_spatial_transform; motion.hip:
-// gvk_motion_artifact) and the reduction of the volume_minmax partials that gives them their pad value.  One definition, so both kernels
+// Resampling arithmetic shared by the kernels that read a volume at computed positions (through a 3x4 map: augment.hip,
+// gvk_spatial_transform, and motion.hip, gvk_motion_artifact; through a displacement field: elastic.hip, gvk_elastic_deform) and the reduction of the volume_minmax partials that gives them their pad value.  One definition, so all of them
 // round exactly alike: the spatial transform's pinned bits are this function's.
 #pragma once
 #include "common.hpp"
@@ -22,13 +22,9 @@ __device__ __forceinline__ void reduce_partials(const float* part, int b, float&
   lo = rlo[0]; hi = rhi[0];
 }
 
-// src [D][H][W] sampled at p = A q + t (m = row-major 3x4 [A | t], array-axis order: axis 0 = depth), trilinear; neighbours outside the
-// volume read `pad`
-__device__ __forceinline__ float trilinear_sample(const float* __restrict__ src, const float* __restrict__ m, float qz, float qy, float qx, int D, int H,
-                                                  int W, float pad) {
-  const float pz = m[0] * qz + m[1] * qy + m[2] * qx + m[3];
-  const float py = m[4] * qz + m[5] * qy + m[6] * qx + m[7];
-  const float px = m[8] * qz + m[9] * qy + m[10] * qx + m[11];
+// src [D][H][W] read at the position (pz, py, px) in voxels (array-axis order: axis 0 = depth), trilinear; neighbours outside the volume
+// read `pad`
+__device__ __forceinline__ float trilinear_at(const float* __restrict__ src, float pz, float py, float px, int D, int H, int W, float pad) {
   const float fz = floorf(pz), fy = floorf(py), fx = floorf(px);
   const int iz = (int)fz, iy = (int)fy, ix = (int)fx;
   const float wz = pz - fz, wy = py - fy, wx = px - fx;
@@ -46,6 +42,15 @@ __device__ __forceinline__ float trilinear_sample(const float* __restrict__ src,
         acc += w * v;
       }
   return acc;
+}
+
+// src sampled at p = A q + t (m = row-major 3x4 [A | t], array-axis order)
+__device__ __forceinline__ float trilinear_sample(const float* __restrict__ src, const float* __restrict__ m, float qz, float qy, float qx, int D, int H,
+                                                  int W, float pad) {
+  const float pz = m[0] * qz + m[1] * qy + m[2] * qx + m[3];
+  const float py = m[4] * qz + m[5] * qy + m[6] * qx + m[7];
+  const float px = m[8] * qz + m[9] * qy + m[10] * qx + m[11];
+  return trilinear_at(src, pz, py, px, D, H, W, pad);
 }
 
 }  // namespace gvk

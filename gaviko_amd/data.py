@@ -26,6 +26,13 @@ array axes, and RandomMotion's movements use this module's RandomAffine conventi
 spacing 1) and are not demeaned: same distributions, not the same voxels for the same seed.  Parity vs torchio is UNPINNED here as well;
 the kernels are pinned against scipy.ndimage.gaussian_filter, a numpy restatement (`tests/intensity_ref.py`) and torchio's compositing
 written literally with np.fft (`tests/motion_ref.py`).
+
+RandomElasticDeformation (not in the reference's Compose; torchio's documented companion of RandomAffine, `train_transforms(elastic=True)`)
+is one more resampling kernel (`csrc/elastic.hip`): ITK's order-3 B-spline transform over the image extent, evaluated separably, and the
+trilinear read of the affine pass.  It keeps torchio's signature, sampling and errors; its axes are the array axes, displacements are in
+voxels, the locked borders are zeroed on all three axes, and inside DeviceCompose it always runs before the affine/flip pass: same
+distributions, not the same voxels for the same seed.  Parity vs torchio / SimpleITK is UNPINNED; the kernel is pinned against a float64
+restatement (`tests/elastic_ref.py`) that is itself checked against scipy.ndimage.map_coordinates.
 """
 from __future__ import annotations
 
@@ -140,6 +147,69 @@ def affine_matrix(scales, degrees, translation, shape) -> np.ndarray:
     return np.concatenate([A, t[:, None]], axis=1)
 
 
+def _triple(v, name, kind):
+    if isinstance(v, (int, float)):
+        return (kind(v),) * 3
+    v = tuple(kind(t) for t in v)
+    if len(v) != 3:
+        raise ValueError(f"{name}: a number or one value per array axis")
+    return v
+
+
+class RandomElasticDeformation:
+    """tio.RandomElasticDeformation(num_control_points=7, max_displacement=7.5, locked_borders=2, image_interpolation='linear', p=1): a
+    random displacement on a coarse grid of control points, interpolated with cubic B-splines (`csrc/elastic.hip`).  num_control_points and
+    max_displacement are a number or one value per array axis; displacements are in voxels (the reference's arrays have spacing 1).
+    locked_borders = 1 zeroes the outermost layer of control points on every axis, 2 the outer two layers.  Draws: one uniform for p, then
+    n0 n1 n2 3 uniforms in grid order, u -> (u - 0.5) 2 max_a for component a."""
+
+    def __init__(self, num_control_points=7, max_displacement=7.5, locked_borders: int = 2, image_interpolation: str = "linear", p: float = 1.0):
+        self.num_control_points = _triple(num_control_points, "num_control_points", int)
+        self.max_displacement = _triple(max_displacement, "max_displacement", float)
+        if any(n < 4 for n in self.num_control_points):
+            raise ValueError(f"RandomElasticDeformation: at least 4 control points per axis (cubic B-splines), not {self.num_control_points}")
+        if any(m < 0 for m in self.max_displacement):
+            raise ValueError("RandomElasticDeformation: max_displacement is non-negative")
+        if locked_borders not in (0, 1, 2):
+            raise ValueError("RandomElasticDeformation: locked_borders is 0, 1 or 2")
+        if locked_borders == 2 and 4 in self.num_control_points:
+            raise ValueError("RandomElasticDeformation: locked_borders = 2 with 4 control points on an axis zeroes them all (an identity transform); "
+                             "use more control points or locked_borders 0 or 1")
+        if image_interpolation != "linear":
+            raise NotImplementedError("RandomElasticDeformation: only image_interpolation='linear' is built")
+        if any(n > ops.ELASTIC_MAX_CONTROL_POINTS for n in self.num_control_points):
+            raise NotImplementedError(f"RandomElasticDeformation: 4..{ops.ELASTIC_MAX_CONTROL_POINTS} control points per axis are built")
+        self.locked_borders, self.p = int(locked_borders), float(p)
+        self._checked_shape = None
+
+    def check_folding(self, shape) -> None:
+        """torchio's folding warning, once the shape is known (DeviceCompose calls this on its first batch): a displacement of half a mesh
+        cell h_a = S_a / (n_a - 3) or more can fold the volume over itself."""
+        if self._checked_shape is not None:
+            return
+        self._checked_shape = tuple(shape)
+        spacing = [S / (n - 3) for S, n in zip(shape, self.num_control_points)]
+        if any(m >= h / 2 for m, h in zip(self.max_displacement, spacing)):
+            import warnings
+            warnings.warn(f"RandomElasticDeformation: max_displacement {self.max_displacement} is not below half the control-point spacing "
+                          f"{tuple(round(h, 4) for h in spacing)} on every axis (volume {tuple(shape)}, {self.num_control_points} control points): "
+                          "the deformation may fold the volume", RuntimeWarning, stacklevel=2)
+
+    def sample(self, rng: np.random.Generator):
+        """None (not applied) or the coarse field float64 [n0][n1][n2][3], locked borders already zero."""
+        if rng.random() >= self.p:
+            return None
+        coarse = (rng.random(self.num_control_points + (3,)) - 0.5) * 2.0 * np.asarray(self.max_displacement, dtype=np.float64)
+        for i in range(self.locked_borders):
+            for a in range(3):
+                layers = np.moveaxis(coarse, a, 0)                          # a view
+                layers[i], layers[-1 - i] = 0.0, 0.0
+        return coarse
+
+
+SPATIAL_ONE_OF_MEMBERS = (RandomAffine, RandomElasticDeformation)
+
+
 class RescaleIntensity:
     """tio.RescaleIntensity(out_min_max): per-volume min-max to [out_min, out_max] (percentiles (0,100), no mask)."""
 
@@ -233,20 +303,22 @@ class RandomMotion:
 
 INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion)
 _BUILT = ("RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, RandomMotion, OneOf of the last four, "
-          "RescaleIntensity (at most one)")
+          "RescaleIntensity (at most one); RandomElasticDeformation (at most one), OneOf of RandomAffine and RandomElasticDeformation in place of "
+          "the two")
 
 
 class OneOf:
     """tio.OneOf(transforms, p=1): with probability p exactly one member is applied, chosen by weight (a dict transform -> weight, or a
     sequence with equal weights; weights are normalised).  The member's own p still applies.  Draws: one uniform for p, one for the choice,
-    then the member's."""
+    then the member's.  The members are all intensity transforms, or all spatial ones (RandomAffine, RandomElasticDeformation: `spatial` is
+    then True and `sample` returns None or (member, the member's draw))."""
 
     def __init__(self, transforms, p: float = 1.0):
         items = list(transforms.items()) if isinstance(transforms, dict) else [(t, 1.0) for t in transforms]
         if not items:
             raise ValueError("OneOf: at least one transform")
         for t, w in items:
-            if not isinstance(t, INTENSITY_TRANSFORMS):
+            if not isinstance(t, INTENSITY_TRANSFORMS + SPATIAL_ONE_OF_MEMBERS):
                 raise NotImplementedError(f"OneOf: {type(t).__name__} is not built on the device ({_BUILT})")
             if w < 0:
                 raise ValueError("OneOf: weights are non-negative")
@@ -254,6 +326,10 @@ class OneOf:
         if total <= 0:
             raise ValueError("OneOf: the weights sum to zero")
         self.transforms = [t for t, _ in items]
+        self.spatial = isinstance(self.transforms[0], SPATIAL_ONE_OF_MEMBERS)
+        if any(isinstance(t, SPATIAL_ONE_OF_MEMBERS) != self.spatial for t in self.transforms):
+            raise NotImplementedError("OneOf: spatial (RandomAffine, RandomElasticDeformation) and intensity members in one OneOf are not built: "
+                                      "the spatial transforms run as passes of their own before the intensity ones")
         self.weights = np.array([w / total for _, w in items], dtype=np.float64)
         self.p = float(p)
 
@@ -261,7 +337,8 @@ class OneOf:
         if rng.random() >= self.p:
             return None
         i = min(int(np.searchsorted(np.cumsum(self.weights), rng.random(), side="right")), len(self.transforms) - 1)
-        return self.transforms[i].sample(rng)
+        draw = self.transforms[i].sample(rng)
+        return (self.transforms[i], draw) if self.spatial else draw
 
 
 def blur_tables(sigmas):
@@ -318,21 +395,31 @@ def motion_tables(times, W: int):
 
 
 class DeviceCompose:
-    """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Spatial transforms are merged
+    """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Affine and flips are merged
     into one resampling pass (affine first, flips on its output), the intensity transforms (singly or inside OneOf) follow in listed
-    order, RescaleIntensity runs last, as in the reference's Compose.  Per sample the random draws are: affine, flips, then every
-    intensity transform in listed order; with no intensity transform listed the consumed stream is what it was before they existed."""
+    order, RescaleIntensity runs last, as in the reference's Compose.  RandomElasticDeformation is a resampling pass of its own BEFORE the
+    affine/flip pass wherever it is listed: torchio would apply the spatial transforms in listed order, here elastic always runs first
+    (a sample that draws both is interpolated twice, as in torchio).  A OneOf of RandomAffine / RandomElasticDeformation members may stand
+    in place of the single affine and/or elastic: each sample then gets at most one of them.  Per sample the random draws are: elastic,
+    affine (or the spatial OneOf in their place), flips, then every intensity transform in listed order; a compose that lists no elastic
+    transform and no spatial OneOf consumes the stream it consumed before they existed."""
 
     def __init__(self, transforms: Sequence, seed: Optional[int] = None):
         self.affine = [t for t in transforms if isinstance(t, RandomAffine)]
+        self.elastic = [t for t in transforms if isinstance(t, RandomElasticDeformation)]
+        self.spatial = [t for t in transforms if isinstance(t, OneOf) and t.spatial]     # in place of the single affine and/or elastic
         self.flips = [t for t in transforms if isinstance(t, RandomFlip)]
         self.rescale = [t for t in transforms if isinstance(t, RescaleIntensity)]
-        self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS + (OneOf,))]
-        if len(self.affine) > 1 or len(self.rescale) > 1 or \
-                len(self.affine) + len(self.flips) + len(self.rescale) + len(self.intensity) != len(transforms):
+        self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS) or (isinstance(t, OneOf) and not t.spatial)]
+        elastic = self.elastic + [t for one in self.spatial for t in one.transforms if isinstance(t, RandomElasticDeformation)]
+        if len(self.affine) > 1 or len(self.rescale) > 1 or len(elastic) > 1 or len(self.spatial) > 1 or \
+                (self.spatial and (self.affine or self.elastic)) or \
+                len(self.affine) + len(self.elastic) + len(self.spatial) + len(self.flips) + len(self.rescale) + len(self.intensity) != len(transforms):
             raise NotImplementedError(f"DeviceCompose: {_BUILT}; anything else is not built")
+        self._elastic = elastic[0] if elastic else None                   # the one elastic transform, listed singly or inside the spatial OneOf
         self.rng = np.random.default_rng(seed)
         self.last_params = None                                           # [(flip bits, affine params or None)] of the last call: tests, logging
+        self.last_elastic = None                                          # per sample None or the coarse field float64 [n0][n1][n2][3], borders locked
         # the intensity draws of the last call, one entry per sample: None or (class name, params) -- with several intensity transforms
         # listed, a tuple of such entries in listed order
         self.last_intensity = None
@@ -340,9 +427,17 @@ class DeviceCompose:
     def sample(self, B: int, shape):
         mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, 1, 1))
         flags = np.zeros(B, dtype=np.int32)
-        params, draws = [], []
+        params, draws, fields = [], [], []
+        if self._elastic is not None:
+            self._elastic.check_folding(shape)
         for b in range(B):
-            aff = self.affine[0].sample(self.rng) if self.affine else None
+            if self.spatial:
+                pick = self.spatial[0].sample(self.rng) or (None, None)
+                el, aff = (None, pick[1]) if isinstance(pick[0], RandomAffine) else (pick[1], None)
+            else:
+                el = self.elastic[0].sample(self.rng) if self.elastic else None
+                aff = self.affine[0].sample(self.rng) if self.affine else None
+            fields.append(el)
             bits = 0
             for f in self.flips:
                 bits ^= f.sample(self.rng)
@@ -353,7 +448,7 @@ class DeviceCompose:
             params.append((bits & 7, aff))
             d = tuple(t.sample(self.rng) for t in self.intensity)
             draws.append(d[0] if len(d) == 1 else (d or None))
-        self.last_params, self.last_intensity = params, draws
+        self.last_params, self.last_intensity, self.last_elastic = params, draws, fields
         return mats, flags
 
     def _intensity_stage(self, x: torch.Tensor, draws) -> torch.Tensor:
@@ -409,8 +504,18 @@ class DeviceCompose:
             x = x.float().contiguous()
         B, shape = x.shape[0], tuple(x.shape[-3:])
         part = ops.minmax_partials(B, x.device)
-        if self.affine or self.flips or self.intensity:
+        if self.affine or self.elastic or self.spatial or self.flips or self.intensity:
             mats, flags = self.sample(B, shape)
+            if any(f is not None for f in self.last_elastic):             # elastic first, a pass of its own (class docstring)
+                ctrl = np.zeros((B,) + self._elastic.num_control_points + (3,), dtype=np.float32)
+                live = np.zeros(B, dtype=np.int32)
+                for b, f in enumerate(self.last_elastic):
+                    if f is not None:
+                        ctrl[b], live[b] = f, 1
+                ops.volume_minmax(x, part)                                # pad value = this pass's input minimum
+                out = torch.empty_like(x)
+                ops.elastic_deform(x, out, torch.from_numpy(ctrl).to(x.device), torch.from_numpy(live).to(x.device), part)
+                x = out
             if flags.any():
                 ops.volume_minmax(x, part)                                # pad value of the resampling = the input volume's minimum
                 out = torch.empty_like(x)
@@ -426,14 +531,16 @@ class DeviceCompose:
         return x
 
 
-def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False) -> DeviceCompose:
+def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False, elastic: bool = False) -> DeviceCompose:
     """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
     line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device, with
     the three members this package had first (RandomMotion's 0.25 spread over them); motion=True as well makes it the reference's dict
-    as declared, four members at 0.25."""
+    as declared, four members at 0.25.  elastic=True (not in the reference) replaces the affine by torchio's documented recipe, the affine
+    in 0.8 and RandomElasticDeformation() in 0.2 of the samples that the group's p = 0.5 selects."""
     if motion and not intensity:
         raise ValueError("train_transforms: motion=True adds RandomMotion to the intensity group and needs intensity=True")
-    spatial = [RandomAffine(degrees=15, p=0.5), RandomFlip(axes=(0,), flip_probability=0.5)]
+    affine = OneOf({RandomAffine(degrees=15): 0.8, RandomElasticDeformation(): 0.2}, p=0.5) if elastic else RandomAffine(degrees=15, p=0.5)
+    spatial = [affine, RandomFlip(axes=(0,), flip_probability=0.5)]
     group = {RandomNoise(): 1, RandomBiasField(): 1, RandomBlur(std=(0, 1.5)): 1}
     if motion:
         group = {RandomNoise(): 0.25, RandomBiasField(): 0.25, RandomBlur(std=(0, 1.5)): 0.25, RandomMotion(): 0.25}
@@ -450,13 +557,15 @@ class DataPreprocessor:
     """train.py:33-78: same CSV columns (`subset`, `mri_path`, `kl_grade`), same loaders and return tuple; the transforms are the
     device-side `train_transforms` / `val_transforms` attributes to call on each batch after `.to(device)`.  config['data']['intensity_augment']
     (default False) adds the intensity OneOf of `train_transforms(intensity=True)`, config['data']['motion_augment'] (default False)
-    RandomMotion to it (`motion=True`)."""
+    RandomMotion to it (`motion=True`), config['data']['elastic_augment'] (default False) puts the affine / elastic OneOf of
+    `train_transforms(elastic=True)` in place of the affine."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
         intensity = bool(config["data"].get("intensity_augment", False))
         motion = bool(config["data"].get("motion_augment", False))
-        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity, motion), eval_transforms(), eval_transforms()
+        elastic = bool(config["data"].get("elastic_augment", False))
+        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity, motion, elastic), eval_transforms(), eval_transforms()
 
     def preprocess(self, df=None):
         import pandas as pd

@@ -185,6 +185,7 @@ SIGNATURES = {
     "gvk_gaussian_blur3d": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_intensity_pointwise": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "gvk_motion_artifact": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "gvk_elastic_deform": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gvk_eval_rows": [_P, _P, _P, _P, _P, _I, _I, _P],
     "gvk_ovr_auc_counts": [_P, _P, _P, _I, _I, _P],
     "gvk_memset_async": [_P, _I, C.c_size_t, _P],

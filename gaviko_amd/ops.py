@@ -1189,6 +1189,31 @@ def motion_artifact(x, out, mats, ctab, live, partials, K) -> None:
             "gvk_motion_artifact")
 
 
+ELASTIC_MAX_CONTROL_POINTS = 16                                           # GVK_ELASTIC_MAX_CONTROL_POINTS
+
+
+def elastic_deform(x, out, ctrl, live, partials, field=None) -> None:
+    """tio.RandomElasticDeformation in one pass: out[b] at voxel q = x[b] read (trilinear, pad = the volume minimum) at q + d(q), d the cubic
+    B-spline interpolation of the control-point displacements ctrl f32 [B][n0][n1][n2][3] (voxels, component a along array axis a; 4..16
+    points per axis).  live i32 [B]: a sample with 0 is copied bit for bit; partials = volume_minmax of x; field (optional) f32
+    [B][3][D][H][W] receives d.  out must not overlap x."""
+    _chk(x, torch.float32, "elastic_deform in")
+    _chk(out, torch.float32, "elastic_deform out", x.numel())
+    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != B * D * H * W:
+        raise L.GavikoHipError("elastic_deform in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    _chk(ctrl, torch.float32, "elastic_deform ctrl")
+    if ctrl.dim() != 5 or ctrl.shape[0] != B or ctrl.shape[4] != 3:
+        raise L.GavikoHipError(f"elastic_deform ctrl: [B = {B}][n0][n1][n2][3] expected, got {tuple(ctrl.shape)}")
+    n0, n1, n2 = ctrl.shape[1:4]
+    _chk(live, torch.int32, "elastic_deform live", B)
+    _chk(partials, torch.float32, "elastic_deform partials", B * L.load().gvk_minmax_partials())
+    if field is not None:
+        _chk(field, torch.float32, "elastic_deform field", 3 * x.numel())
+    L.check(L.load().gvk_elastic_deform(L.ptr(x), L.ptr(out), L.ptr(field) if field is not None else None, L.ptr(ctrl), L.ptr(live), L.ptr(partials),
+                                        B, D, H, W, n0, n1, n2, L.stream_ptr()), "gvk_elastic_deform")
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

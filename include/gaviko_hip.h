@@ -687,6 +687,20 @@ enum { GVK_MOTION_MAX_TRANSFORMS = 4, GVK_MOTION_MAX_W = 256 };
 int gvk_motion_artifact(const float* in, float* out, const float* mats, const float* ctab, const int32_t* live, const float* partials, int K, int B,
                         int D, int H, int W, void* stream);
 
+/* ---- tio.RandomElasticDeformation (csrc/elastic.hip): a cubic B-spline warp of the volume, in one pass ---------------------------
+ * ITK's order-3 BSplineTransform over the image extent.  ctrl [B][n0][n1][n2][3]: control-point displacements in VOXELS, component a along
+ * array axis a.  Per axis a with S voxels and n control points: M = n - 3 mesh cells of h = S / M voxels; output index q has
+ * u = (q + 0.5) / h, i = min(floor(u), M - 1), t = u - i, and control points i..i+3 weigh B0 = (1-t)^3/6, B1 = (3t^3 - 6t^2 + 4)/6,
+ * B2 = (-3t^3 + 3t^2 + 3t + 1)/6, B3 = t^3/6.  d(q) = the tensor product of the three axes' weights over the 4x4x4 control points (fp32,
+ * contracted axis 1, then axis 0, then axis 2), and out[b] at q reads in[b] at float(q) + d(q) -- one fp32 add per axis -- with the
+ * trilinear arithmetic and pad rule of gvk_spatial_transform: neighbours outside the volume read the volume minimum taken from partials =
+ * gvk_volume_minmax of in.  field (may be NULL) receives [B][3][D][H][W] = exactly the d the read used.  live [B]: a sample with
+ * live[b] == 0 is copied bit for bit and its field is zero.  4 <= n_a <= GVK_ELASTIC_MAX_CONTROL_POINTS (one grid size per launch); in, out
+ * and field must not overlap; no divisibility or alignment requirement on D, H, W.  No atomics: the same bits on every run. */
+enum { GVK_ELASTIC_MAX_CONTROL_POINTS = 16 };
+int gvk_elastic_deform(const float* in, float* out, float* field, const float* ctrl, const int32_t* live, const float* partials, int B, int D, int H,
+                       int W, int n0, int n1, int n2, void* stream);
+
 /* ---- nn.Dropout as its own pass (sites without a producing kernel to fuse into) ------------------------------------------
  * Replaces vision_transformer.py:157 (emb_dropout), vpt.py:129,148,152 (prompt_dropout) and carries the masks of the
  * Linear+Dropout pairs (vision_transformer.py:34,54) onto the gradient side.  out32 / out16 (either may be NULL, out32 may alias x)
