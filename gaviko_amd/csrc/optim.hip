@@ -6,6 +6,8 @@
 //   gvk_sumsq      two-stage deterministic sum of squares of the flat gradient -> device scalar (no host sync)
 //   gvk_adam_step  clip = min(1, max_norm / (sqrt(sumsq) + 1e-6)) (torch.nn.utils.clip_grad_norm_), g *= clip (written back, as
 //                  torch does), m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+//                  Non-finite gradients behave as in torch: a NaN norm gives clip = NaN (every gradient, moment and parameter
+//                  turns NaN), an infinite norm gives clip = 0 (the inf elements turn NaN, every other gradient 0).
 // lr and beta1 of the step come from the host-side OneCycleLR mirror (gaviko_amd/optim.py); both are plain kernel arguments.
 #include "common.hpp"
 #include "../../include/gaviko_hip.h"
@@ -52,7 +54,11 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
   const int tid = bt[0], toff = bt[1], foff = bt[2], cnt = bt[3];
   float* p = (float*)a.ptr_tab[tid] + toff;
   float clip = 1.f;
-  if (a.norm_sq != nullptr) clip = fminf(1.f, a.max_norm / (sqrtf(a.norm_sq[0]) + 1e-6f));
+  if (a.norm_sq != nullptr) {
+    // torch clamps clip_coef with max=1, which keeps a NaN (fminf would drop it): a NaN norm poisons every gradient, as in torch
+    const float c = a.max_norm / (sqrtf(a.norm_sq[0]) + 1e-6f);
+    clip = c > 1.f ? 1.f : c;
+  }
   const float step = a.lr / a.bias_c1, rs2 = 1.f / sqrtf(a.bias_c2);
   for (int i = threadIdx.x; i < cnt; i += 256) {
     const float g = a.grad[foff + i] * clip;

@@ -190,7 +190,10 @@ class FusedAdamOneCycle:
             eng.invalidate_weights(eng.trainable_names())
 
     def grad_norm(self) -> torch.Tensor:
-        """Device scalar: the pre-clip total gradient norm of the last step (what clip_grad_norm_ returns)."""
+        """Device scalar: the pre-clip total gradient norm of the last step (what clip_grad_norm_ returns); NaN / inf if a gradient was."""
+        if self._tabs is None:
+            raise L.GavikoHipError("FusedAdamOneCycle.grad_norm(): no step has run since the optimizer was created or loaded (step() "
+                                   "computes the norm, of the gradients it saw)")
         return self._tabs["norm_sq"].sqrt()
 
     def get_last_lr(self) -> List[float]:
@@ -215,21 +218,49 @@ class FusedAdamOneCycle:
                 "names": None if self._layout is None else [n for n, _ in self._layout],
                 "numels": None if self._layout is None else [k for _, k in self._layout]}
 
-    def load_state_dict(self, sd):
-        """The moments are re-ordered to the current flat layout at the next step (by name); a state saved before names were recorded
-        (round <= 4) is taken to be in `named_parameters()` order of the trainable tensors, which is what those rounds stored."""
+    def _legacy_layout(self, legacy_order, legacy_layers_per_bucket):
+        """[(name, numel)] of a model-bound state saved without `names`.  Such a state does not say which of two layouts it is in:
+        "named" -- `trainable_names()` (= `named_parameters()`) order, what was stored while the flat gradient buffer was not grouped;
+        "flat"  -- `distributed.flat_order(trainable_names, share_factor, layers_per_bucket)`, completion groups with the highest layers
+                   first, what was stored once the buffer was grouped and until names were recorded (4 layers per bucket then, unless
+                   the model's reducer was made with another `layers_per_bucket`).
+        Both cover the same tensors, so the sizes cannot tell them apart, and guessing wrong pairs every moment with another parameter."""
+        from .distributed import flat_order
+        eng = self.model._engine()
+        named = list(eng.trainable_names())
+        share = eng.cfg.get("share_factor", 1) if eng.kind == "gaviko" else 1
+        flat = list(flat_order(named, share, 4 if legacy_layers_per_bucket is None else int(legacy_layers_per_bucket)))
+        if legacy_order is None:
+            if flat != named:
+                raise L.GavikoHipError(
+                    "FusedAdamOneCycle.load_state_dict: this state records no tensor names, and for this model its two possible layouts "
+                    "differ: 'named' (trainable_names() order, saved before the flat gradient buffer was grouped) and 'flat' "
+                    "(distributed.flat_order: completion groups, highest layers first, saved after).  Pass legacy_order='named' or "
+                    "legacy_order='flat' (with legacy_layers_per_bucket= if the saving run's reducer did not use 4)")
+            order = named
+        elif legacy_order in ("flat", "named"):
+            order = flat if legacy_order == "flat" else named
+        else:
+            raise L.GavikoHipError("FusedAdamOneCycle.load_state_dict: legacy_order must be 'flat' or 'named'")
+        return [(n, eng.p[n].numel()) for n in order]
+
+    def load_state_dict(self, sd, legacy_order: Optional[str] = None, legacy_layers_per_bucket: Optional[int] = None):
+        """The moments are re-ordered to the current flat layout at the next step (by name).  A state saved before names were recorded
+        is positional: for an explicit (params, flat_grad) pair it is in the order of the params; for a model it is accepted as it is only
+        if its two possible layouts coincide, otherwise `legacy_order` ("flat" | "named", see _legacy_layout) has to say which one it is
+        in.  Nothing of the optimizer changes when the load is refused."""
+        m = v = layout = None
+        if sd["exp_avg"] is not None:
+            m, v = sd["exp_avg"], sd["exp_avg_sq"]
+            if sd.get("names") is not None:
+                layout = list(zip(sd["names"], (int(k) for k in sd["numels"])))
+            elif self.model is not None:
+                layout = self._legacy_layout(legacy_order, legacy_layers_per_bucket)
+            else:
+                layout = [(f"#{i}", p.numel()) for i, p in enumerate(self._params)]
+            if sum(k for _, k in layout) != m.numel() or v.numel() != m.numel():
+                raise L.GavikoHipError("FusedAdamOneCycle.load_state_dict: exp_avg / exp_avg_sq do not have the size their layout says")
+            m, v = m.clone(), v.clone()
         self.t = int(sd["t"])
         self._tabs = None
-        if sd["exp_avg"] is None:
-            self.m = self.v = self._layout = None
-            return
-        self.m, self.v = sd["exp_avg"].clone(), sd["exp_avg_sq"].clone()
-        if sd.get("names") is not None:
-            self._layout = list(zip(sd["names"], (int(k) for k in sd["numels"])))
-        elif self.model is not None:
-            eng = self.model._engine()
-            self._layout = [(n, eng.p[n].numel()) for n in eng.trainable_names()]
-        else:
-            self._layout = [(f"#{i}", p.numel()) for i, p in enumerate(self._params)]
-        if sum(k for _, k in self._layout) != self.m.numel():
-            raise L.GavikoHipError("FusedAdamOneCycle.load_state_dict: exp_avg does not have the size its layout says")
+        self.m, self.v, self._layout = m, v, layout
