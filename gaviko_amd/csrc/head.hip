@@ -4,7 +4,8 @@
 //   rows_batch_sum : out[r][:] = sum_b dG[b][row_off + r][:]            (gradient of a batch-broadcast parameter)
 //   head_fwd       : logits = Linear(mean_r LN(G[b][r0 .. r0+R)))       (final LN restricted to the pooled rows:
 //                    gaviko.py:306,316 pools rows 0..P; vision_transformer.py:89,161 pools row 0 or all rows)
-//   head_bwd       : dWh, dbh and the gradient into the pooled rows of the final residual stream (other rows: zero)
+//   head_bwd       : dWh, dbh and the gradient into the pooled rows r0 .. r0+R of the final residual stream (the other rows of dg are
+//                    NOT written: their gradient is zero, and the caller zero-fills them)
 #include "common.hpp"
 #include "../../include/gaviko_hip.h"
 
