@@ -33,6 +33,13 @@ trilinear read of the affine pass.  It keeps torchio's signature, sampling and e
 voxels, the locked borders are zeroed on all three axes, and inside DeviceCompose it always runs before the affine/flip pass: same
 distributions, not the same voxels for the same seed.  Parity vs torchio / SimpleITK is UNPINNED; the kernel is pinned against a float64
 restatement (`tests/elastic_ref.py`) that is itself checked against scipy.ndimage.map_coordinates.
+
+The last step of every batch is a normaliser.  The reference's is the plain RescaleIntensity((0, 1)) (two kernels of `csrc/augment.hip`,
+kept bit for bit as the default); torchio's two MRI normalisers, RescaleIntensity with percentiles and a mask and ZNormalization
+(`normalization='percentile'` / `'znorm'`), run on exact per-volume order statistics and float64 moments computed on the device without a
+sort or a host read (`csrc/normalize.hip`).  Empty masks and zero ranges become a per-sample status word (`DeviceCompose.last_norm_status`)
+where torchio warns or raises; cutoffs are rounded to float32 before the clip.  Parity vs torchio is UNPINNED; the kernels are pinned against
+np.sort / np.percentile / math.fsum (`tests/normalize_ref.py`).
 """
 from __future__ import annotations
 
@@ -210,11 +217,42 @@ class RandomElasticDeformation:
 SPATIAL_ONE_OF_MEMBERS = (RandomAffine, RandomElasticDeformation)
 
 
-class RescaleIntensity:
-    """tio.RescaleIntensity(out_min_max): per-volume min-max to [out_min, out_max] (percentiles (0,100), no mask)."""
+def _masking_method(m, name):
+    """None, 'mean' or a float threshold: the mask rules `ops.volume_stats` knows."""
+    if m is None or (isinstance(m, str) and m == "mean"):
+        return m
+    if isinstance(m, (int, float)) and not isinstance(m, bool):
+        return float(m)
+    raise NotImplementedError(f"{name}: masking_method is None, 'mean' or a number (voxels above it); {m!r} (callables, label names) is not built")
 
-    def __init__(self, out_min_max=(0, 1)):
+
+class RescaleIntensity:
+    """tio.RescaleIntensity(out_min_max, percentiles, masking_method): the volume is clipped to the two percentiles of its masked voxels and
+    the clipped range goes to [out_min, out_max].  The defaults (percentiles (0, 100), no mask) are the plain per-volume min-max and keep its
+    two kernels; anything else runs the exact order statistics of `csrc/normalize.hip`."""
+
+    def __init__(self, out_min_max=(0, 1), percentiles=(0, 100), masking_method=None):
         self.out_min, self.out_max = float(out_min_max[0]), float(out_min_max[1])
+        percentiles = tuple(float(p) for p in percentiles)
+        if len(percentiles) != 2 or not 0.0 <= percentiles[0] <= percentiles[1] <= 100.0:
+            raise ValueError(f"RescaleIntensity: percentiles are (low, high) with 0 <= low <= high <= 100, not {percentiles}")
+        self.percentiles = percentiles
+        self.masking_method = _masking_method(masking_method, "RescaleIntensity")
+
+    @property
+    def plain(self) -> bool:
+        """True for the min-max rescale this package had first (its own two kernels, its own bits)."""
+        return self.percentiles == (0.0, 100.0) and self.masking_method is None
+
+
+class ZNormalization:
+    """tio.ZNormalization(masking_method): y = (x - mean) / std with the mean and the unbiased standard deviation of the masked voxels.
+    `ZNormalization.mean` is torchio's name for the rule 'voxels above the volume mean'."""
+
+    mean = "mean"
+
+    def __init__(self, masking_method=None):
+        self.masking_method = _masking_method(masking_method, "ZNormalization")
 
 # ---- intensity transforms: train.py:43-48 --------------------------------------------------------------------------------------------
 # Each `sample(rng)` returns None (not applied) or (class name, params) and draws, in this order: one uniform for p, then the
@@ -304,7 +342,8 @@ class RandomMotion:
 INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion)
 _BUILT = ("RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, RandomMotion, OneOf of the last four, "
           "RescaleIntensity (at most one); RandomElasticDeformation (at most one), OneOf of RandomAffine and RandomElasticDeformation in place of "
-          "the two")
+          "the two; ZNormalization in place of RescaleIntensity (at most one normaliser, it runs last), RescaleIntensity percentiles and "
+          "masking_method None / 'mean' / a threshold")
 
 
 class OneOf:
@@ -397,7 +436,7 @@ def motion_tables(times, W: int):
 class DeviceCompose:
     """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Affine and flips are merged
     into one resampling pass (affine first, flips on its output), the intensity transforms (singly or inside OneOf) follow in listed
-    order, RescaleIntensity runs last, as in the reference's Compose.  RandomElasticDeformation is a resampling pass of its own BEFORE the
+    order, the one normaliser (RescaleIntensity or ZNormalization) runs last, as in the reference's Compose.  RandomElasticDeformation is a resampling pass of its own BEFORE the
     affine/flip pass wherever it is listed: torchio would apply the spatial transforms in listed order, here elastic always runs first
     (a sample that draws both is interpolated twice, as in torchio).  A OneOf of RandomAffine / RandomElasticDeformation members may stand
     in place of the single affine and/or elastic: each sample then gets at most one of them.  Per sample the random draws are: elastic,
@@ -410,11 +449,13 @@ class DeviceCompose:
         self.spatial = [t for t in transforms if isinstance(t, OneOf) and t.spatial]     # in place of the single affine and/or elastic
         self.flips = [t for t in transforms if isinstance(t, RandomFlip)]
         self.rescale = [t for t in transforms if isinstance(t, RescaleIntensity)]
+        self.znorm = [t for t in transforms if isinstance(t, ZNormalization)]
         self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS) or (isinstance(t, OneOf) and not t.spatial)]
         elastic = self.elastic + [t for one in self.spatial for t in one.transforms if isinstance(t, RandomElasticDeformation)]
-        if len(self.affine) > 1 or len(self.rescale) > 1 or len(elastic) > 1 or len(self.spatial) > 1 or \
+        if len(self.affine) > 1 or len(self.rescale) + len(self.znorm) > 1 or len(elastic) > 1 or len(self.spatial) > 1 or \
                 (self.spatial and (self.affine or self.elastic)) or \
-                len(self.affine) + len(self.elastic) + len(self.spatial) + len(self.flips) + len(self.rescale) + len(self.intensity) != len(transforms):
+                len(self.affine) + len(self.elastic) + len(self.spatial) + len(self.flips) + len(self.rescale) + len(self.znorm) + \
+                len(self.intensity) != len(transforms):
             raise NotImplementedError(f"DeviceCompose: {_BUILT}; anything else is not built")
         self._elastic = elastic[0] if elastic else None                   # the one elastic transform, listed singly or inside the spatial OneOf
         self.rng = np.random.default_rng(seed)
@@ -423,6 +464,9 @@ class DeviceCompose:
         # the intensity draws of the last call, one entry per sample: None or (class name, params) -- with several intensity transforms
         # listed, a tuple of such entries in listed order
         self.last_intensity = None
+        # int32 [B] on the device after a call that ran a percentile / masked rescale or a z-normalisation: 0 normalised, 1 empty mask,
+        # 2 zero range or zero std (such samples come back unchanged).  Never synchronised on here; None after any other call.
+        self.last_norm_status = None
 
     def sample(self, B: int, shape):
         mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, 1, 1))
@@ -523,20 +567,47 @@ class DeviceCompose:
                 x = out
             for s in range(len(self.intensity)):
                 x = self._intensity_stage(x, [d if len(self.intensity) == 1 else (d[s] if d else None) for d in self.last_intensity])
-        if self.rescale:
+        self.last_norm_status = None
+        if self.rescale and self.rescale[0].plain:
             ops.volume_minmax(x, part)
             y = torch.empty_like(x)
             ops.rescale_intensity(x, part, y, self.rescale[0].out_min, self.rescale[0].out_max)
             x = y
+        elif self.rescale:
+            t = self.rescale[0]
+            stats, _ = ops.volume_stats(x, t.masking_method, want_std=False)
+            _, cutoffs = ops.volume_order_stats(x, stats, t.percentiles)
+            y = torch.empty_like(x)
+            self.last_norm_status = ops.normalize_intensity(x, y, stats, ops.NORMALIZE_RESCALE, cutoffs, t.out_min, t.out_max)
+            x = y
+        elif self.znorm:
+            stats, _ = ops.volume_stats(x, self.znorm[0].masking_method, want_std=True)
+            y = torch.empty_like(x)
+            self.last_norm_status = ops.normalize_intensity(x, y, stats, ops.NORMALIZE_ZNORM)
+            x = y
         return x
 
 
-def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False, elastic: bool = False) -> DeviceCompose:
+def normalizer(normalization: str = "minmax"):
+    """The batch's last step: 'minmax' = RescaleIntensity((0, 1)) as in train.py:50,58; 'percentile' = torchio's MRI recipe
+    RescaleIntensity((0, 1), percentiles=(0.5, 99.5)); 'znorm' = ZNormalization(masking_method=ZNormalization.mean)."""
+    if normalization == "minmax":
+        return RescaleIntensity((0, 1))
+    if normalization == "percentile":
+        return RescaleIntensity((0, 1), percentiles=(0.5, 99.5))
+    if normalization == "znorm":
+        return ZNormalization(masking_method=ZNormalization.mean)
+    raise ValueError(f"normalization is 'minmax', 'percentile' or 'znorm', not {normalization!r}")
+
+
+def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False, elastic: bool = False,
+                     normalization: str = "minmax") -> DeviceCompose:
     """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
     line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device, with
     the three members this package had first (RandomMotion's 0.25 spread over them); motion=True as well makes it the reference's dict
     as declared, four members at 0.25.  elastic=True (not in the reference) replaces the affine by torchio's documented recipe, the affine
-    in 0.8 and RandomElasticDeformation() in 0.2 of the samples that the group's p = 0.5 selects."""
+    in 0.8 and RandomElasticDeformation() in 0.2 of the samples that the group's p = 0.5 selects.  normalization picks the last step
+    (`normalizer`); it draws nothing, so the random stream does not depend on it."""
     if motion and not intensity:
         raise ValueError("train_transforms: motion=True adds RandomMotion to the intensity group and needs intensity=True")
     affine = OneOf({RandomAffine(degrees=15): 0.8, RandomElasticDeformation(): 0.2}, p=0.5) if elastic else RandomAffine(degrees=15, p=0.5)
@@ -545,12 +616,12 @@ def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion
     if motion:
         group = {RandomNoise(): 0.25, RandomBiasField(): 0.25, RandomBlur(std=(0, 1.5)): 0.25, RandomMotion(): 0.25}
     one_of = [OneOf(group, p=0.75)] if intensity else []
-    return DeviceCompose(spatial + one_of + [RescaleIntensity((0, 1))], seed)
+    return DeviceCompose(spatial + one_of + [normalizer(normalization)], seed)
 
 
-def eval_transforms() -> DeviceCompose:
+def eval_transforms(normalization: str = "minmax") -> DeviceCompose:
     """train.py:54-60: val and test."""
-    return DeviceCompose([RescaleIntensity((0, 1))])
+    return DeviceCompose([normalizer(normalization)])
 
 
 class DataPreprocessor:
@@ -558,14 +629,17 @@ class DataPreprocessor:
     device-side `train_transforms` / `val_transforms` attributes to call on each batch after `.to(device)`.  config['data']['intensity_augment']
     (default False) adds the intensity OneOf of `train_transforms(intensity=True)`, config['data']['motion_augment'] (default False)
     RandomMotion to it (`motion=True`), config['data']['elastic_augment'] (default False) puts the affine / elastic OneOf of
-    `train_transforms(elastic=True)` in place of the affine."""
+    `train_transforms(elastic=True)` in place of the affine, config['data']['normalization'] (default 'minmax'; 'percentile', 'znorm') picks
+    the last step of all three splits (`normalizer`)."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
         intensity = bool(config["data"].get("intensity_augment", False))
         motion = bool(config["data"].get("motion_augment", False))
         elastic = bool(config["data"].get("elastic_augment", False))
-        self.train_transforms, self.val_transforms, self.test_transforms = train_transforms(seed, intensity, motion, elastic), eval_transforms(), eval_transforms()
+        norm = config["data"].get("normalization", "minmax")
+        self.train_transforms, self.val_transforms, self.test_transforms = (train_transforms(seed, intensity, motion, elastic, norm),
+                                                                            eval_transforms(norm), eval_transforms(norm))
 
     def preprocess(self, df=None):
         import pandas as pd

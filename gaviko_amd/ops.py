@@ -1214,6 +1214,105 @@ def elastic_deform(x, out, ctrl, live, partials, field=None) -> None:
                                         B, D, H, W, n0, n1, n2, L.stream_ptr()), "gvk_elastic_deform")
 
 
+NORMALIZE_SLABS, NORMALIZE_STATS, NORMALIZE_MAX_PERCENTILES = 128, 8, 4     # GVK_NORMALIZE_SLABS, _STATS, _MAX_PERCENTILES
+NORMALIZE_ORDER_WS_WORDS = 32 + 3 * 8 * 2048                              # GVK_NORMALIZE_ORDER_WS_WORDS
+NORMALIZE_RESCALE, NORMALIZE_ZNORM = 1, 2                                 # mode of normalize_intensity
+STATS_FIELDS = ("min", "max", "mean_all", "threshold", "n", "mean", "std")    # columns of the stats table
+
+
+def _volumes(x, what):
+    _chk(x, torch.float32, what)
+    B = x.shape[0]
+    V = x.numel() // B
+    if x.dim() < 2 or V < 1 or V >= 2 ** 31:
+        raise L.GavikoHipError(f"{what}: [B][...] with 1 <= voxels per sample < 2^31, got {tuple(x.shape)}")
+    return B, V
+
+
+def _mask_rule(mask, what):
+    """(mask_mode, threshold) of gvk_volume_stats for a mask rule None, 'mean' or a number."""
+    if mask is None:
+        return 0, 0.0
+    if isinstance(mask, str) and mask == "mean":
+        return 1, 0.0
+    if isinstance(mask, (int, float)) and not isinstance(mask, bool):
+        return 2, float(mask)
+    raise L.GavikoHipError(f"{what}: the mask rule is None, 'mean' or a number, not {mask!r}")
+
+
+def volume_stats(x: torch.Tensor, mask=None, want_std: bool = True, stats: torch.Tensor = None, count: torch.Tensor = None,
+                 partials: torch.Tensor = None):
+    """Per-sample statistics of float32 volumes x [B][...] (any voxel count below 2^31): (stats, count), stats float64 [B][8] with the columns
+    STATS_FIELDS = min, max and mean of ALL voxels, the mask threshold, then n, mean and unbiased std (0 unless want_std) of the masked
+    voxels; count int64 [B] = n.  mask: None (every voxel), 'mean' (x > the float32 mean of all voxels) or a number t (x > t).  Float64
+    sums in a fixed order: the same bits on every run.  No host read.  stats, count and the scratch `partials` (float64,
+    B * NORMALIZE_SLABS * 4) are allocated here unless given."""
+    B, V = _volumes(x, "volume_stats x")
+    mode, t = _mask_rule(mask, "volume_stats")
+    if stats is None:
+        stats = torch.empty((B, NORMALIZE_STATS), dtype=torch.float64, device=x.device)
+    if count is None:
+        count = torch.empty(B, dtype=torch.int64, device=x.device)
+    _chk(stats, torch.float64, "volume_stats stats", B * NORMALIZE_STATS)
+    _chk(count, torch.int64, "volume_stats count", B)
+    if partials is None:
+        partials = torch.empty(B * NORMALIZE_SLABS * 4, dtype=torch.float64, device=x.device)
+    _chk(partials, torch.float64, "volume_stats partials", B * NORMALIZE_SLABS * 4)
+    L.check(L.load().gvk_volume_stats(L.ptr(x), L.ptr(partials), L.ptr(stats), L.ptr(count), mode, t, int(bool(want_std)), B, V, L.stream_ptr()),
+            "gvk_volume_stats")
+    return stats, count
+
+
+def volume_order_stats(x: torch.Tensor, stats: torch.Tensor, percentiles, pairs: torch.Tensor = None, cutoffs: torch.Tensor = None,
+                       workspace: torch.Tensor = None):
+    """Exact order statistics of the masked voxels of x (threshold and n come from `stats` = volume_stats of the same x) for up to 4
+    percentiles in [0, 100]: (pairs float32 [B][Q][2], cutoffs float32 [B][Q]) -- the two neighbouring sorted values of each percentile and
+    numpy's 'linear' percentile of the float64 values, rounded to float32.  No sort, no host read.  The outputs and the scratch `workspace`
+    (int32, B * NORMALIZE_ORDER_WS_WORDS) are allocated here unless given."""
+    B, V = _volumes(x, "volume_order_stats x")
+    _chk(stats, torch.float64, "volume_order_stats stats", B * NORMALIZE_STATS)
+    q = [float(p) for p in percentiles]
+    if not 1 <= len(q) <= NORMALIZE_MAX_PERCENTILES or any(not 0.0 <= p <= 100.0 for p in q):
+        raise L.GavikoHipError(f"volume_order_stats: 1..{NORMALIZE_MAX_PERCENTILES} percentiles in [0, 100], got {percentiles!r}")
+    qf = [p / 100.0 for p in q] + [0.0] * (NORMALIZE_MAX_PERCENTILES - len(q))
+    ws = torch.empty(B * NORMALIZE_ORDER_WS_WORDS, dtype=torch.int32, device=x.device) if workspace is None else workspace
+    pairs = torch.empty((B, len(q), 2), dtype=torch.float32, device=x.device) if pairs is None else pairs
+    cutoffs = torch.empty((B, len(q)), dtype=torch.float32, device=x.device) if cutoffs is None else cutoffs
+    _chk(ws, torch.int32, "volume_order_stats workspace", B * NORMALIZE_ORDER_WS_WORDS)
+    _chk(pairs, torch.float32, "volume_order_stats pairs", 2 * B * len(q))
+    _chk(cutoffs, torch.float32, "volume_order_stats cutoffs", B * len(q))
+    L.check(L.load().gvk_volume_order_stats(L.ptr(x), L.ptr(stats), L.ptr(ws), L.ptr(pairs), L.ptr(cutoffs), len(q), *qf, B, V, L.stream_ptr()),
+            "gvk_volume_order_stats")
+    return pairs, cutoffs
+
+
+def normalize_intensity(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, mode: int, cutoffs: torch.Tensor = None, out_min: float = 0.0,
+                        out_max: float = 1.0, status: torch.Tensor = None, params: torch.Tensor = None) -> torch.Tensor:
+    """The apply pass.  mode NORMALIZE_RESCALE: torchio's rescale with the volume clipped to cutoffs[b][0:2] (volume_order_stats);
+    NORMALIZE_ZNORM: y = float32((x - mean) / std) in float64 with the masked mean and std of `stats`.  Returns status int32 [B] (0 normalised,
+    1 empty mask, 2 zero range / zero std / fewer than two voxels: such a sample is copied bit for bit), a device tensor nobody waits on."""
+    B, V = _volumes(x, "normalize_intensity x")
+    _chk(y, torch.float32, "normalize_intensity y", x.numel())
+    _chk(stats, torch.float64, "normalize_intensity stats", B * NORMALIZE_STATS)
+    if mode not in (NORMALIZE_RESCALE, NORMALIZE_ZNORM):
+        raise L.GavikoHipError("normalize_intensity: mode is NORMALIZE_RESCALE or NORMALIZE_ZNORM")
+    Q = 0
+    if mode == NORMALIZE_RESCALE:
+        if cutoffs is None or cutoffs.dim() != 2 or cutoffs.shape[0] != B or not 2 <= cutoffs.shape[1] <= NORMALIZE_MAX_PERCENTILES:
+            raise L.GavikoHipError("normalize_intensity: the rescale needs cutoffs [B][Q >= 2] (low, high first)")
+        _chk(cutoffs, torch.float32, "normalize_intensity cutoffs")
+        Q = cutoffs.shape[1]
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=x.device)
+    if params is None:
+        params = torch.empty((B, 8), dtype=torch.float64, device=x.device)
+    _chk(status, torch.int32, "normalize_intensity status", B)
+    _chk(params, torch.float64, "normalize_intensity params", 8 * B)
+    L.check(L.load().gvk_normalize_intensity(L.ptr(x), L.ptr(y), L.ptr(stats), L.ptr(cutoffs) if Q else None, Q, L.ptr(params), L.ptr(status), mode,
+                                             float(out_min), float(out_max), B, V, L.stream_ptr()), "gvk_normalize_intensity")
+    return status
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

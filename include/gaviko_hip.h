@@ -701,6 +701,40 @@ enum { GVK_ELASTIC_MAX_CONTROL_POINTS = 16 };
 int gvk_elastic_deform(const float* in, float* out, float* field, const float* ctrl, const int32_t* live, const float* partials, int B, int D, int H,
                        int W, int n0, int n1, int n2, void* stream);
 
+/* ---- intensity normalisation (csrc/normalize.hip): tio.RescaleIntensity with percentiles and a mask, tio.ZNormalization ---------------
+ * Volumes are float32 x [B][V], 1 <= V < 2^31, x (and y) 16-byte aligned; NO divisibility requirement on V (sample b starts at x + b V; heads
+ * and tails are handled in the kernels).  Everything stays on the device: the three calls hand each other DEVICE tables and none reads the
+ * host.  NaN input is out of scope.
+ * gvk_volume_stats: stats [B][GVK_NORMALIZE_STATS] doubles = (min, max, mean of ALL voxels; the mask threshold t; n, mean and unbiased
+ *   standard deviation of the MASKED voxels x > t; one unused word), count [B] int64 = n.  mask_mode 0: no mask (t = -inf, n = V);
+ *   1: t = the mean of all voxels rounded to float32 (x > x.mean()); 2: t = threshold.  The standard deviation (want_std != 0, else 0) is
+ *   sqrt(sum (x - mean)^2 / (n - 1)) with the deviations taken from that mean in a pass of their own; 0 when n < 2.  All sums are float64 in a
+ *   fixed order (per thread ascending, a fixed tree over the workgroup, a fixed tree over at most GVK_NORMALIZE_SLABS slabs), no floating-point
+ *   atomics: the same input gives the same bits on every run.  partials: scratch of B * GVK_NORMALIZE_SLABS * 4 doubles.
+ * gvk_volume_order_stats: exact order statistics of the masked voxels (t and n read from stats) for Q <= GVK_NORMALIZE_MAX_PERCENTILES
+ *   percentile fractions qj = percentile / 100 (computed by the caller; entries beyond Q are ignored).  Per sample and j: v = (double)(n - 1) * qj
+ *   (one float64 multiply), i = floor(v), g = v - i, a = the i-th smallest masked value, b = the min(i + 1, n - 1)-th; pairs [B][Q][2] = (a, b);
+ *   cutoffs [B][Q] = float32 of numpy's 'linear' rule on float64 operands, c = a + (b - a) g for g < 0.5, else b - (b - a) (1 - g), every operation
+ *   rounded once (nothing contracted).  The selection is a most-significant-first radix select on an order-preserving 32-bit key (3 passes of
+ *   11 / 11 / 10 bits) and is exact for every finite float32 input, denormals included; -0.0 and +0.0 are one value (a or b may come back with
+ *   either sign bit).  Each pass counts the digit of the keys under the distinct prefixes the 2 Q ranks fall under: at most 8 prefixes,
+ *   4 per sweep over the data (a 32 KB LDS histogram), so more than 4 cost a second sweep of that pass.  The histograms are merged with integer
+ *   atomics, which are exact in any order.  An empty mask gives zeros.  workspace: B * GVK_NORMALIZE_ORDER_WS_WORDS uint32.
+ * gvk_normalize_intensity: a finishing step writes params [B][8] doubles = (lo, hi, sub, div, mul, add, mean, std) and status [B] from stats
+ *   (and cutoffs [B][Q], entries 0 and 1 = low and high), then ONE streaming pass writes y.
+ *   GVK_NORMALIZE_RESCALE: torchio's rescale.  lo, hi = the cutoffs; in_min = clamp(min, lo, hi), in_max = clamp(max, lo, hi) (the extremes of
+ *   the clipped volume); y = (((clip(x, lo, hi) - in_min) / in_range) * (out_max - out_min)) + out_min, four float32 steps with a true divide.
+ *   GVK_NORMALIZE_ZNORM: y = float32(((double)x - mean) / std), mean and std those of the masked voxels.
+ *   status: 0 normalised; 1 empty mask; 2 in_range == 0, or std == 0, or n < 2.  A sample with a non-zero status is copied bit for bit. */
+enum { GVK_NORMALIZE_SLABS = 128, GVK_NORMALIZE_STATS = 8, GVK_NORMALIZE_MAX_PERCENTILES = 4, GVK_NORMALIZE_ORDER_WS_WORDS = 32 + 3 * 8 * 2048 };
+enum { GVK_NORMALIZE_RESCALE = 1, GVK_NORMALIZE_ZNORM = 2 };
+int gvk_volume_stats(const float* x, double* partials, double* stats, int64_t* count, int mask_mode, float threshold, int want_std, int B, int64_t V,
+                     void* stream);
+int gvk_volume_order_stats(const float* x, const double* stats, void* workspace, float* pairs, float* cutoffs, int Q, double q0, double q1, double q2,
+                           double q3, int B, int64_t V, void* stream);
+int gvk_normalize_intensity(const float* x, float* y, const double* stats, const float* cutoffs, int Q, double* params, int32_t* status, int mode,
+                            float out_min, float out_max, int B, int64_t V, void* stream);
+
 /* ---- nn.Dropout as its own pass (sites without a producing kernel to fuse into) ------------------------------------------
  * Replaces vision_transformer.py:157 (emb_dropout), vpt.py:129,148,152 (prompt_dropout) and carries the masks of the
  * Linear+Dropout pairs (vision_transformer.py:34,54) onto the gradient side.  out32 / out16 (either may be NULL, out32 may alias x)
