@@ -40,9 +40,18 @@ kept bit for bit as the default); torchio's two MRI normalisers, RescaleIntensit
 sort or a host read (`csrc/normalize.hip`).  Empty masks and zero ranges become a per-sample status word (`DeviceCompose.last_norm_status`)
 where torchio warns or raises; cutoffs are rounded to float32 before the clip.  Parity vs torchio is UNPINNED; the kernels are pinned against
 np.sort / np.percentile / math.fsum (`tests/normalize_ref.py`).
+
+The rest of torchio's MRI augmentation family (`train_transforms(intensity=True, artifacts=True)`, `csrc/kspace.hip`) joins the intensity
+group: RandomGhosting reduces the way RandomMotion did, to a real circular convolution along the one axis its k-space mask depends on (any of
+the three, drawn per sample, on the fp32 matrix cores); a RandomSpike is one cosine added in image space, its phase tabulated per axis on the
+host; RandomGamma is a streaming power; RandomAnisotropy collapses to a two-tap gather along one axis.  They keep torchio's signatures, value
+ranges and errors; ghosting restores exactly the centre plane (not a band of relative width `restore`), a spike's amplitude is g |mean(x)|
+(torchio's g max|F| / V for a non-negative volume), anisotropy clamps at the edges where torchio pads.  Parity vs torchio is UNPINNED; the kernels
+are pinned against the literal np.fft algorithms and float64 restatements (`tests/kspace_ref.py`).
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional, Sequence
 
@@ -339,11 +348,107 @@ class RandomMotion:
         return "RandomMotion", dict(degrees=degrees, translation=translation, times=times)
 
 
-INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion)
+def _axes(axes, name):
+    axes = (axes,) if isinstance(axes, int) else tuple(axes)
+    if not axes or any(not isinstance(a, (int, np.integer)) or isinstance(a, bool) or a not in (0, 1, 2) for a in axes):
+        raise ValueError(f"{name}: axes are array axes 0, 1, 2 (anatomical labels are not built), not {axes!r}")
+    return tuple(int(a) for a in axes)
+
+
+class RandomGhosting:
+    """tio.RandomGhosting(num_ghosts=(4, 10), axes=(0, 1, 2), intensity=(0.5, 1), restore=0.02, p=1): every n-th plane of the shifted spectrum
+    along one axis is scaled by 1 - g and the centre plane N // 2 is put back (`ghosting_tables`, `csrc/kspace.hip`).  A scalar num_ghosts n
+    means U{0..n}, a scalar intensity d means U(0, d).  Draws: n, an integer uniform on [low, high] inclusive; the axis, uniform over axes; g.
+    n == 0 or g == 0 is the identity.  restore is accepted and validated for signature compatibility only: exactly the centre plane is
+    restored, where torchio restores a band of that relative width."""
+
+    def __init__(self, num_ghosts=(4, 10), axes=(0, 1, 2), intensity=(0.5, 1), restore: float = 0.02, p: float = 1.0):
+        ng = tuple(num_ghosts) if isinstance(num_ghosts, (tuple, list)) else (0, num_ghosts)
+        if len(ng) != 2 or any(not isinstance(v, (int, np.integer)) or isinstance(v, bool) for v in ng) or not 0 <= ng[0] <= ng[1]:
+            raise ValueError(f"RandomGhosting: num_ghosts is a non-negative integer or a (low, high) pair of them with low <= high, not {num_ghosts!r}")
+        self.num_ghosts = (int(ng[0]), int(ng[1]))
+        self.axes = _axes(axes, "RandomGhosting")
+        self.intensity = (0.0, float(intensity)) if isinstance(intensity, (int, float)) else _pair(intensity, "intensity")
+        if self.intensity[0] < 0 or self.intensity[1] < self.intensity[0]:
+            raise ValueError("RandomGhosting: intensity is a non-negative number or a (low, high) pair with 0 <= low <= high")
+        if not 0.0 <= float(restore) <= 1.0:
+            raise ValueError(f"RandomGhosting: restore is in [0, 1], not {restore}")
+        self.restore, self.p = float(restore), float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        n = int(rng.integers(self.num_ghosts[0], self.num_ghosts[1] + 1))
+        axis = self.axes[int(rng.integers(len(self.axes)))]
+        return "RandomGhosting", dict(num_ghosts=n, axis=axis, intensity=float(rng.uniform(*self.intensity)))
+
+
+class RandomSpike:
+    """tio.RandomSpike(num_spikes=1, intensity=(1, 3), p=1): num_spikes points of the shifted spectrum get A added and the real part is kept:
+    stripes y = x + (A / V) sum_s cos(2 pi sum_a (k_sa - N_a // 2) x_a / N_a), k_sa = floor(pos_sa N_a), with A / V = g |mean(x)|, which is
+    torchio's g max|F| / V for a non-negative volume (`spike_tables`, `csrc/kspace.hip`).  num_spikes is a fixed integer 1..4; a scalar
+    intensity d means U(-d, d).  Draws: positions U(0, 1) [num_spikes][3], then g."""
+
+    def __init__(self, num_spikes: int = 1, intensity=(1, 3), p: float = 1.0):
+        if not isinstance(num_spikes, (int, np.integer)) or isinstance(num_spikes, bool):
+            raise NotImplementedError("RandomSpike: a fixed integer number of spikes is built, not a range")
+        if num_spikes < 1:
+            raise ValueError("RandomSpike: num_spikes is at least 1")
+        if num_spikes > ops.SPIKE_MAX:
+            raise NotImplementedError(f"RandomSpike: num_spikes 1..{ops.SPIKE_MAX} are built")
+        self.num_spikes, self.intensity, self.p = int(num_spikes), _pair(intensity, "intensity"), float(p)
+        if self.intensity[1] < self.intensity[0]:
+            raise ValueError("RandomSpike: intensity is a number or a (low, high) pair with low <= high")
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        positions = rng.random((self.num_spikes, 3))
+        return "RandomSpike", dict(positions=positions, intensity=float(rng.uniform(*self.intensity)))
+
+
+class RandomGamma:
+    """tio.RandomGamma(log_gamma=(-0.3, 0.3), p=1): y = sign(x) |x|^gamma, gamma = exp(beta), beta ~ U(low, high); a scalar d means U(-d, d).
+    Draws: beta.  Zeros stay zero with their sign (torchio rescales nothing either; its warning about negative voxels is not raised)."""
+
+    def __init__(self, log_gamma=(-0.3, 0.3), p: float = 1.0):
+        self.log_gamma, self.p = _pair(log_gamma, "log_gamma"), float(p)
+        if self.log_gamma[1] < self.log_gamma[0]:
+            raise ValueError("RandomGamma: log_gamma is a number or a (low, high) pair with low <= high")
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        beta = float(rng.uniform(*self.log_gamma))
+        return "RandomGamma", dict(log_gamma=beta, gamma=math.exp(beta))
+
+
+class RandomAnisotropy:
+    """tio.RandomAnisotropy(axes=(0, 1, 2), downsampling=(1.5, 5), image_interpolation='linear', p=1): the volume is downsampled along one axis
+    by f with nearest neighbour and brought back to its shape with linear interpolation (`anisotropy_tables`, `csrc/kspace.hip`).  A scalar
+    downsampling d means U(1, d).  Draws: the axis, uniform over axes; f.  The edges are clamped where torchio pads."""
+
+    def __init__(self, axes=(0, 1, 2), downsampling=(1.5, 5), image_interpolation: str = "linear", p: float = 1.0):
+        if image_interpolation != "linear":
+            raise NotImplementedError("RandomAnisotropy: only image_interpolation='linear' is built")
+        self.axes = _axes(axes, "RandomAnisotropy")
+        self.downsampling = (1.0, float(downsampling)) if isinstance(downsampling, (int, float)) else _pair(downsampling, "downsampling")
+        if self.downsampling[0] < 1 or self.downsampling[1] < self.downsampling[0]:
+            raise ValueError("RandomAnisotropy: downsampling is a number >= 1 or a (low, high) pair with 1 <= low <= high")
+        self.p = float(p)
+
+    def sample(self, rng: np.random.Generator):
+        if rng.random() >= self.p:
+            return None
+        axis = self.axes[int(rng.integers(len(self.axes)))]
+        return "RandomAnisotropy", dict(axis=axis, downsampling=float(rng.uniform(*self.downsampling)))
+
+
+INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion, RandomGhosting, RandomSpike, RandomGamma, RandomAnisotropy)
 _BUILT = ("RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, RandomMotion, OneOf of the last four, "
           "RescaleIntensity (at most one); RandomElasticDeformation (at most one), OneOf of RandomAffine and RandomElasticDeformation in place of "
           "the two; ZNormalization in place of RescaleIntensity (at most one normaliser, it runs last), RescaleIntensity percentiles and "
-          "masking_method None / 'mean' / a threshold")
+          "masking_method None / 'mean' / a threshold; RandomGhosting, RandomSpike, RandomGamma, RandomAnisotropy, singly or in the intensity OneOf")
 
 
 class OneOf:
@@ -431,6 +536,70 @@ def motion_tables(times, W: int):
             ctab[b, s] = np.cos(2.0 * np.pi * freq[:, None] * m[None, :] / W).sum(axis=0) / W
         src[b] = order
     return ctab, src
+
+
+def ghosting_tables(num_ghosts, intensity, N) -> np.ndarray:
+    """Host half of `ops.axis_circular_conv` for RandomGhosting draws: ctab float32 [B][ops.AXIS_CONV_MAX_N], row b = the real circular
+    convolution kernel along an axis of N[b] voxels (entries N[b].. are zero) that scaling the planes j % n == 0, j != N // 2, of the shifted
+    spectrum by 1 - g stands for: c[m] = delta[m] - (g / N) sum_{j in S} cos(2 pi (j - N // 2) m / N), the phase reduced modulo N in integers,
+    summed in float64 and then rounded.  n == 0 or g == 0 gives the unit impulse; c[0] = 1 - g |S| / N and the row sums to 1 (the centre plane, the DC term, is kept)."""
+    n_, g_, N_ = np.atleast_1d(num_ghosts), np.atleast_1d(intensity), np.atleast_1d(N)
+    ctab = np.zeros((len(n_), ops.AXIS_CONV_MAX_N), dtype=np.float32)
+    for b, (n, g, N) in enumerate(zip(n_, g_, N_)):
+        n, g, N = int(n), float(g), int(N)
+        if not 2 <= N <= ops.AXIS_CONV_MAX_N:
+            raise ValueError(f"ghosting_tables: an axis of {N} voxels; 2..{ops.AXIS_CONV_MAX_N} are built")
+        if n < 0:
+            raise ValueError("ghosting_tables: num_ghosts is non-negative")
+        c = np.zeros(N, dtype=np.float64)
+        c[0] = 1.0
+        if n > 0 and g != 0.0:
+            j = np.array([j for j in range(0, N, n) if j != N // 2], dtype=np.int64)
+            m = np.arange(N, dtype=np.int64)
+            phase = ((j[:, None] - N // 2) * m[None, :]) % N
+            c -= (g / N) * np.cos(2.0 * np.pi * phase / N).sum(axis=0)
+        ctab[b, :N] = c
+    return ctab
+
+
+def spike_tables(positions, shape) -> np.ndarray:
+    """Host half of `ops.gamma_spike` for the spikes of ONE sample, positions [S][3] in [0, 1): float32 [ops.SPIKE_MAX][2][D + H + W], entry
+    [s][0 / 1][offset_a + x] = cos / sin(2 pi ((k_sa - N_a // 2) x mod N_a) / N_a) with k_sa = floor(pos_sa N_a) (at most N_a - 1) and offsets
+    0, D, D + H: the phase is reduced in integers, evaluated in float64 and then rounded.  Rows S.. are zero."""
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    if not 1 <= len(pos) <= ops.SPIKE_MAX:
+        raise ValueError(f"spike_tables: {len(pos)} spikes; 1..{ops.SPIKE_MAX} are built")
+    if (pos < 0).any() or (pos >= 1).any():
+        raise ValueError("spike_tables: positions are in [0, 1)")
+    tab = np.zeros((ops.SPIKE_MAX, 2, int(sum(shape))), dtype=np.float32)
+    for s in range(len(pos)):
+        off = 0
+        for a, N in enumerate(int(v) for v in shape):
+            k = min(int(np.floor(pos[s, a] * N)), N - 1)
+            phase = 2.0 * np.pi * (((k - N // 2) * np.arange(N, dtype=np.int64)) % N) / N
+            tab[s, 0, off:off + N], tab[s, 1, off:off + N] = np.cos(phase), np.sin(phase)
+            off += N
+    return tab
+
+
+def anisotropy_tables(downsampling, N: int, n_max: Optional[int] = None):
+    """Host half of `ops.axis_gather2` for ONE sample's factor f >= 1 along an axis of N voxels: (src int32 [n_max][2], w float32 [n_max]), n_max
+    = N unless given.  All in float64: n_low = max(1, ceil(N / f)) low-resolution samples, sample j = the original voxel nearest to
+    (j + 0.5) f - 0.5 (floor(c + 0.5), clamped to 0..N-1); output voxel i sits at u = (i + 0.5) / f - 0.5 on the low grid, clamped to
+    [0, n_low - 1]; src[i] = the voxels of low samples floor(u) and min(floor(u) + 1, n_low - 1), w[i] = float32(u - floor(u)).  f == 1 gives
+    src[i][0] = i and w = 0."""
+    f, N = float(downsampling), int(N)
+    if f < 1.0 or N < 1:
+        raise ValueError("anisotropy_tables: downsampling >= 1 along an axis of at least one voxel")
+    n_max = N if n_max is None else int(n_max)
+    n_low = max(1, int(np.ceil(N / f)))
+    low = np.clip(np.floor((np.arange(n_low, dtype=np.float64) + 0.5) * f - 0.5 + 0.5), 0, N - 1).astype(np.int64)
+    u = np.clip((np.arange(N, dtype=np.float64) + 0.5) / f - 0.5, 0.0, float(n_low - 1))
+    j0 = np.floor(u).astype(np.int64)
+    j1 = np.minimum(j0 + 1, n_low - 1)
+    src, w = np.zeros((n_max, 2), dtype=np.int32), np.zeros(n_max, dtype=np.float32)
+    src[:N, 0], src[:N, 1], w[:N] = low[j0], low[j1], (u - j0).astype(np.float32)
+    return src, w
 
 
 class DeviceCompose:
@@ -539,6 +708,42 @@ class DeviceCompose:
             y = torch.empty_like(x)
             ops.motion_artifact(x, y, torch.from_numpy(mats).to(dev), torch.from_numpy(ctab).to(dev), torch.from_numpy(live).to(dev), part, K)
             x = y
+        if "RandomGhosting" in names:
+            shape = tuple(x.shape[-3:])
+            n, g, N = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.float64), np.full(B, shape[2], dtype=np.int64)
+            axis, live = np.full(B, 2, dtype=np.int32), np.zeros(B, dtype=np.int32)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomGhosting":
+                    n[b], g[b], axis[b], N[b], live[b] = d[1]["num_ghosts"], d[1]["intensity"], d[1]["axis"], shape[d[1]["axis"]], 1
+            y = torch.empty_like(x)
+            ops.axis_circular_conv(x, y, torch.from_numpy(ghosting_tables(n, g, N)).to(dev), torch.from_numpy(axis).to(dev), torch.from_numpy(live).to(dev))
+            x = y
+        if "RandomGamma" in names or "RandomSpike" in names:
+            shape = tuple(x.shape[-3:])
+            kind, gamma, amp = np.zeros(B, dtype=np.int32), np.ones(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+            nspikes, tab = np.zeros(B, dtype=np.int32), np.zeros((B, ops.SPIKE_MAX, 2, sum(shape)), dtype=np.float32)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomGamma":
+                    kind[b], gamma[b] = ops.KSPACE_GAMMA, d[1]["gamma"]
+                elif d and d[0] == "RandomSpike":
+                    kind[b], amp[b], nspikes[b], tab[b] = ops.KSPACE_SPIKE, d[1]["intensity"], len(d[1]["positions"]), spike_tables(d[1]["positions"], shape)
+            # the spikes scale with the mean of this stage's input, taken on the device and never read here
+            stats = ops.volume_stats(x, None, want_std=False)[0] if "RandomSpike" in names else torch.zeros((B, ops.NORMALIZE_STATS), dtype=torch.float64, device=dev)
+            y = torch.empty_like(x)
+            ops.gamma_spike(x, y, torch.from_numpy(kind).to(dev), torch.from_numpy(gamma).to(dev), torch.from_numpy(amp).to(dev),
+                            torch.from_numpy(nspikes).to(dev), torch.from_numpy(tab).to(dev), stats)
+            x = y
+        if "RandomAnisotropy" in names:
+            shape = tuple(x.shape[-3:])
+            src, w = np.zeros((B, max(shape), 2), dtype=np.int32), np.zeros((B, max(shape)), dtype=np.float32)
+            axis, live = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+            for b, d in enumerate(draws):
+                if d and d[0] == "RandomAnisotropy":
+                    axis[b], live[b] = d[1]["axis"], 1
+                    src[b], w[b] = anisotropy_tables(d[1]["downsampling"], shape[axis[b]], max(shape))
+            y = torch.empty_like(x)
+            ops.axis_gather2(x, y, torch.from_numpy(src).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(axis).to(dev), torch.from_numpy(live).to(dev))
+            x = y
         return x
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
@@ -601,20 +806,27 @@ def normalizer(normalization: str = "minmax"):
 
 
 def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False, elastic: bool = False,
-                     normalization: str = "minmax") -> DeviceCompose:
+                     normalization: str = "minmax", artifacts: bool = False) -> DeviceCompose:
     """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
     line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device, with
     the three members this package had first (RandomMotion's 0.25 spread over them); motion=True as well makes it the reference's dict
     as declared, four members at 0.25.  elastic=True (not in the reference) replaces the affine by torchio's documented recipe, the affine
     in 0.8 and RandomElasticDeformation() in 0.2 of the samples that the group's p = 0.5 selects.  normalization picks the last step
-    (`normalizer`); it draws nothing, so the random stream does not depend on it."""
+    (`normalizer`); it draws nothing, so the random stream does not depend on it.  artifacts=True (not in the reference) adds torchio's other
+    MRI artifacts, RandomGhosting(), RandomSpike(), RandomGamma() and RandomAnisotropy() with their defaults, to the intensity group, every
+    member of the group at the same weight: 1/7 each, 1/8 each with motion=True."""
     if motion and not intensity:
         raise ValueError("train_transforms: motion=True adds RandomMotion to the intensity group and needs intensity=True")
+    if artifacts and not intensity:
+        raise ValueError("train_transforms: artifacts=True adds RandomGhosting, RandomSpike, RandomGamma and RandomAnisotropy to the intensity group "
+                         "and needs intensity=True")
     affine = OneOf({RandomAffine(degrees=15): 0.8, RandomElasticDeformation(): 0.2}, p=0.5) if elastic else RandomAffine(degrees=15, p=0.5)
     spatial = [affine, RandomFlip(axes=(0,), flip_probability=0.5)]
     group = {RandomNoise(): 1, RandomBiasField(): 1, RandomBlur(std=(0, 1.5)): 1}
     if motion:
         group = {RandomNoise(): 0.25, RandomBiasField(): 0.25, RandomBlur(std=(0, 1.5)): 0.25, RandomMotion(): 0.25}
+    if artifacts:
+        group = {t: 1 for t in list(group) + [RandomGhosting(), RandomSpike(), RandomGamma(), RandomAnisotropy()]}
     one_of = [OneOf(group, p=0.75)] if intensity else []
     return DeviceCompose(spatial + one_of + [normalizer(normalization)], seed)
 
@@ -630,7 +842,8 @@ class DataPreprocessor:
     (default False) adds the intensity OneOf of `train_transforms(intensity=True)`, config['data']['motion_augment'] (default False)
     RandomMotion to it (`motion=True`), config['data']['elastic_augment'] (default False) puts the affine / elastic OneOf of
     `train_transforms(elastic=True)` in place of the affine, config['data']['normalization'] (default 'minmax'; 'percentile', 'znorm') picks
-    the last step of all three splits (`normalizer`)."""
+    the last step of all three splits (`normalizer`), config['data']['artifact_augment'] (default False) adds RandomGhosting, RandomSpike,
+    RandomGamma and RandomAnisotropy to the intensity OneOf (`artifacts=True`; it needs intensity_augment)."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
@@ -638,7 +851,8 @@ class DataPreprocessor:
         motion = bool(config["data"].get("motion_augment", False))
         elastic = bool(config["data"].get("elastic_augment", False))
         norm = config["data"].get("normalization", "minmax")
-        self.train_transforms, self.val_transforms, self.test_transforms = (train_transforms(seed, intensity, motion, elastic, norm),
+        artifacts = bool(config["data"].get("artifact_augment", False))
+        self.train_transforms, self.val_transforms, self.test_transforms = (train_transforms(seed, intensity, motion, elastic, norm, artifacts=artifacts),
                                                                             eval_transforms(norm), eval_transforms(norm))
 
     def preprocess(self, df=None):

@@ -1313,6 +1313,65 @@ def normalize_intensity(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, m
     return status
 
 
+AXIS_CONV_MAX_N, SPIKE_MAX = 256, 4                                       # GVK_AXIS_CONV_MAX_N, GVK_SPIKE_MAX
+KSPACE_COPY, KSPACE_GAMMA, KSPACE_SPIKE = 0, 1, 2                         # kind[b] of gamma_spike
+
+
+def _one_channel(x, out, what):
+    _chk(x, torch.float32, f"{what} in")
+    _chk(out, torch.float32, f"{what} out", x.numel())
+    if x.dim() < 4:
+        raise L.GavikoHipError(f"{what} in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != B * D * H * W:
+        raise L.GavikoHipError(f"{what} in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    return B, D, H, W
+
+
+def axis_circular_conv(x, out, ctab, axis, live) -> None:
+    """tio.RandomGhosting's arithmetic: out[b] = the real circular convolution of x[b] along array axis axis[b] (i32 [B]: 0, 1, 2) with the row
+    ctab[b] (f32 [B][AXIS_CONV_MAX_N], entries 0..N-1 used; data.ghosting_tables), on the fp32 matrix cores.  live i32 [B]: a sample with 0 is
+    copied bit for bit.  The tables stay on the device and are not read here, so all of D, H, W must be in 2..AXIS_CONV_MAX_N.  out must not
+    overlap x."""
+    B, D, H, W = _one_channel(x, out, "axis_circular_conv")
+    _chk(ctab, torch.float32, "axis_circular_conv ctab", AXIS_CONV_MAX_N * B)
+    _chk(axis, torch.int32, "axis_circular_conv axis", B)
+    _chk(live, torch.int32, "axis_circular_conv live", B)
+    L.check(L.load().gvk_axis_circular_conv(L.ptr(x), L.ptr(out), L.ptr(ctab), L.ptr(axis), L.ptr(live), B, D, H, W, L.stream_ptr()),
+            "gvk_axis_circular_conv")
+
+
+def gamma_spike(x, out, kind, gamma, amp, nspikes, tab, stats) -> None:
+    """One streaming pass, kind i32 [B]: KSPACE_COPY; KSPACE_GAMMA, out = sign(x) |x|^gamma[b] (gamma f32 [B]; 1 is exactly the identity);
+    KSPACE_SPIKE, out = x + amp[b] |mean(x[b])| sum over nspikes[b] (i32 [B], <= SPIKE_MAX) spikes of the cosine that the per-axis cos / sin
+    tables tab f32 [B][SPIKE_MAX][2][D + H + W] (data.spike_tables) stand for; amp f32 [B]; stats = volume_stats(x)[0], whose float64 mean of
+    all voxels is read on the device.  Every table must be given whatever the kinds.  out must not overlap x."""
+    B, D, H, W = _one_channel(x, out, "gamma_spike")
+    _chk(kind, torch.int32, "gamma_spike kind", B)
+    _chk(gamma, torch.float32, "gamma_spike gamma", B)
+    _chk(amp, torch.float32, "gamma_spike amp", B)
+    _chk(nspikes, torch.int32, "gamma_spike nspikes", B)
+    _chk(tab, torch.float32, "gamma_spike tab", B * SPIKE_MAX * 2 * (D + H + W))
+    _chk(stats, torch.float64, "gamma_spike stats", B * NORMALIZE_STATS)
+    L.check(L.load().gvk_gamma_spike(L.ptr(x), L.ptr(out), L.ptr(kind), L.ptr(gamma), L.ptr(amp), L.ptr(nspikes), L.ptr(tab), L.ptr(stats), B, D, H, W,
+                                     L.stream_ptr()), "gvk_gamma_spike")
+
+
+def axis_gather2(x, out, src, w, axis, live) -> None:
+    """tio.RandomAnisotropy's arithmetic: along array axis axis[b] (i32 [B]), out[..i..] = x0 if w[b][i] == 0 else fmaf(w[b][i], x1 - x0, x0) with
+    x0, x1 = x[b] at the indices src[b][i][0], src[b][i][1] of that axis; src i32 [B][n_max][2], w f32 [B][n_max], n_max >= max(D, H, W)
+    (data.anisotropy_tables).  live i32 [B]: a sample with 0 is copied bit for bit.  out must not overlap x."""
+    B, D, H, W = _one_channel(x, out, "axis_gather2")
+    _chk(src, torch.int32, "axis_gather2 src")
+    _chk(w, torch.float32, "axis_gather2 w")
+    if src is None or w is None or src.dim() != 3 or src.shape[0] != B or src.shape[2] != 2 or tuple(w.shape) != tuple(src.shape[:2]):
+        raise L.GavikoHipError(f"axis_gather2: src [B = {B}][n_max][2] and w [B][n_max] expected")
+    _chk(axis, torch.int32, "axis_gather2 axis", B)
+    _chk(live, torch.int32, "axis_gather2 live", B)
+    L.check(L.load().gvk_axis_gather2(L.ptr(x), L.ptr(out), L.ptr(src), L.ptr(w), L.ptr(axis), L.ptr(live), int(src.shape[1]), B, D, H, W,
+                                      L.stream_ptr()), "gvk_axis_gather2")
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

@@ -735,6 +735,41 @@ int gvk_volume_order_stats(const float* x, const double* stats, void* workspace,
 int gvk_normalize_intensity(const float* x, float* y, const double* stats, const float* cutoffs, int Q, double* params, int32_t* status, int mode,
                             float out_min, float out_max, int B, int64_t V, void* stream);
 
+/* ---- tio.RandomGhosting / RandomSpike / RandomGamma / RandomAnisotropy (csrc/kspace.hip): the rest of torchio's MRI augmentation family ----
+ * Volumes are float32 [B][D][H][W], one channel, resident in HBM; every table is a DEVICE array with one row per sample and is never read by
+ * the host, so one launch serves a batch in which each sample drew a different axis, a different transform or none.  A sample that drew
+ * nothing (live[b] == 0, kind[b] == 0) is copied bit for bit, signed zeros and subnormals included.  in and out must not overlap; no
+ * divisibility or alignment requirement on D, H, W; no atomics: the same bits on every run.  Parity with torchio itself is unpinned.
+ * gvk_axis_circular_conv: ghosting.  Scaling planes of the shifted spectrum along ONE axis by a mask that does not depend on the other two
+ *   frequency axes is a real circular convolution along that axis -- no FFT:  out[..i..] = sum_i' ctab[b][(i - i') mod N] * in[..i'..] along
+ *   array axis axis[b] (0, 1, 2 = D, H, W; any other value is treated as live[b] == 0) of N voxels.  ctab [B][GVK_AXIS_CONV_MAX_N], entries
+ *   0..N-1 of a row used, is built on the host in float64 (data.ghosting_tables): c[m] = delta[m] - (g / N) sum_{j in S} cos(2 pi (j - N/2) m / N),
+ *   S = {0 <= j < N : j % n == 0, j != N/2}, N/2 the integer quotient.  The product runs on the f32-input matrix cores (fp32 operands, one
+ *   rounding per product, fp32 accumulation in ascending i' = an fmaf chain).  Axis 2 multiplies 32 (d, h) lines by the circulant from the
+ *   right (the product of gvk_motion_artifact with one image); axes 0 and 1 multiply a slab [N x 32 contiguous voxels] by it from the left, so
+ *   global accesses run along W in all three forms; the circulant is read from a copy of the row in LDS and never exists in HBM; every output
+ *   element is written once.  axis is not read by the host, so D, H and W must ALL be in 2..GVK_AXIS_CONV_MAX_N.
+ * gvk_gamma_spike: one streaming pass.  kind [B]: GVK_KSPACE_COPY; GVK_KSPACE_GAMMA, y = copysignf(powf(|x|, gamma[b]), x) (zeros keep their
+ *   sign; gamma[b] == 1 is the copy, exactly); GVK_KSPACE_SPIKE, nspikes[b] <= GVK_SPIKE_MAX spikes (clamped):
+ *   y = x + scale * sum_s (c0 * (c1 * c2 - s1 * s2) - s0 * (s1 * c2 + c1 * s2)), every operation rounded once and nothing contracted, the sum
+ *   in ascending s from 0.f, with (ca, sa) = tab[b][s][0 / 1][offset_a + x_a] = float32 of cos / sin(2 pi ((k_sa - N_a/2) x_a mod N_a) / N_a),
+ *   tab [B][GVK_SPIKE_MAX][2][D + H + W] (offsets 0, D, D + H; data.spike_tables reduces the phase in integers and evaluates in float64), and
+ *   scale = float32((double)amp[b] * |mean|), mean = column 2 of the stats row [B][GVK_NORMALIZE_STATS] of gvk_volume_stats of `in` (the
+ *   float64 mean of all voxels): amp * |mean| is amp * max|F| / V for a non-negative volume.  Every table must be a valid pointer whatever
+ *   the kinds.  D*H*W < 2^31.
+ * gvk_axis_gather2: anisotropy.  Along array axis axis[b] of N voxels, with i the output index on that axis:
+ *   out[..i..] = w[b][i] == 0 ? x0 : fmaf(w[b][i], x1 - x0, x0),  x0 = in[..src[b][i][0]..], x1 = in[..src[b][i][1]..];
+ *   src int32 [B][n_max][2] (clamped to 0..N-1 on the device), w float32 [B][n_max], n_max >= max(D, H, W); data.anisotropy_tables does the
+ *   coordinate arithmetic (nearest-neighbour downsampling, linear upsampling, edges clamped) in float64.  Lanes run along W for every axis. */
+enum { GVK_AXIS_CONV_MAX_N = 256, GVK_SPIKE_MAX = 4 };
+enum { GVK_KSPACE_COPY = 0, GVK_KSPACE_GAMMA = 1, GVK_KSPACE_SPIKE = 2 };
+int gvk_axis_circular_conv(const float* in, float* out, const float* ctab, const int32_t* axis, const int32_t* live, int B, int D, int H, int W,
+                           void* stream);
+int gvk_gamma_spike(const float* in, float* out, const int32_t* kind, const float* gamma, const float* amp, const int32_t* nspikes, const float* tab,
+                    const double* stats, int B, int D, int H, int W, void* stream);
+int gvk_axis_gather2(const float* in, float* out, const int32_t* src, const float* w, const int32_t* axis, const int32_t* live, int n_max, int B, int D,
+                     int H, int W, void* stream);
+
 /* ---- nn.Dropout as its own pass (sites without a producing kernel to fuse into) ------------------------------------------
  * Replaces vision_transformer.py:157 (emb_dropout), vpt.py:129,148,152 (prompt_dropout) and carries the masks of the
  * Linear+Dropout pairs (vision_transformer.py:34,54) onto the gradient side.  out32 / out16 (either may be NULL, out32 may alias x)
