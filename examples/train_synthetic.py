@@ -44,13 +44,14 @@ def make_dataset(root, n, num_classes, seed=0):
 
 
 def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False,
-        motion_augment=False):
+        motion_augment=False, batch_mix=False):
     dev = torch.device("cuda:0")
     K = 5
     csv = make_dataset(os.path.join(out, "data"), samples, K, seed)
     config = {"data": dict(data_path=csv, image_folder=os.path.join(out, "data"), batch_size=batch_size, num_workers=0,
                            intensity_augment=intensity_augment,          # train.py:43-51: the OneOf(intensity_augment) stage, on the device
-                           motion_augment=motion_augment),               # ... with tio.RandomMotion as its fourth member (needs the stage)
+                           motion_augment=motion_augment,                # ... with tio.RandomMotion as its fourth member (needs the stage)
+                           **({"batch_mix": dict(seed=seed)} if batch_mix else {})),   # Mixup / CutMix of the batch, timm's defaults
               "model": dict(method=method, backbone=backbone, image_size=160, image_patch_size=16, frames=120, frame_patch_size=12, num_classes=K,
                             channels=1, pool="cls", dim_head=64, dropout=0.1, emb_dropout=0.1, freeze_vit=True, num_prompts=8, prompt_dim=64,
                             prompt_dropout=0.1, deep_prompt=method == "deep_vpt", prompt_latent_dim=20, local_dim=20, local_k=(6, 6, 6),
@@ -72,8 +73,10 @@ def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gavi
         model.train()
         meter.reset()
         for inputs, labels in train_loader:
-            inputs = pre.train_transforms(inputs.to(dev, non_blocking=True))
-            loss = criterion(model(inputs), labels.to(dev))
+            inputs, target = pre.train_transforms(inputs.to(dev, non_blocking=True)), labels.to(dev)
+            if pre.batch_mix is not None:                                 # after the normaliser; the target becomes a data.MixedTarget
+                inputs, target = pre.batch_mix(inputs, target)
+            loss = criterion(model(inputs), target)
             loss.backward()
             opt.step()
             opt.zero_grad()
@@ -103,7 +106,9 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="/tmp/gaviko_run")
     ap.add_argument("--intensity-augment", action="store_true", help="add noise / bias field / blur (one of, p=0.75) to the train transforms")
     ap.add_argument("--motion-augment", action="store_true", help="with --intensity-augment: add k-space motion as the fourth member of that group")
+    ap.add_argument("--batch-mix", action="store_true", help="Mixup / CutMix of each training batch (data.BatchMix, timm's defaults) with the mixed-target loss")
     a = ap.parse_args()
-    res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment)
+    res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment,
+              batch_mix=a.batch_mix)
     print("checkpoint:", res["checkpoint"])
     print("results   :", res["results_csv"])

@@ -48,12 +48,17 @@ host; RandomGamma is a streaming power; RandomAnisotropy collapses to a two-tap 
 ranges and errors; ghosting restores exactly the centre plane (not a band of relative width `restore`), a spike's amplitude is g |mean(x)|
 (torchio's g max|F| / V for a non-negative volume), anisotropy clamps at the edges where torchio pads.  Parity vs torchio is UNPINNED; the kernels
 are pinned against the literal np.fft algorithms and float64 restatements (`tests/kspace_ref.py`).
+
+`BatchMix` (not in the reference; timm.data.Mixup's arguments and arithmetic) is the one transform that combines two samples: Mixup and
+CutMix of the normalised batch in one streaming launch (`csrc/batchmix.hip`), with the mixed target returned as the pair `MixedTarget` that
+the fused losses take (`losses.py`, `gvk_loss_mixed_fwd_bwd`).  It has its own random stream, so DeviceCompose's is untouched; partners come
+from a permutation, not timm's flipped batch.  The kernel is pinned against a float64 restatement (`tests/batchmix_ref.py`).
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -793,6 +798,107 @@ class DeviceCompose:
         return x
 
 
+class MixedTarget(NamedTuple):
+    """The target of a mixed batch, kept as the pair it came from: row i is class a[i] with weight lam[i] and class b[i] with 1 - lam[i].
+    a, b int64 [B], lam float32 [B], device tensors.  The fused losses take it as `target` (losses._FusedLoss.forward)."""
+    a: torch.Tensor
+    b: torch.Tensor
+    lam: torch.Tensor
+
+    def dense(self, num_classes: int, smoothing: float = 0.0) -> torch.Tensor:
+        """[B][K] probability rows (1 - e)(lam onehot(a) + (1 - lam) onehot(b)) + e / K in plain torch: for metrics of one's own and for tests."""
+        lam = self.lam.to(torch.float64).unsqueeze(1)
+        one = lambda t: torch.nn.functional.one_hot(t, num_classes).to(torch.float64)  # noqa: E731
+        return (1.0 - smoothing) * (lam * one(self.a) + (1.0 - lam) * one(self.b)) + smoothing / num_classes
+
+
+def mix_box(lam: float, centre, shape):
+    """timm's rand_bbox carried to three axes: r = (1 - lam)^(1/3), side s_a = int(N_a r), the half-open range [clip(c_a - s_a // 2),
+    clip(c_a + s_a // 2)) per axis, and lam corrected to 1 - box volume / V.  Returns ((d0, d1, h0, h1, w0, w1), lam)."""
+    r = (1.0 - lam) ** (1.0 / 3.0)
+    box, vol = [], 1
+    for c, n in zip(centre, shape):
+        s = int(n * r)
+        lo, hi = int(np.clip(c - s // 2, 0, n)), int(np.clip(c + s // 2, 0, n))
+        box += [lo, hi]
+        vol *= hi - lo
+    return tuple(box), 1.0 - vol / float(np.prod([int(n) for n in shape]))
+
+
+class BatchMix:
+    """timm.data.Mixup on a batch of volumes already on the GPU: `x, target = mix(x, labels)`, called AFTER DeviceCompose (timm mixes
+    normalised tensors), one launch (csrc/batchmix.hip).  Arguments and meanings are timm's: Mixup with lam ~ Beta(mixup_alpha, mixup_alpha),
+    CutMix with a box of volume share 1 - lam, lam ~ Beta(cutmix_alpha, cutmix_alpha); `prob` applies a unit at all, `switch_prob` picks CutMix
+    when both alphas are live; mode 'elem' draws per sample, 'batch' once for the batch.  Unlike timm, a sample's partner is perm[b] of a random
+    permutation (not the flipped batch), and the mixed target comes back as the pair MixedTarget(labels, labels[perm], lam).
+
+    Its random stream is its own (np.random.default_rng(seed)).  Per unit, always all of them so that the stream does not depend on the
+    outcomes: one uniform for `prob`, one for the switch (CutMix when it is < switch_prob and both alphas are > 0, otherwise the only live
+    alpha), lam = rng.beta(alpha, alpha) of the chosen kind, three box centres rng.integers(N_a); after all units one rng.permutation(B).
+    A unit that is not applied, and a CutMix whose box came out empty, is a copy with lam = 1; in 'elem' mode so is a sample whose partner is
+    itself ('batch' mode keeps one mode, lam and box for every sample: mixing a volume with itself changes nothing beyond rounding)."""
+
+    def __init__(self, mixup_alpha: float = 0.8, cutmix_alpha: float = 1.0, prob: float = 1.0, switch_prob: float = 0.5, mode: str = "elem",
+                 seed: Optional[int] = None):
+        if mixup_alpha < 0 or cutmix_alpha < 0:
+            raise ValueError(f"BatchMix: the alphas must not be negative, got {mixup_alpha}, {cutmix_alpha}")
+        if mixup_alpha == 0 and cutmix_alpha == 0:
+            raise ValueError("BatchMix: mixup_alpha and cutmix_alpha are both 0, which mixes nothing")
+        if not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+            raise ValueError(f"BatchMix: prob and switch_prob lie in [0, 1], got {prob}, {switch_prob}")
+        if mode not in ("elem", "batch"):
+            raise ValueError(f"BatchMix: mode is 'elem' or 'batch', not {mode!r}")
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob, self.mode = float(mixup_alpha), float(cutmix_alpha), float(prob), float(switch_prob), mode
+        self.rng = np.random.default_rng(seed)
+        self.last_mix = None                                              # dict(mode, lam, box, perm) of the last call, numpy arrays
+
+    def _unit(self, shape):
+        """(mode, lam, box) of one unit; consumes the same draws whatever comes out."""
+        applied = self.rng.random() < self.prob
+        switch = self.rng.random()
+        cut = self.mixup_alpha == 0 or (self.cutmix_alpha > 0 and switch < self.switch_prob)
+        alpha = self.cutmix_alpha if cut else self.mixup_alpha
+        lam = float(self.rng.beta(alpha, alpha))
+        centre = [int(self.rng.integers(n)) for n in shape]
+        if not applied:
+            return ops.MIX_COPY, 1.0, (0,) * 6
+        if not cut:
+            return ops.MIX_MIXUP, lam, (0,) * 6
+        box, lam = mix_box(lam, centre, shape)
+        if any(box[2 * a + 1] <= box[2 * a] for a in range(3)):
+            return ops.MIX_COPY, 1.0, (0,) * 6
+        return ops.MIX_CUTMIX, lam, box
+
+    def sample(self, B: int, shape) -> dict:
+        """The host tables of one call: mode int32 [B], lam float64 [B], box int32 [B][6], perm int32 [B].  Pure host work."""
+        shape = tuple(int(n) for n in shape)
+        units = [self._unit(shape) for _ in range(B)] if self.mode == "elem" else [self._unit(shape)] * B
+        perm = self.rng.permutation(B).astype(np.int32)
+        mode = np.array([u[0] for u in units], dtype=np.int32)
+        lam = np.array([u[1] for u in units], dtype=np.float64)
+        box = np.array([u[2] for u in units], dtype=np.int32).reshape(B, 6)
+        if self.mode == "elem":
+            own = perm == np.arange(B)
+            mode[own], lam[own], box[own] = ops.MIX_COPY, 1.0, 0
+        self.last_mix = dict(mode=mode, lam=lam, box=box, perm=perm)
+        return self.last_mix
+
+    def __call__(self, x: torch.Tensor, labels: torch.Tensor):
+        if not x.is_cuda:
+            raise RuntimeError("BatchMix runs on the GPU: move the batch first (there is no CPU path)")
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        t = self.sample(x.shape[0], tuple(x.shape[-3:]))
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous().view(-1)
+        lam32 = t["lam"].astype(np.float32)
+        target = MixedTarget(labels, labels[torch.from_numpy(t["perm"].astype(np.int64)).to(x.device)], torch.from_numpy(lam32).to(x.device))
+        if (t["mode"] == ops.MIX_COPY).all():
+            return x, target
+        out = torch.empty_like(x)
+        ops.batch_mix(x, out, t["mode"], lam32, t["perm"], t["box"])
+        return out, target
+
+
 def normalizer(normalization: str = "minmax"):
     """The batch's last step: 'minmax' = RescaleIntensity((0, 1)) as in train.py:50,58; 'percentile' = torchio's MRI recipe
     RescaleIntensity((0, 1), percentiles=(0.5, 99.5)); 'znorm' = ZNormalization(masking_method=ZNormalization.mean)."""
@@ -843,7 +949,9 @@ class DataPreprocessor:
     RandomMotion to it (`motion=True`), config['data']['elastic_augment'] (default False) puts the affine / elastic OneOf of
     `train_transforms(elastic=True)` in place of the affine, config['data']['normalization'] (default 'minmax'; 'percentile', 'znorm') picks
     the last step of all three splits (`normalizer`), config['data']['artifact_augment'] (default False) adds RandomGhosting, RandomSpike,
-    RandomGamma and RandomAnisotropy to the intensity OneOf (`artifacts=True`; it needs intensity_augment)."""
+    RandomGamma and RandomAnisotropy to the intensity OneOf (`artifacts=True`; it needs intensity_augment).  config['data']['batch_mix'] (absent by
+    default: `batch_mix` is None) is a dict of `BatchMix` arguments and builds the `batch_mix` attribute, to call on the training batch and its
+    labels after `train_transforms`."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
@@ -854,6 +962,8 @@ class DataPreprocessor:
         artifacts = bool(config["data"].get("artifact_augment", False))
         self.train_transforms, self.val_transforms, self.test_transforms = (train_transforms(seed, intensity, motion, elastic, norm, artifacts=artifacts),
                                                                             eval_transforms(norm), eval_transforms(norm))
+        mix = config["data"].get("batch_mix")
+        self.batch_mix = BatchMix(**mix) if mix is not None else None
 
     def preprocess(self, df=None):
         import pandas as pd

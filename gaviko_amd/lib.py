@@ -85,6 +85,8 @@ DvptDesc = _struct("DvptDesc", ["z", "enh", "lse", "dcomb", "gate", "bu", "colsu
 AdamDesc = _struct("AdamDesc", ["ptr_tab", "blk_tab", "grad", "m", "v", "norm_sq"], ["nblocks"],
                    ["lr", "beta1", "beta2", "eps", "bias_c1", "bias_c2", "max_norm"])
 LossDesc = _struct("LossDesc", ["logits", "target", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"], ["gamma", "eps"], i64=["ignore_index"])
+LossMixedDesc = _struct("LossMixedDesc", ["logits", "target_a", "target_b", "lam", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"],
+                        ["gamma", "eps", "smoothing"], i64=["ignore_index"])
 DropoutDesc = _struct("DropoutDesc", ["x", "out32", "out16", "seed_ptr"], ["M", "N", "ld", "rows_in", "rows_out", "row_off"], ["drop_p"], ["seed"])
 RowProjDesc = _struct("RowProjDesc", ["w", "bias", "y", "z", "y_split"], ["L", "w_layout", "act", "ld_split", "col_split"])
 LnBwdDesc = _struct("LnBwdDesc", ["dy", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
@@ -178,6 +180,8 @@ SIGNATURES = {
     "gvk_sumsq": [_P, C.c_int64, _P, _P, _P],
     "gvk_adam_step": [C.POINTER(AdamDesc), _P],
     "gvk_loss_fwd_bwd": [C.POINTER(LossDesc), _P],
+    "gvk_loss_mixed_fwd_bwd": [C.POINTER(LossMixedDesc), _P],
+    "gvk_batch_mix": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_dropout_rows": [C.POINTER(DropoutDesc), _P],
     "gvk_volume_minmax": [_P, _P, _I, _L, _P],
     "gvk_rescale_intensity": [_P, _P, _P, _P, _I, _L, _F, _F, _P],
@@ -230,7 +234,7 @@ NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, [
              "gvk_plan_set_timing": (C.c_int, [C.c_int]),
              "gvk_plan_event_elapsed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)])}
 STRUCTS = {"gvk_gemm_desc": GemmDesc, "gvk_skinny_down_desc": SkinnyDownDesc, "gvk_skinny_up_desc": SkinnyUpDesc,
-           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_attention_desc": AttentionDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
+           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_attention_desc": AttentionDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_loss_mixed_desc": LossMixedDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
            "gvk_feature_topk_desc": FeatureTopkDesc}
 
 # diag library only (include/gaviko_hip_diag.h): bound when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so

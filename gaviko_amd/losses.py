@@ -6,7 +6,11 @@
 * `StepMeter` replaces the two per-step host reads of `train.py:327-328` (`running_loss += loss.item() * B`,
   `num_acc += (argmax == labels).sum().item()`): the loss kernel accumulates both on the device; read once per epoch.
 
-The kernels live in `csrc/loss.hip` (`gvk_loss_fwd_bwd`); there is no torch fallback.
+* A `data.MixedTarget` (Mixup / CutMix, `data.BatchMix`) as `target`, or `CrossEntropyLoss(label_smoothing=e)`, takes the second kernel of
+  the same file: row i costs lam_i l(x_i, a_i) + (1 - lam_i) l(x_i, b_i) in ONE launch -- timm's Mixup + SoftTargetCrossEntropy without the
+  dense target matrix, with per-sample lam, class weights, ignored rows and the meter counted once.
+
+The kernels live in `csrc/loss.hip` (`gvk_loss_fwd_bwd`, `gvk_loss_mixed_fwd_bwd`); there is no torch fallback.
 """
 from __future__ import annotations
 
@@ -16,6 +20,7 @@ import torch
 from torch import Tensor, nn
 
 from . import ops
+from .data import MixedTarget
 
 
 class StepMeter:
@@ -47,9 +52,15 @@ class _LossFn(torch.autograd.Function):
         none = mod.reduction == "none"
         loss = torch.empty(x.shape[0] if none else 1, dtype=torch.float32, device=x.device)
         dlogits = torch.empty_like(x)
-        ops.loss_fwd_bwd(x, target.contiguous().view(-1), loss, dlogits, mod._kind, gamma=float(mod._gamma), eps=float(mod.eps),
-                         ignore_index=int(mod.ignore_index), weights=mod._weights_on(x.device), meter=mod.meter.buf if mod.meter is not None else None,
-                         reduction=mod.reduction)
+        kw = dict(gamma=float(mod._gamma), eps=float(mod.eps), ignore_index=int(mod.ignore_index), weights=mod._weights_on(x.device),
+                  meter=mod.meter.buf if mod.meter is not None else None, reduction=mod.reduction)
+        if isinstance(target, MixedTarget):
+            ops.loss_mixed_fwd_bwd(x, target.a.contiguous().view(-1), target.b.contiguous().view(-1), target.lam.float().contiguous().view(-1),
+                                   loss, dlogits, mod._kind, smoothing=float(mod.label_smoothing), **kw)
+        elif mod.label_smoothing > 0:                    # plain label smoothing: no partner
+            ops.loss_mixed_fwd_bwd(x, target.contiguous().view(-1), None, None, loss, dlogits, mod._kind, smoothing=float(mod.label_smoothing), **kw)
+        else:
+            ops.loss_fwd_bwd(x, target.contiguous().view(-1), loss, dlogits, mod._kind, **kw)
         ctx.save_for_backward(dlogits)
         ctx.in_dtype = logits.dtype
         ctx.none = none
@@ -69,6 +80,7 @@ class _FusedLoss(nn.Module):
     eps = 1e-16
     ignore_index = -100
     reduction = "mean"
+    label_smoothing = 0.0
     weights: Optional[Tensor] = None
     meter: Optional[StepMeter] = None
 
@@ -83,9 +95,11 @@ class _FusedLoss(nn.Module):
             self.weights = self.weights.to(device=device, dtype=torch.float32).contiguous()
         return self.weights
 
-    def forward(self, x: Tensor, target: Tensor) -> Tensor:
+    def forward(self, x: Tensor, target: Union[Tensor, MixedTarget]) -> Tensor:
         if x.dim() != 2 or x.shape[-1] < 2:
             raise NotImplementedError("the fused loss takes [batch, classes >= 2] logits (train.py feeds [B, num_classes])")
+        if isinstance(target, Tensor) and target.is_floating_point():
+            raise NotImplementedError("dense [B][K] probability targets are not built: pass class indices, or the pair data.MixedTarget(a, b, lam)")
         return _LossFn.apply(x, target, self)
 
 
@@ -109,10 +123,13 @@ class FocalLoss(_FusedLoss):
 class CrossEntropyLoss(_FusedLoss):
     _kind = ops.LOSS_CE
 
-    def __init__(self, weight: Optional[Tensor] = None, ignore_index: int = -100, reduction: str = "mean") -> None:
+    def __init__(self, weight: Optional[Tensor] = None, ignore_index: int = -100, reduction: str = "mean", label_smoothing: float = 0.0) -> None:
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise NotImplementedError("Reduction {} not implemented.".format(reduction))
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError("label_smoothing must be between 0.0 and 1.0. Got: {}".format(label_smoothing))
+        self.label_smoothing = float(label_smoothing)
         self.weights = weight
         self.ignore_index = ignore_index
         self.reduction = reduction

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -1101,6 +1102,42 @@ def loss_fwd_bwd(logits, target, loss, dlogits, kind, gamma=0.0, eps=1e-16, igno
     L.check(L.load().gvk_loss_fwd_bwd(C.byref(d), L.stream_ptr()), "gvk_loss_fwd_bwd")
 
 
+def loss_mixed_fwd_bwd(logits, target_a, target_b, lam, loss, dlogits, kind, gamma=0.0, eps=1e-16, smoothing=0.0, ignore_index=-100, weights=None,
+                       meter=None, reduction="mean"):
+    """The loss seed for mixed targets: row i costs lam[i] * l(x_i, target_a[i]) + (1 - lam[i]) * l(x_i, target_b[i]), l the per-sample loss of
+    loss_fwd_bwd (class weight included; cross entropy with label smoothing `smoothing` by torch's rule for class-index targets, focal without).
+    target_b and lam (f32 [B]) may both be None: no partner, lam = 1 -- plain label smoothing.  'mean' divides by the sum over the rows that are
+    not ignored of lam w_a + (1 - lam) w_b; a row is ignored when either target is ignore_index; meter[1] counts argmax == the dominant label
+    (target_a where lam >= 0.5).  With smoothing = 0 and lam = 1 the bits are those of loss_fwd_bwd.  One launch, no host read."""
+    _chk(logits, torch.float32, "loss_mixed logits")
+    B, K = logits.shape
+    for t, what in ((target_a, "target_a"), (target_b, "target_b")):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != B):
+            raise ValueError(f"loss_mixed {what} must be a contiguous int64 [B] tensor on the device")
+    if target_a is None or (target_b is None) != (lam is None):
+        raise ValueError("loss_mixed: target_a is required; target_b and lam come together (both None: no partner, lam = 1)")
+    if lam is not None:
+        _chk(lam, torch.float32, "loss_mixed lam", B)
+        if lam.numel() != B:
+            raise ValueError("loss_mixed lam must be a float32 [B] tensor")
+    if not 0.0 <= smoothing <= 1.0:
+        raise ValueError(f"loss_mixed: smoothing must be in [0, 1], got {smoothing}")
+    if kind != LOSS_CE and smoothing != 0.0:
+        raise ValueError("loss_mixed: label smoothing is built for the cross entropy only")
+    _chk(loss, torch.float32, "loss_mixed out", B if reduction == "none" else 1)
+    _chk(dlogits, torch.float32, "loss_mixed dlogits", B * K)
+    if weights is not None:
+        _chk(weights, torch.float32, "loss_mixed weights", K)
+    if meter is not None:
+        _chk(meter, torch.float32, "loss_mixed meter", 3)
+    d = L.LossMixedDesc(logits=L.ptr(logits), target_a=L.ptr(target_a), target_b=L.ptr(target_b) if target_b is not None else None,
+                        lam=L.ptr(lam) if lam is not None else None, weights=L.ptr(weights) if weights is not None else None,
+                        loss=L.ptr(loss), dlogits=L.ptr(dlogits), meter=L.ptr(meter) if meter is not None else None,
+                        B=B, K=K, kind=kind, reduction={"mean": 0, "sum": 1, "none": 2}[reduction], gamma=gamma, eps=eps, smoothing=smoothing,
+                        ignore_index=ignore_index)
+    L.check(L.load().gvk_loss_mixed_fwd_bwd(C.byref(d), L.stream_ptr()), "gvk_loss_mixed_fwd_bwd")
+
+
 # ---- data side + evaluation metrics (train.py:38-62, eval.py:103-122) --------------------------------------------------------
 def minmax_partials(B: int, device) -> torch.Tensor:
     return torch.empty(B * L.load().gvk_minmax_partials(), dtype=torch.float32, device=device)
@@ -1370,6 +1407,32 @@ def axis_gather2(x, out, src, w, axis, live) -> None:
     _chk(live, torch.int32, "axis_gather2 live", B)
     L.check(L.load().gvk_axis_gather2(L.ptr(x), L.ptr(out), L.ptr(src), L.ptr(w), L.ptr(axis), L.ptr(live), int(src.shape[1]), B, D, H, W,
                                       L.stream_ptr()), "gvk_axis_gather2")
+
+
+MIX_COPY, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2                                  # mode[b] of batch_mix (GVK_MIX_*)
+
+
+def batch_mix(x, out, mode, lam, perm, box) -> None:
+    """Mixup / CutMix of a batch in one streaming pass (data.BatchMix).  x, out: float32 volumes on the device, out must not overlap x.  The
+    tables are HOST arrays (numpy or CPU tensors), checked here and then uploaded: mode [B] (MIX_COPY: out[b] = x[b] bit for bit; MIX_MIXUP:
+    out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]] in float32, two roundings; MIX_CUTMIX: out[b] = x[perm[b]] inside the half-open
+    box[b] = (d0, d1, h0, h1, w0, w1) and x[b] outside, bit for bit), lam [B] in [0, 1], perm [B] in [0, B), box [B][6] inside the volume."""
+    B, D, H, W = _one_channel(x, out, "batch_mix")
+    mode, perm = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1), np.ascontiguousarray(perm, dtype=np.int32).reshape(-1)
+    lam, box = np.ascontiguousarray(lam, dtype=np.float32).reshape(-1), np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 6)
+    if not (len(mode) == len(perm) == len(lam) == len(box) == B):
+        raise L.GavikoHipError(f"batch_mix: mode, lam, perm [B] and box [B][6] with B = {B} expected")
+    if ((mode < MIX_COPY) | (mode > MIX_CUTMIX)).any():
+        raise L.GavikoHipError("batch_mix: mode is MIX_COPY, MIX_MIXUP or MIX_CUTMIX")
+    if ((perm < 0) | (perm >= B)).any():
+        raise L.GavikoHipError(f"batch_mix: perm must lie in [0, {B})")
+    if not ((lam >= 0) & (lam <= 1)).all():
+        raise L.GavikoHipError("batch_mix: lam must lie in [0, 1]")
+    lo, hi = box[:, 0::2], box[:, 1::2]
+    if ((lo < 0) | (hi < lo) | (hi > np.array([D, H, W]))).any():
+        raise L.GavikoHipError(f"batch_mix: boxes (d0, d1, h0, h1, w0, w1) must be half-open ranges inside the volume {(D, H, W)}")
+    tabs = [torch.from_numpy(t).to(x.device) for t in (mode, lam, perm, box)]
+    L.check(L.load().gvk_batch_mix(L.ptr(x), L.ptr(out), *[L.ptr(t) for t in tabs], B, D, H, W, L.stream_ptr()), "gvk_batch_mix")
 
 
 def eval_rows(logits, target, proba, pred, confusion) -> None:

@@ -631,6 +631,42 @@ typedef struct gvk_loss_desc {
 } gvk_loss_desc;
 int gvk_loss_fwd_bwd(const gvk_loss_desc* d, void* stream);
 
+/* ---- mixed targets and label smoothing (csrc/loss.hip, csrc/batchmix.hip): Mixup / CutMix across the data / loss boundary ----------
+ * gvk_loss_mixed_fwd_bwd: the loss seed above for rows that carry TWO classes and a weight between them (timm's Mixup + SoftTargetCrossEntropy,
+ *   kept as the pair it came from).  target_a, target_b int64 [B], lam float32 [B]; target_b and lam may both be NULL = no partner, lam = 1.
+ *   l_i = lam_i l(x_i, a_i) + (1 - lam_i) l(x_i, b_i), 1 - lam_i formed in float32, l(x, t) the per-sample loss of gvk_loss_fwd_bwd with its class
+ *   weight: GVK_LOSS_FOCAL as it executes (smoothing must be 0); GVK_LOSS_CE with smoothing e in [0, 1],
+ *   l(x, t) = (1 - e) w_t (-log p_t) + (e / K) sum_k w_k (-log p_k), torch's label_smoothing rule for class-index targets.
+ *   reduction 1 adds the l_i, 2 writes them, 0 divides their sum by sum_i (lam_i w_{a_i} + (1 - lam_i) w_{b_i}) over the rows that are not ignored
+ *   (the weighted-mean rule of gvk_loss_fwd_bwd, which lam = 1 reproduces).  A row is ignored when a_i or b_i equals ignore_index: loss 0,
+ *   gradient row 0.  dlogits = the gradient of the reduced loss (reduction 2: each row's own).  meter[0] and meter[2] as in gvk_loss_fwd_bwd;
+ *   meter[1] += #(argmax == the dominant label: a_i when lam_i >= 0.5, else b_i).  A side whose coefficient is zero is not evaluated and both
+ *   kernels call the same row functions, so smoothing = 0 with lam = 1 (or NULL) returns loss and dlogits bit for bit as gvk_loss_fwd_bwd does.
+ *   One workgroup, one thread per row, strided over B.
+ * gvk_batch_mix: the data side, one streaming pass for a batch in which every sample drew its own mode; x, out float32 [B][D][H][W], out must
+ *   not overlap x; mode, perm int32 [B], lam float32 [B], box int32 [B][6] are DEVICE tables.  With p = perm[b]:
+ *   GVK_MIX_COPY: out[b] = x[b] bit for bit; lam, perm and box are not read for that sample.
+ *   GVK_MIX_MIXUP: out[b] = lam[b] * x[b] + (1 - lam[b]) * x[p] in float32, 1 - lam[b] formed in float32 in the kernel, in the TWO-ROUNDING form
+ *     (each product rounded, then the sum: nothing is contracted), except that a term whose coefficient is exactly 0 is left out and not
+ *     read: lam = 1 gives x[b] and lam = 0 gives x[p], bit for bit.
+ *   GVK_MIX_CUTMIX: box[b] = (d0, d1, h0, h1, w0, w1), half-open: out[b] = x[p] inside the box and x[b] outside, bit for bit; lam is not read.
+ *     An empty box gives x[b], a full box x[p].
+ *   The kernel trusts perm in [0, B) and boxes inside the volume (the caller checks its host tables before the upload).  No atomics; copy
+ *   and CutMix read one source voxel per output voxel, Mixup two.  16-byte accesses for a sample whose addresses are all on the 16-byte grid
+ *   (sample b starts at x + b V: with V odd every second sample is off it and runs voxel by voxel), four scalar loads for a group of four that
+ *   the box's edge or a row's end cuts, a scalar tail of V % 4 voxels.  B <= 65535, D*H*W < 2^31, no divisibility or alignment requirement. */
+enum { GVK_MIX_COPY = 0, GVK_MIX_MIXUP = 1, GVK_MIX_CUTMIX = 2 };
+typedef struct gvk_loss_mixed_desc {
+  const float* logits; const void* target_a; const void* target_b; const float* lam; const float* weights;
+  float* loss; float* dlogits; float* meter;
+  int32_t B, K, kind, reduction;           /* as in gvk_loss_desc */
+  float gamma, eps, smoothing;
+  int64_t ignore_index;
+} gvk_loss_mixed_desc;
+int gvk_loss_mixed_fwd_bwd(const gvk_loss_mixed_desc* d, void* stream);
+int gvk_batch_mix(const float* x, float* out, const int32_t* mode, const float* lam, const int32_t* perm, const int32_t* box, int B, int D, int H, int W,
+                  void* stream);
+
 /* ---- data side and evaluation metrics ------------------------------------------------------------------
  * Replace the torchio transforms of train.py:38-62 on a batch of raw volumes x [B][V] (V = D*H*W, float32, resident in HBM):
  * gvk_volume_minmax: partials [B][gvk_minmax_partials()] = per-slab (min, max) pairs of every volume.
