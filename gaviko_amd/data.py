@@ -258,6 +258,18 @@ class RescaleIntensity:
         """True for the min-max rescale this package had first (its own two kernels, its own bits)."""
         return self.percentiles == (0.0, 100.0) and self.masking_method is None
 
+    def apply(self, x: torch.Tensor, partials: torch.Tensor):
+        """(y, status) for the batch x: status is None on the plain path (min/max into the scratch `partials` of `ops.minmax_partials`),
+        otherwise the int32 [B] device words of `ops.normalize_intensity`."""
+        y = torch.empty_like(x)
+        if self.plain:
+            ops.volume_minmax(x, partials)
+            ops.rescale_intensity(x, partials, y, self.out_min, self.out_max)
+            return y, None
+        stats, _ = ops.volume_stats(x, self.masking_method, want_std=False)
+        _, cutoffs = ops.volume_order_stats(x, stats, self.percentiles)
+        return y, ops.normalize_intensity(x, y, stats, ops.NORMALIZE_RESCALE, cutoffs, self.out_min, self.out_max)
+
 
 class ZNormalization:
     """tio.ZNormalization(masking_method): y = (x - mean) / std with the mean and the unbiased standard deviation of the masked voxels.
@@ -267,6 +279,13 @@ class ZNormalization:
 
     def __init__(self, masking_method=None):
         self.masking_method = _masking_method(masking_method, "ZNormalization")
+
+    def apply(self, x: torch.Tensor, partials: torch.Tensor = None):
+        """(y, status) for the batch x, as `RescaleIntensity.apply`; `partials` is not used."""
+        stats, _ = ops.volume_stats(x, self.masking_method, want_std=True)
+        y = torch.empty_like(x)
+        return y, ops.normalize_intensity(x, y, stats, ops.NORMALIZE_ZNORM)
+
 
 # ---- intensity transforms: train.py:43-48 --------------------------------------------------------------------------------------------
 # Each `sample(rng)` returns None (not applied) or (class name, params) and draws, in this order: one uniform for p, then the
@@ -490,6 +509,15 @@ class OneOf:
         return (self.transforms[i], draw) if self.spatial else draw
 
 
+# ---- host tables of the intensity launches ---------------------------------------------------------------------------------------------
+# A `*_tables` function builds the rows of given samples; a `pack_*` function assembles one launch's tables for a batch from its draws,
+# draws[b] = None or (class name, params) as in `DeviceCompose.last_intensity`: numpy only, rows of samples that drew anything else keep
+# the defaults that make the kernel copy them.
+def _drew(draws, name):
+    """[(b, params)] of the samples that drew `name`."""
+    return [(b, d[1]) for b, d in enumerate(draws) if d and d[0] == name]
+
+
 def blur_tables(sigmas):
     """Host half of `ops.gaussian_blur3d` for sigmas [B][3]: (weights float32 [B][3][2R+1], radius int32 [B][3]) exactly as
     scipy.ndimage.gaussian_filter builds them (truncate = 4.0: radius int(4 sigma + 0.5), exp(-0.5 k^2 / sigma^2) normalised in float64; an
@@ -511,10 +539,33 @@ def blur_tables(sigmas):
     return weights, radius
 
 
+def pack_blur(draws):
+    """`blur_tables` of the batch: sigma 0 on every axis (radius 0, the single weight 1) for a sample that drew no blur."""
+    sig = np.zeros((len(draws), 3), dtype=np.float64)
+    for b, p in _drew(draws, "RandomBlur"):
+        sig[b] = p["std"]
+    return blur_tables(sig)
+
+
 def bias_coefficients(coefficients, order: int, to_order: int) -> np.ndarray:
     """The coefficients of an order-`order` bias field laid out for a launch at `to_order` >= order (the missing terms are zero)."""
     have = {t: c for t, c in zip(bias_terms(order), coefficients)}
     return np.array([have.get(t, 0.0) for t in bias_terms(to_order)], dtype=np.float64)
+
+
+def pack_pointwise(draws):
+    """Tables of `ops.intensity_pointwise`: (kind int32 [B], noise float32 [B][2] = (std, mean), seeds uint64 [B], coeff float32
+    [B][ops.BIAS_COEFFS], order).  order is the largest bias-field order of the batch (0 without one), every field laid out for it."""
+    B = len(draws)
+    kind, noise = np.zeros(B, dtype=np.int32), np.zeros((B, 2), dtype=np.float32)
+    seeds, coeff = np.zeros(B, dtype=np.uint64), np.zeros((B, ops.BIAS_COEFFS), dtype=np.float32)
+    order = max([p["order"] for _, p in _drew(draws, "RandomBiasField")], default=0)
+    for b, p in _drew(draws, "RandomNoise"):
+        kind[b], noise[b], seeds[b] = ops.INTENSITY_NOISE, (p["std"], p["mean"]), p["seed"]
+    for b, p in _drew(draws, "RandomBiasField"):
+        c = bias_coefficients(p["coefficients"], p["order"], order)
+        kind[b], coeff[b, :len(c)] = ops.INTENSITY_BIAS, c
+    return kind, noise, seeds, coeff, order
 
 
 def motion_tables(times, W: int):
@@ -543,6 +594,21 @@ def motion_tables(times, W: int):
     return ctab, src
 
 
+def pack_motion(draws, shape):
+    """Tables of `ops.motion_artifact` for volumes of `shape`: (mats float32 [B][K][3][4], ctab float32 [B][K+1][W], live int32 [B], K), K the
+    largest number of movements in the batch.  A sample with fewer keeps identity maps and zero kernel rows for the rest."""
+    moved = _drew(draws, "RandomMotion")
+    B, W, K = len(draws), shape[2], max(len(p["times"]) for _, p in moved)
+    mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, K, 1, 1))
+    ctab, live = np.zeros((B, K + 1, W), dtype=np.float32), np.zeros(B, dtype=np.int32)
+    for b, p in moved:
+        k = len(p["times"])
+        ctab[b, :k + 1], live[b] = motion_tables(p["times"], W)[0][0], 1
+        for j in range(k):
+            mats[b, j] = affine_matrix((1, 1, 1), p["degrees"][j], p["translation"][j], shape).astype(np.float32)
+    return mats, ctab, live, K
+
+
 def ghosting_tables(num_ghosts, intensity, N) -> np.ndarray:
     """Host half of `ops.axis_circular_conv` for RandomGhosting draws: ctab float32 [B][ops.AXIS_CONV_MAX_N], row b = the real circular
     convolution kernel along an axis of N[b] voxels (entries N[b].. are zero) that scaling the planes j % n == 0, j != N // 2, of the shifted
@@ -567,6 +633,17 @@ def ghosting_tables(num_ghosts, intensity, N) -> np.ndarray:
     return ctab
 
 
+def pack_ghosting(draws, shape):
+    """Tables of `ops.axis_circular_conv` for volumes of `shape`: (ctab, axis int32 [B], live int32 [B]).  A sample that drew no ghosting gets
+    the unit impulse along the last axis and live 0."""
+    B = len(draws)
+    n, g, N = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.float64), np.full(B, shape[2], dtype=np.int64)
+    axis, live = np.full(B, 2, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    for b, p in _drew(draws, "RandomGhosting"):
+        n[b], g[b], axis[b], N[b], live[b] = p["num_ghosts"], p["intensity"], p["axis"], shape[p["axis"]], 1
+    return ghosting_tables(n, g, N), axis, live
+
+
 def spike_tables(positions, shape) -> np.ndarray:
     """Host half of `ops.gamma_spike` for the spikes of ONE sample, positions [S][3] in [0, 1): float32 [ops.SPIKE_MAX][2][D + H + W], entry
     [s][0 / 1][offset_a + x] = cos / sin(2 pi ((k_sa - N_a // 2) x mod N_a) / N_a) with k_sa = floor(pos_sa N_a) (at most N_a - 1) and offsets
@@ -587,6 +664,19 @@ def spike_tables(positions, shape) -> np.ndarray:
     return tab
 
 
+def pack_gamma_spike(draws, shape):
+    """Tables of `ops.gamma_spike` for volumes of `shape`: (kind int32 [B], gamma float32 [B], amp float32 [B], nspikes int32 [B], tab float32
+    [B][ops.SPIKE_MAX][2][D + H + W]); gamma 1 and zeros for a sample that drew neither."""
+    B = len(draws)
+    kind, gamma, amp = np.zeros(B, dtype=np.int32), np.ones(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+    nspikes, tab = np.zeros(B, dtype=np.int32), np.zeros((B, ops.SPIKE_MAX, 2, sum(shape)), dtype=np.float32)
+    for b, p in _drew(draws, "RandomGamma"):
+        kind[b], gamma[b] = ops.KSPACE_GAMMA, p["gamma"]
+    for b, p in _drew(draws, "RandomSpike"):
+        kind[b], amp[b], nspikes[b], tab[b] = ops.KSPACE_SPIKE, p["intensity"], len(p["positions"]), spike_tables(p["positions"], shape)
+    return kind, gamma, amp, nspikes, tab
+
+
 def anisotropy_tables(downsampling, N: int, n_max: Optional[int] = None):
     """Host half of `ops.axis_gather2` for ONE sample's factor f >= 1 along an axis of N voxels: (src int32 [n_max][2], w float32 [n_max]), n_max
     = N unless given.  All in float64: n_low = max(1, ceil(N / f)) low-resolution samples, sample j = the original voxel nearest to
@@ -605,6 +695,100 @@ def anisotropy_tables(downsampling, N: int, n_max: Optional[int] = None):
     src, w = np.zeros((n_max, 2), dtype=np.int32), np.zeros(n_max, dtype=np.float32)
     src[:N, 0], src[:N, 1], w[:N] = low[j0], low[j1], (u - j0).astype(np.float32)
     return src, w
+
+
+def pack_anisotropy(draws, shape):
+    """Tables of `ops.axis_gather2` for volumes of `shape`: (src int32 [B][max(shape)][2], w float32 [B][max(shape)], axis int32 [B], live
+    int32 [B]); zeros for a sample that drew no anisotropy."""
+    B, n_max = len(draws), max(shape)
+    src, w = np.zeros((B, n_max, 2), dtype=np.int32), np.zeros((B, n_max), dtype=np.float32)
+    axis, live = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    for b, p in _drew(draws, "RandomAnisotropy"):
+        axis[b], live[b] = p["axis"], 1
+        src[b], w[b] = anisotropy_tables(p["downsampling"], shape[p["axis"]], n_max)
+    return src, w, axis, live
+
+
+def pack_elastic(fields, num_control_points):
+    """Tables of `ops.elastic_deform`: (ctrl float32 [B][n0][n1][n2][3], live int32 [B]) from fields[b] = None or a sample's coarse field
+    (`RandomElasticDeformation.sample`)."""
+    ctrl = np.zeros((len(fields),) + tuple(num_control_points) + (3,), dtype=np.float32)
+    live = np.zeros(len(fields), dtype=np.int32)
+    for b, f in enumerate(fields):
+        if f is not None:
+            ctrl[b], live[b] = f, 1
+    return ctrl, live
+
+
+# ---- the intensity launches: one launcher per kernel, each uploads its packer's tables and runs the batch through one `ops` entry point ------
+def _dev(a: np.ndarray, device) -> torch.Tensor:
+    return torch.from_numpy(a).to(device)
+
+
+def _launch_pointwise(x, draws):
+    kind, noise, seeds, coeff, order = pack_pointwise(draws)
+    y = torch.empty_like(x)
+    ops.intensity_pointwise(x, y, _dev(kind, x.device), _dev(noise, x.device), _dev(seeds.view(np.int64), x.device), _dev(coeff, x.device), order)
+    return y
+
+
+def _launch_blur(x, draws):
+    weights, radius = pack_blur(draws)
+    y, scratch = torch.empty_like(x), torch.empty_like(x)
+    ops.gaussian_blur3d(x, y, scratch, _dev(weights, x.device), _dev(radius, x.device), int(radius.max()))
+    return y
+
+
+def _launch_motion(x, draws):
+    mats, ctab, live, K = pack_motion(draws, tuple(x.shape[-3:]))
+    part = ops.minmax_partials(x.shape[0], x.device)
+    ops.volume_minmax(x, part)                                            # pad value of the movements = this stage's input minimum
+    y = torch.empty_like(x)
+    ops.motion_artifact(x, y, _dev(mats, x.device), _dev(ctab, x.device), _dev(live, x.device), part, K)
+    return y
+
+
+def _launch_ghosting(x, draws):
+    ctab, axis, live = pack_ghosting(draws, tuple(x.shape[-3:]))
+    y = torch.empty_like(x)
+    ops.axis_circular_conv(x, y, _dev(ctab, x.device), _dev(axis, x.device), _dev(live, x.device))
+    return y
+
+
+def _launch_gamma_spike(x, draws):
+    tables = pack_gamma_spike(draws, tuple(x.shape[-3:]))
+    # the spikes scale with the mean of this stage's input, taken on the device and never read here
+    stats = ops.volume_stats(x, None, want_std=False)[0] if _drew(draws, "RandomSpike") else \
+        torch.zeros((x.shape[0], ops.NORMALIZE_STATS), dtype=torch.float64, device=x.device)
+    y = torch.empty_like(x)
+    ops.gamma_spike(x, y, *[_dev(t, x.device) for t in tables], stats)
+    return y
+
+
+def _launch_anisotropy(x, draws):
+    tables = pack_anisotropy(draws, tuple(x.shape[-3:]))
+    y = torch.empty_like(x)
+    ops.axis_gather2(x, y, *[_dev(t, x.device) for t in tables])
+    return y
+
+
+# (the class names a launch serves, its launcher), in launch order: a new intensity transform adds or joins a row here
+INTENSITY_GROUPS = ((("RandomNoise", "RandomBiasField"), _launch_pointwise),
+                    (("RandomBlur",), _launch_blur),
+                    (("RandomMotion",), _launch_motion),
+                    (("RandomGhosting",), _launch_ghosting),
+                    (("RandomGamma", "RandomSpike"), _launch_gamma_spike),
+                    (("RandomAnisotropy",), _launch_anisotropy))
+
+
+def apply_intensity(x: torch.Tensor, draws) -> torch.Tensor:
+    """One listed intensity transform on the batch: draws[b] = None or (class name, params).  At most one launch per group of
+    INTENSITY_GROUPS, each only when a sample drew one of its classes; samples that drew anything else ride along as copies."""
+    drawn = {d[0] for d in draws if d}
+    for names, launch in INTENSITY_GROUPS:
+        if drawn.intersection(names):
+            x = launch(x, draws)
+    return x
 
 
 class DeviceCompose:
@@ -669,88 +853,6 @@ class DeviceCompose:
         self.last_params, self.last_intensity, self.last_elastic = params, draws, fields
         return mats, flags
 
-    def _intensity_stage(self, x: torch.Tensor, draws) -> torch.Tensor:
-        """One listed intensity transform on the batch: draws[b] = None or (name, params).  At most one pointwise, one blur and one motion
-        launch, each only when a sample drew it; samples that drew nothing ride along as copies."""
-        B, dev = x.shape[0], x.device
-        names = [d[0] if d else None for d in draws]
-        if "RandomNoise" in names or "RandomBiasField" in names:
-            kind, noise = np.zeros(B, dtype=np.int32), np.zeros((B, 2), dtype=np.float32)
-            seeds, coeff = np.zeros(B, dtype=np.uint64), np.zeros((B, ops.BIAS_COEFFS), dtype=np.float32)
-            order = max([d[1]["order"] for d in draws if d and d[0] == "RandomBiasField"], default=0)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomNoise":
-                    kind[b], noise[b], seeds[b] = ops.INTENSITY_NOISE, (d[1]["std"], d[1]["mean"]), d[1]["seed"]
-                elif d and d[0] == "RandomBiasField":
-                    c = bias_coefficients(d[1]["coefficients"], d[1]["order"], order)
-                    kind[b], coeff[b, :len(c)] = ops.INTENSITY_BIAS, c
-            y = torch.empty_like(x)
-            ops.intensity_pointwise(x, y, torch.from_numpy(kind).to(dev), torch.from_numpy(noise).to(dev), torch.from_numpy(seeds.view(np.int64)).to(dev),
-                                    torch.from_numpy(coeff).to(dev), order)
-            x = y
-        if "RandomBlur" in names:
-            sig = np.zeros((B, 3), dtype=np.float64)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomBlur":
-                    sig[b] = d[1]["std"]
-            weights, radius = blur_tables(sig)
-            y, scratch = torch.empty_like(x), torch.empty_like(x)
-            ops.gaussian_blur3d(x, y, scratch, torch.from_numpy(weights).to(dev), torch.from_numpy(radius).to(dev), int(radius.max()))
-            x = y
-        if "RandomMotion" in names:
-            shape, W = tuple(x.shape[-3:]), x.shape[-1]
-            K = max(len(d[1]["times"]) for d in draws if d and d[0] == "RandomMotion")
-            mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, K, 1, 1))
-            ctab, live = np.zeros((B, K + 1, W), dtype=np.float32), np.zeros(B, dtype=np.int32)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomMotion":
-                    k = len(d[1]["times"])                                 # fewer movements than the launch's: the other rows stay zero
-                    ctab[b, :k + 1], live[b] = motion_tables(d[1]["times"], W)[0][0], 1
-                    for j in range(k):
-                        mats[b, j] = affine_matrix((1, 1, 1), d[1]["degrees"][j], d[1]["translation"][j], shape).astype(np.float32)
-            part = ops.minmax_partials(B, dev)
-            ops.volume_minmax(x, part)                                    # pad value of the movements = this stage's input minimum
-            y = torch.empty_like(x)
-            ops.motion_artifact(x, y, torch.from_numpy(mats).to(dev), torch.from_numpy(ctab).to(dev), torch.from_numpy(live).to(dev), part, K)
-            x = y
-        if "RandomGhosting" in names:
-            shape = tuple(x.shape[-3:])
-            n, g, N = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.float64), np.full(B, shape[2], dtype=np.int64)
-            axis, live = np.full(B, 2, dtype=np.int32), np.zeros(B, dtype=np.int32)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomGhosting":
-                    n[b], g[b], axis[b], N[b], live[b] = d[1]["num_ghosts"], d[1]["intensity"], d[1]["axis"], shape[d[1]["axis"]], 1
-            y = torch.empty_like(x)
-            ops.axis_circular_conv(x, y, torch.from_numpy(ghosting_tables(n, g, N)).to(dev), torch.from_numpy(axis).to(dev), torch.from_numpy(live).to(dev))
-            x = y
-        if "RandomGamma" in names or "RandomSpike" in names:
-            shape = tuple(x.shape[-3:])
-            kind, gamma, amp = np.zeros(B, dtype=np.int32), np.ones(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-            nspikes, tab = np.zeros(B, dtype=np.int32), np.zeros((B, ops.SPIKE_MAX, 2, sum(shape)), dtype=np.float32)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomGamma":
-                    kind[b], gamma[b] = ops.KSPACE_GAMMA, d[1]["gamma"]
-                elif d and d[0] == "RandomSpike":
-                    kind[b], amp[b], nspikes[b], tab[b] = ops.KSPACE_SPIKE, d[1]["intensity"], len(d[1]["positions"]), spike_tables(d[1]["positions"], shape)
-            # the spikes scale with the mean of this stage's input, taken on the device and never read here
-            stats = ops.volume_stats(x, None, want_std=False)[0] if "RandomSpike" in names else torch.zeros((B, ops.NORMALIZE_STATS), dtype=torch.float64, device=dev)
-            y = torch.empty_like(x)
-            ops.gamma_spike(x, y, torch.from_numpy(kind).to(dev), torch.from_numpy(gamma).to(dev), torch.from_numpy(amp).to(dev),
-                            torch.from_numpy(nspikes).to(dev), torch.from_numpy(tab).to(dev), stats)
-            x = y
-        if "RandomAnisotropy" in names:
-            shape = tuple(x.shape[-3:])
-            src, w = np.zeros((B, max(shape), 2), dtype=np.int32), np.zeros((B, max(shape)), dtype=np.float32)
-            axis, live = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-            for b, d in enumerate(draws):
-                if d and d[0] == "RandomAnisotropy":
-                    axis[b], live[b] = d[1]["axis"], 1
-                    src[b], w[b] = anisotropy_tables(d[1]["downsampling"], shape[axis[b]], max(shape))
-            y = torch.empty_like(x)
-            ops.axis_gather2(x, y, torch.from_numpy(src).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(axis).to(dev), torch.from_numpy(live).to(dev))
-            x = y
-        return x
-
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:
             raise RuntimeError("DeviceCompose runs on the GPU: move the batch first (there is no CPU path)")
@@ -761,40 +863,21 @@ class DeviceCompose:
         if self.affine or self.elastic or self.spatial or self.flips or self.intensity:
             mats, flags = self.sample(B, shape)
             if any(f is not None for f in self.last_elastic):             # elastic first, a pass of its own (class docstring)
-                ctrl = np.zeros((B,) + self._elastic.num_control_points + (3,), dtype=np.float32)
-                live = np.zeros(B, dtype=np.int32)
-                for b, f in enumerate(self.last_elastic):
-                    if f is not None:
-                        ctrl[b], live[b] = f, 1
+                ctrl, live = pack_elastic(self.last_elastic, self._elastic.num_control_points)
                 ops.volume_minmax(x, part)                                # pad value = this pass's input minimum
                 out = torch.empty_like(x)
-                ops.elastic_deform(x, out, torch.from_numpy(ctrl).to(x.device), torch.from_numpy(live).to(x.device), part)
+                ops.elastic_deform(x, out, _dev(ctrl, x.device), _dev(live, x.device), part)
                 x = out
             if flags.any():
                 ops.volume_minmax(x, part)                                # pad value of the resampling = the input volume's minimum
                 out = torch.empty_like(x)
-                ops.spatial_transform(x, out, torch.from_numpy(mats).to(x.device), torch.from_numpy(flags).to(x.device), part)
+                ops.spatial_transform(x, out, _dev(mats, x.device), _dev(flags, x.device), part)
                 x = out
             for s in range(len(self.intensity)):
-                x = self._intensity_stage(x, [d if len(self.intensity) == 1 else (d[s] if d else None) for d in self.last_intensity])
+                x = apply_intensity(x, [d if len(self.intensity) == 1 else (d[s] if d else None) for d in self.last_intensity])
         self.last_norm_status = None
-        if self.rescale and self.rescale[0].plain:
-            ops.volume_minmax(x, part)
-            y = torch.empty_like(x)
-            ops.rescale_intensity(x, part, y, self.rescale[0].out_min, self.rescale[0].out_max)
-            x = y
-        elif self.rescale:
-            t = self.rescale[0]
-            stats, _ = ops.volume_stats(x, t.masking_method, want_std=False)
-            _, cutoffs = ops.volume_order_stats(x, stats, t.percentiles)
-            y = torch.empty_like(x)
-            self.last_norm_status = ops.normalize_intensity(x, y, stats, ops.NORMALIZE_RESCALE, cutoffs, t.out_min, t.out_max)
-            x = y
-        elif self.znorm:
-            stats, _ = ops.volume_stats(x, self.znorm[0].masking_method, want_std=True)
-            y = torch.empty_like(x)
-            self.last_norm_status = ops.normalize_intensity(x, y, stats, ops.NORMALIZE_ZNORM)
-            x = y
+        for t in self.rescale + self.znorm:                               # the one normaliser, if any
+            x, self.last_norm_status = t.apply(x, part)
         return x
 
 

@@ -1174,15 +1174,20 @@ BLUR_MAX_RADIUS, BLUR_TAPS, BIAS_COEFFS = 16, 33, 20                     # GVK_B
 INTENSITY_COPY, INTENSITY_NOISE, INTENSITY_BIAS = 0, 1, 2                # kind[b] of intensity_pointwise
 
 
+def _one_channel(x, out, what):
+    """The x / out checks every one-channel volume pass shares; returns (B, D, H, W)."""
+    _chk(x, torch.float32, f"{what} in")
+    _chk(out, torch.float32, f"{what} out", x.numel())
+    if x.dim() < 4 or x.numel() != x.shape[0] * x.shape[-3] * x.shape[-2] * x.shape[-1]:
+        raise L.GavikoHipError(f"{what} in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    return x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+
+
 def gaussian_blur3d(x, out, scratch, weights, radius, max_radius) -> None:
     """out = scipy.ndimage.gaussian_filter(x[b], sigma_b) per sample (mode='reflect', truncate=4): weights f32 [B][3][33] and radius i32
     [B][3] are device tables built on the host (data.blur_tables), max_radius their largest radius; scratch is a third buffer of x's size."""
-    _chk(x, torch.float32, "gaussian_blur3d in")
-    _chk(out, torch.float32, "gaussian_blur3d out", x.numel())
+    B, D, H, W = _one_channel(x, out, "gaussian_blur3d")
     _chk(scratch, torch.float32, "gaussian_blur3d scratch", x.numel())
-    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
-    if x.numel() != B * D * H * W:
-        raise L.GavikoHipError("gaussian_blur3d in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
     _chk(weights, torch.float32, "gaussian_blur3d weights", 3 * BLUR_TAPS * B)
     _chk(radius, torch.int32, "gaussian_blur3d radius", 3 * B)
     L.check(L.load().gvk_gaussian_blur3d(L.ptr(x), L.ptr(out), L.ptr(scratch), L.ptr(weights), L.ptr(radius), int(max_radius), B, D, H, W,
@@ -1192,11 +1197,7 @@ def gaussian_blur3d(x, out, scratch, weights, radius, max_radius) -> None:
 def intensity_pointwise(x, y, kind, noise, seeds, coeff, order=3) -> None:
     """y[b] = x[b] (kind 0), x[b] + (std z + mean) (kind 1: noise f32 [B][2] = (std, mean), seeds i64 [B] holding the uint64 bit patterns) or
     x[b] exp(P) (kind 2: coeff f32 [B][20], polynomial order <= 3 for the launch); kind i32 [B].  y may be x."""
-    _chk(x, torch.float32, "intensity_pointwise x")
-    _chk(y, torch.float32, "intensity_pointwise y", x.numel())
-    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
-    if x.numel() != B * D * H * W:
-        raise L.GavikoHipError("intensity_pointwise x: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    B, D, H, W = _one_channel(x, y, "intensity_pointwise")
     _chk(kind, torch.int32, "intensity_pointwise kind", B)
     _chk(noise, torch.float32, "intensity_pointwise noise", 2 * B)
     _chk(seeds, torch.int64, "intensity_pointwise seeds", B)
@@ -1212,11 +1213,7 @@ def motion_artifact(x, out, mats, ctab, live, partials, K) -> None:
     """tio.RandomMotion in one fused pass: out[b] = sum over the K+1 images (x[b] and x[b] resampled through mats f32 [B][K][12], the maps of
     `data.affine_matrix`) of the circular convolution along the last axis with ctab f32 [B][K+1][W] (data.motion_tables).  live i32 [B]: a
     sample with 0 is copied bit for bit; partials = volume_minmax of x (the pad value).  out must not overlap x."""
-    _chk(x, torch.float32, "motion_artifact in")
-    _chk(out, torch.float32, "motion_artifact out", x.numel())
-    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
-    if x.numel() != B * D * H * W:
-        raise L.GavikoHipError("motion_artifact in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    B, D, H, W = _one_channel(x, out, "motion_artifact")
     K = int(K)
     _chk(mats, torch.float32, "motion_artifact mats", 12 * max(K, 0) * B)
     _chk(ctab, torch.float32, "motion_artifact ctab", (max(K, 0) + 1) * W * B)
@@ -1234,11 +1231,7 @@ def elastic_deform(x, out, ctrl, live, partials, field=None) -> None:
     B-spline interpolation of the control-point displacements ctrl f32 [B][n0][n1][n2][3] (voxels, component a along array axis a; 4..16
     points per axis).  live i32 [B]: a sample with 0 is copied bit for bit; partials = volume_minmax of x; field (optional) f32
     [B][3][D][H][W] receives d.  out must not overlap x."""
-    _chk(x, torch.float32, "elastic_deform in")
-    _chk(out, torch.float32, "elastic_deform out", x.numel())
-    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
-    if x.numel() != B * D * H * W:
-        raise L.GavikoHipError("elastic_deform in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
+    B, D, H, W = _one_channel(x, out, "elastic_deform")
     _chk(ctrl, torch.float32, "elastic_deform ctrl")
     if ctrl.dim() != 5 or ctrl.shape[0] != B or ctrl.shape[4] != 3:
         raise L.GavikoHipError(f"elastic_deform ctrl: [B = {B}][n0][n1][n2][3] expected, got {tuple(ctrl.shape)}")
@@ -1352,17 +1345,6 @@ def normalize_intensity(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, m
 
 AXIS_CONV_MAX_N, SPIKE_MAX = 256, 4                                       # GVK_AXIS_CONV_MAX_N, GVK_SPIKE_MAX
 KSPACE_COPY, KSPACE_GAMMA, KSPACE_SPIKE = 0, 1, 2                         # kind[b] of gamma_spike
-
-
-def _one_channel(x, out, what):
-    _chk(x, torch.float32, f"{what} in")
-    _chk(out, torch.float32, f"{what} out", x.numel())
-    if x.dim() < 4:
-        raise L.GavikoHipError(f"{what} in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
-    B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
-    if x.numel() != B * D * H * W:
-        raise L.GavikoHipError(f"{what} in: one channel, [B, D, H, W] or [B, 1, D, H, W]")
-    return B, D, H, W
 
 
 def axis_circular_conv(x, out, ctab, axis, live) -> None:
