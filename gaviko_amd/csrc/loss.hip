@@ -7,6 +7,9 @@
 //   p1 = softmax(clamp(x)),  p2 = softmax(clamp(p1)),  pt = p2[target],  l = w_t (1-pt)^gamma * -log(eps + pt)
 //   loss = sum l / sum (not ignored) w_t
 // and the gradient flows back through both softmaxes and both clamps (zero for every logit outside [eps, 1-eps]).
+// A label that is neither ignore_index nor a class (outside [0, K), compared as the 64-bit value it is) makes its row a BAD row: nothing is
+// read at that index, the row's loss and its whole dlogits row are NaN, the reduced loss is NaN and the meter's correct count gains nothing.
+// The step makes no host read, so the kernel cannot raise as torch does; NaN is the loud device-side equivalent.
 // The logits are [B, K] with K a handful of classes: one workgroup, one thread per sample, every vector recomputed per pass
 // instead of kept (no arrays, no scratch).
 #include "common.hpp"
@@ -53,8 +56,9 @@ __device__ __forceinline__ CeRow ce_row(const float* x, int K) {
   for (int k = 0; k < K; ++k) s += expf(x[k] - m);
   return {m, s};
 }
-// cross entropy: w * -log softmax(x)[t], and its gradient by x[k]
-__device__ __forceinline__ float ce_loss(const float* x, int t, float w, CeRow r) { return w * (logf(r.s) + r.m - x[t]); }
+// cross entropy: w * -log softmax(x)[t], and its gradient by x[k].  m - x[t] comes first: it is exact for logits of like size, where
+// (log s + m) - x[t] rounds log s to the spacing of m (1e-3 for logits near 1e4) before the large parts cancel.
+__device__ __forceinline__ float ce_loss(const float* x, int t, float w, CeRow r) { return w * (logf(r.s) + (r.m - x[t])); }
 __device__ __forceinline__ float ce_grad(const float* x, int k, int t, float w, CeRow r) { return w * (expf(x[k] - r.m) / r.s - (k == t ? 1.f : 0.f)); }
 
 struct FocalRow { Soft1 a; float m2, s2; };                // both softmaxes' statistics: they do not depend on the target
@@ -93,8 +97,12 @@ __device__ __forceinline__ float focal_grad(const float* x, int k, int t, FocalR
 
 // The end of both kernels: a fixed tree over the 256 threads' (loss, denominator, correct) sums, the division of the gradient rows by the
 // mean's denominator, the reduced loss and the meter.
+// 'mean' with a zero denominator (every row ignored, or zero class weights on all the others): the loss is 0/0 = NaN for both kinds, and the
+// gradient is what the references return -- torch's cross entropy leaves the ignored rows' zeros alone and divides the others (NaN); the
+// focal reference divides every row, ignored ones too (NaN), except the logits outside its clamp, whose gradient the clamp has masked to 0.
+struct LossRows { const float* logits; const long long* ta; const long long* tb; long long ignore_index; float lo, hi; int kind; };   // tb may be null
 __device__ __forceinline__ void loss_finish(float (*red)[256], float lsum, float wsum, float correct, float* loss_out, float* dlogits, float* meter,
-                                            int B, int K, int reduction) {
+                                            int B, int K, int reduction, LossRows q) {
   const int tid = threadIdx.x;
   red[0][tid] = lsum; red[1][tid] = wsum; red[2][tid] = correct;
   __syncthreads();
@@ -106,9 +114,19 @@ __device__ __forceinline__ void loss_finish(float (*red)[256], float lsum, float
   }
   const float den = reduction == 0 ? red[1][0] : 1.f;      // 'mean': sum over not-ignored samples of their weight
   const float loss = red[0][0] / den;
-  for (int b = tid; b < B; b += 256) {
-    float* dx = dlogits + (size_t)b * K;
-    for (int k = 0; k < K; ++k) dx[k] /= den;
+  if (den != 0.f) {
+    for (int b = tid; b < B; b += 256) {
+      float* dx = dlogits + (size_t)b * K;
+      for (int k = 0; k < K; ++k) dx[k] /= den;
+    }
+  } else {
+    for (int b = tid; b < B; b += 256) {
+      const float* x = q.logits + (size_t)b * K;
+      float* dx = dlogits + (size_t)b * K;
+      if (q.kind == 0 && (q.ta[b] == q.ignore_index || (q.tb != nullptr && q.tb[b] == q.ignore_index))) continue;
+      for (int k = 0; k < K; ++k)
+        if (q.kind == 0 || (x[k] >= q.lo && x[k] <= q.hi)) dx[k] /= den;
+    }
   }
   if (tid == 0) {
     if (reduction != 2) loss_out[0] = loss;
@@ -131,6 +149,12 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs p) {
     float* dx = p.dlogits + (size_t)b * K;
     const long long tg = p.target[b];
     const bool ign = tg == p.ignore_index;
+    if (!ign && (tg < 0 || tg >= (long long)K)) {         // a bad row: not a class, nothing is read at it
+      for (int k = 0; k < K; ++k) dx[k] = NAN;
+      if (p.reduction == 2) p.loss[b] = NAN;
+      lsum += NAN;
+      continue;
+    }
     const int t = ign ? 0 : (int)tg;
     const float w = p.weights != nullptr ? p.weights[t] : 1.f;
     if (!ign && argmax_row(x, K) == t) correct += 1.f;
@@ -154,7 +178,7 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs p) {
     if (p.reduction == 2) p.loss[b] = f.l;                // 'none' (focal_loss.py:118): the per-sample vector, dlogits = its rows' own gradients
     for (int k = 0; k < K; ++k) dx[k] = focal_grad(x, k, t, r, f, lo, hi);
   }
-  loss_finish(red, lsum, wsum, correct, p.loss, p.dlogits, p.meter, p.B, K, p.reduction);
+  loss_finish(red, lsum, wsum, correct, p.loss, p.dlogits, p.meter, p.B, K, p.reduction, LossRows{p.logits, p.target, nullptr, p.ignore_index, lo, hi, p.kind});
 }
 
 // ---- mixed targets (Mixup / CutMix) and label smoothing --------------------------------------------------------------------------------
@@ -162,7 +186,8 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs p) {
 //   l(x, t) = (1 - e) w_t (-log p_t) + (e / K) sum_k w_k (-log p_k)      (torch's label_smoothing rule for class-index targets).
 // A side whose coefficient is zero is not evaluated, so lam = 1 (or no partner at all) with e = 0 runs exactly the operations of loss_kernel
 // and returns its bits.  'mean' divides by sum_i (lam_i w_{a_i} + (1 - lam_i) w_{b_i}) over the rows that are not ignored; a row is ignored
-// when a_i or b_i is ignore_index; the meter's accuracy counts argmax == the dominant label (a_i when lam_i >= 0.5, else b_i).
+// when a_i or b_i is ignore_index, and bad (see the top of the file) when it is not ignored and a_i or b_i is no class, whatever lam_i is;
+// the meter's accuracy counts argmax == the dominant label (a_i when lam_i >= 0.5, else b_i).
 struct LossMixedArgs {
   const float* logits; const long long* target_a; const long long* target_b; const float* lam; const float* weights;
   float* loss; float* dlogits; float* meter;
@@ -185,6 +210,12 @@ __global__ __launch_bounds__(256) void loss_mixed_kernel(LossMixedArgs p) {
     if (ign) {
       for (int k = 0; k < K; ++k) dx[k] = 0.f;
       if (p.reduction == 2) p.loss[b] = 0.f;
+      continue;
+    }
+    if (ta < 0 || ta >= (long long)K || tb < 0 || tb >= (long long)K) {   // a bad row: either label is not a class, nothing is read at it
+      for (int k = 0; k < K; ++k) dx[k] = NAN;
+      if (p.reduction == 2) p.loss[b] = NAN;
+      lsum += NAN;
       continue;
     }
     const float ca = p.lam != nullptr ? p.lam[b] : 1.f, cb = 1.f - ca;
@@ -233,7 +264,7 @@ __global__ __launch_bounds__(256) void loss_mixed_kernel(LossMixedArgs p) {
     lsum += l;
     if (p.reduction == 2) p.loss[b] = l;
   }
-  loss_finish(red, lsum, wsum, correct, p.loss, p.dlogits, p.meter, p.B, K, p.reduction);
+  loss_finish(red, lsum, wsum, correct, p.loss, p.dlogits, p.meter, p.B, K, p.reduction, LossRows{p.logits, p.target_a, p.target_b, p.ignore_index, lo, hi, p.kind});
 }
 
 }  // namespace gvk

@@ -10,6 +10,12 @@
   the same file: row i costs lam_i l(x_i, a_i) + (1 - lam_i) l(x_i, b_i) in ONE launch -- timm's Mixup + SoftTargetCrossEntropy without the
   dense target matrix, with per-sample lam, class weights, ignored rows and the meter counted once.
 
+* Labels are checked on the device.  A label that is neither `ignore_index` nor a class in [0, K) -- a label file numbered 1..K, say --
+  cannot raise as torch does (the step makes no host read), so it is answered with NaN: that row's loss and gradient row are NaN, the
+  'mean' / 'sum' loss is NaN, and the meter does not count the row as correct.  A batch whose rows are all ignored has a NaN 'mean' loss;
+  `CrossEntropyLoss` then returns all-zero gradients as torch does, `FocalLoss` NaN gradients as its reference does (0 at the logits
+  its clamp cuts off).
+
 The kernels live in `csrc/loss.hip` (`gvk_loss_fwd_bwd`, `gvk_loss_mixed_fwd_bwd`); there is no torch fallback.
 """
 from __future__ import annotations

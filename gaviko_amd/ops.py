@@ -1085,7 +1085,13 @@ LOSS_CE, LOSS_FOCAL = 0, 1
 
 def loss_fwd_bwd(logits, target, loss, dlogits, kind, gamma=0.0, eps=1e-16, ignore_index=-100, weights=None, meter=None, reduction="mean"):
     """loss[0] = criterion(logits, target), dlogits = its gradient, meter += (loss*B, #correct, B): one launch, no host read.
-    reduction='none': loss receives the B per-sample values and meter[0] their sum (losses.StepMeter)."""
+    reduction='none': loss receives the B per-sample values and meter[0] their sum (losses.StepMeter).
+    A label that is neither ignore_index nor within [0, K) (compared as the int64 it is: 2^32 + 1 is not class 1) makes its row a bad row.
+    The kernel reads nothing at that index; there is no host read, so it cannot raise as torch does ("Target 5 is out of bounds") and
+    answers with NaN instead: the row's per-sample loss and its whole dlogits row are NaN, 'mean' and 'sum' return NaN, and the meter's
+    correct count gains nothing.  'mean' with a zero denominator (every row ignored, or zero class weights on all the others) returns
+    NaN; the cross entropy then leaves the ignored rows' gradient at zero and makes the others NaN, as torch does, and the focal loss
+    makes every row NaN, ignored ones too, except at the logits outside its clamp (their gradient stays 0), as its reference does."""
     _chk(logits, torch.float32, "loss logits")
     B, K = logits.shape
     if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != B:
@@ -1108,7 +1114,10 @@ def loss_mixed_fwd_bwd(logits, target_a, target_b, lam, loss, dlogits, kind, gam
     loss_fwd_bwd (class weight included; cross entropy with label smoothing `smoothing` by torch's rule for class-index targets, focal without).
     target_b and lam (f32 [B]) may both be None: no partner, lam = 1 -- plain label smoothing.  'mean' divides by the sum over the rows that are
     not ignored of lam w_a + (1 - lam) w_b; a row is ignored when either target is ignore_index; meter[1] counts argmax == the dominant label
-    (target_a where lam >= 0.5).  With smoothing = 0 and lam = 1 the bits are those of loss_fwd_bwd.  One launch, no host read."""
+    (target_a where lam >= 0.5).  With smoothing = 0 and lam = 1 the bits are those of loss_fwd_bwd.  One launch, no host read.
+    A row that is not ignored and whose target_a or target_b lies outside [0, K) (as an int64), whatever its lam, is a bad row as in
+    loss_fwd_bwd: nothing is read at that index, its loss and dlogits row are NaN, 'mean' and 'sum' return NaN, the meter's correct count
+    gains nothing.  'mean' with a zero denominator behaves as there too."""
     _chk(logits, torch.float32, "loss_mixed logits")
     B, K = logits.shape
     for t, what in ((target_a, "target_a"), (target_b, "target_b")):
@@ -1429,9 +1438,13 @@ def eval_rows(logits, target, proba, pred, confusion) -> None:
 
 
 def ovr_auc_counts(proba, target, counts) -> None:
+    """counts[c] += {2 #{p_i > p_j} + #{p_i == p_j}, n_pos, n_neg} over positives i (target == c) and negatives j of column c of proba
+    f32 [N, K].  The kernel ADDS to counts (int64 [K][3]): the caller zeroes the buffer, and a second call on it accumulates."""
     _chk(proba, torch.float32, "ovr_auc proba")
     N, K = proba.shape
     _chk(counts, torch.int64, "ovr_auc counts", 3 * K)
+    if not target.is_cuda or target.dtype != torch.int64 or target.numel() != N or not target.is_contiguous():
+        raise ValueError("ovr_auc_counts target must be a contiguous int64 [N] tensor on the device")
     L.check(L.load().gvk_ovr_auc_counts(L.ptr(proba), L.ptr(target), L.ptr(counts), N, K, L.stream_ptr()), "gvk_ovr_auc_counts")
 
 
