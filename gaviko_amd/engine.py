@@ -6,7 +6,9 @@ One `Engine` per model instance.  It owns
   * the per-batch-size workspace (fp32 residual streams per layer, bf16 GEMM operands, saved statistics),
   * the ordered list of C-ABI launches that make up forward() and backward().
 The method-specific halves are mixins (engine_gaviko.py, engine_peft.py), and so are the analysis entry points of gaviko_amd.explain /
-uncertainty / features (engine_analysis.py); the sweeps here call their hooks.
+uncertainty / features (engine_analysis.py); the sweeps here call their hooks.  What is STATIC about a method -- token geometry, feature
+flags, its own workspace slots, name patterns, which tensors its own gradient kernels cover -- is one spec per kind in engine_methods.py
+(`self.method`); `self.kind` is compared only where a sweep picks its next launch.
 Everything is enqueued on torch's current HIP stream; nothing synchronises, so a whole step can be captured in a HIP
 graph.  There is no CPU / eager fallback.
 
@@ -31,6 +33,7 @@ from .engine_common import (GRAPH_WARMUP, PLAN_TIMING, SEED_EMB, SEED_LAYER, SEE
                             _on, flat_views)
 from .engine_common import evp_highpass_operator  # noqa: F401  (re-exported: tests import it from here)
 from .engine_gaviko import GavikoPaths
+from .engine_methods import METHOD_SPECS
 from .engine_peft import PeftPaths
 
 # bench.py instrumentation: when set to a dict, plans recorded from then on bracket every GEMM launch (and the patch-embed
@@ -38,16 +41,13 @@ from .engine_peft import PeftPaths
 GEMM_MARKS = None
 
 
-# classes whose backbone tensors can train (engine_peft.py `_bb_*`): the plain ViT (`fft` / `bitfit`); every class that freezes by default, with freeze_vit=False
-_BB_KINDS = ("vit", "adaptformer", "gaviko", "dvpt", "evp", "vpt", "ssf")
-
-
 class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
     def __init__(self, kind: str, cfg: dict, params: Dict[str, torch.nn.Parameter], depth, heads, dim, mlp_dim):
         self.kind, self.cfg, self.p = kind, cfg, params
+        self.method = METHOD_SPECS.get(kind)           # the kind's static facts: geometry, flags, its own buffers and names (engine_methods.py)
+        if self.method is None:
+            raise L.GavikoHipError(f"unknown engine kind {kind!r}: expected one of {tuple(METHOD_SPECS)}")
         self.depth, self.heads, self.C, self.mlp = depth, heads, dim, mlp_dim
-        self.lora_layers = frozenset(cfg.get("lora_layer") or range(depth)) if kind == "melo" else frozenset()
-        self.names = Names(kind, self.lora_layers if kind == "melo" else None)
         fp, ip = cfg["frame_patch_size"], cfg["image_patch_size"]
         self.patch = (fp, ip, ip)
         self.grid = (cfg["frames"] // fp, cfg["image_size"] // ip, cfg["image_size"] // ip)
@@ -68,52 +68,8 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         if cfg.get("channels", 1) != 1:
             raise L.GavikoHipError("patch embedding is built for single-channel volumes (channels = 1)")
         self.pool = cfg.get("pool", "cls")
-        if kind == "gaviko":
-            self.P = cfg["num_prompts"]
-            self.Lat = cfg.get("prompt_latent_dim", 20)
-            if cfg.get("local_dim", 20) != self.Lat:
-                raise L.GavikoHipError("local_dim and prompt_latent_dim must match (one latent width per build)")
-            self.share = cfg.get("share_factor", 1)
-            self.T = self.P + 1 + self.N
-            self.row_off = self.P + 1
-            dhw = cfg.get("DHW", (10, 10, 10))
-            if dhw is None:
-                self.win = tuple(2 * g + 1 for g in self.grid)     # no mask == a window that always covers the grid
-            else:
-                if tuple(dhw) != self.grid:
-                    raise L.GavikoHipError(f"DHW={tuple(dhw)} does not match the patch grid {self.grid}")
-                self.win = tuple(cfg.get("local_k", (3, 6, 6)))
-        elif kind == "evp":
-            self.P, self.T, self.row_off = 0, 1 + self.N, 1
-            self.r = dim // int(cfg.get("scale_factor", 32))                              # rank of the prompt latents (evp.py:41-42)
-            widths = [w_ for w_ in (4, 8, 16, 20, 24, 32) if w_ >= self.r]
-            if not widths or self.r < 1:
-                raise L.GavikoHipError(f"EVP: prompt rank dim/scale_factor = {self.r} is outside the rank-L kernels' range (1..32)")
-            self.Lp = widths[0]                                                            # latents are zero-padded to this width
-            self.freq = float(cfg.get("freq_nums", 0.25))
-        elif kind == "dvpt":
-            self.P = cfg.get("num_prompts", 50)
-            self.Lat = 20                                                                  # share_MLP.latent_dim (dvpt.py:27)
-            self.T, self.row_off = self.P + 1 + self.N, self.P + 1
-        elif kind == "vpt":
-            self.P = cfg.get("num_prompts", 8)
-            self.pd = cfg.get("prompt_dim", 64)
-            self.deep = bool(cfg.get("deep_prompt", True))
-            self.T, self.row_off = 1 + self.P + self.N, 1 + self.P
-        else:
-            self.P, self.T, self.row_off = 0, 1 + self.N, 1
-        if kind == "melo":
-            self.r, self.lora_s = int(cfg["r"]), int(cfg["alpha"]) // int(cfg["r"])      # integer alpha // r (melo.py:45-46)
-        if kind == "adaptformer":
-            self.adim = 64                                                                # Adapter(down_dim=64), adaptformer.py:25
-        # tokens entering layer i.  Deep VPT rebuilds the sequence before every layer > 0 as [cls | P prompts | x[:, 1+prompt_dim:]]
-        # (vpt.py:147-153: the slice uses deep_prompt_embeddings[i].shape[1] == prompt_dim), so it shrinks by prompt_dim - P per layer.
-        self.Ts = [self.T] * depth
-        if kind == "vpt" and self.deep:
-            for i in range(1, depth):
-                self.Ts[i] = self.Ts[i - 1] - self.pd + self.P
-            if self.Ts[-1] <= 1 + self.pd:
-                raise L.GavikoHipError("deep VPT: the shrinking sequence runs out of tokens for this depth / prompt_dim")
+        self.method.geometry(self, cfg)                # P, T, Ts, row_off and the method's own widths
+        self.names = Names(kind, self.lora_layers if self.method.wraps_qkv else None)
         self._w16: Dict[str, torch.Tensor] = {}
         self._w16_version = None
         self._shadowed = frozenset(self._backbone_weight_names())
@@ -128,43 +84,9 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         self._recording = False
         self._keep_inputs = False               # unfrozen backbone weights: the forward keeps the GEMM inputs for their wgrads
         self._eff: Dict[str, torch.Tensor] = {}
-        # GPA projections of backbone rows ride along in the backbone's LayerNorm kernels (gvk_layernorm_fwd_proj, gvk_ln_bwd_desc.proj)
-        self._fuse_proj = (kind == "gaviko" and not self.fp32 and ops.rowproj_supported(self.Lat, dim)
-                           and L.diag_env("GAVIKO_HIP_FUSE_PROJ", "1") != "0")
-        # In the backward, the LayerNorm-1 backward of layer i > 0 also leaves dcomb = dG . W_up for the GPA core of layer i - 1 (computing it
-        # on the GPA stream instead was measured slower and removed: DESIGN.md 7e).
-        # Rows nobody consumes are not computed (round 5).  With a frozen backbone the loss reads the LAST layer's output only at the rows
-        # the head pools (prompts + CLS, gaviko.py:316), so that layer's MLP -- a row-wise function -- runs on those rows in the forward, and
-        # its backward (fc2 / fc1 dgrad, LayerNorm 2) on the same rows: every other row of the incoming gradient is an exact zero.  At the
-        # other end only the P prompt rows of the FIRST layer's input carry a trainable tensor (patch embedding, cls token and position
-        # embedding are frozen: gaviko.py:540-548), so its qkv dgrad and LayerNorm-1 backward run on those rows.  Logits and every gradient
-        # are bit-identical to the full computation (tests/test_model_gpu.py::test_pruned_rows_are_dead); GAVIKO_HIP_PRUNE=0 computes
-        # everything (the golden taps of the last layer's far rows need that).
-        self.prune_dead_rows = kind == "gaviko" and not self.fp32 and os.environ.get("GAVIKO_HIP_PRUNE", "1") != "0"
-        # frozen backbone: the fc1 / qkv dgrad GEMMs hand the LayerNorm backward its input gradient in bf16 (half the bytes on both sides; the other
-        # operands of that chain -- dpre, dqkv, the dgrad operands -- are bf16 already)
-        self._dy16 = kind == "gaviko" and not self.fp32 and L.diag_env("GAVIKO_HIP_DY16", "1") != "0"
-        # ... and fc1's forward epilogue leaves GELU'(pre) instead of pre (it has the exponential in hand and VALU to spare behind its two output
-        # streams); the fc2 dgrad epilogue then multiplies instead of evaluating the derivative (isolated: 33.7 -> 30.3 us with a free derivative)
-        self._gelu_grad = kind == "gaviko" and not self.fp32 and L.diag_env("GAVIKO_HIP_GELU_GRAD", "1") != "0"
-        self._fuse_local = kind == "gaviko" and ops.side_tile_supported(self.Lat, dim)
-        self._fuse_bnd = self._fuse_local and L.diag_env("GAVIKO_HIP_FUSE_BOUNDARY", "1") != "0"
-        self._fuse_next = self._fuse_local and L.diag_env("GAVIKO_HIP_FUSE_NEXT", "1") != "0"
         self._mwsa_pending = None
-        # every parameter gradient of a side-path module of one layer in ONE launch per stream (csrc/paramgrad.hip; round 4)
-        self._pgrad = (kind == "gaviko" and ops.param_grads_supported(cfg.get("prompt_latent_dim", 20), dim)
-                       and L.diag_env("GAVIKO_HIP_PGRAD", "1") != "0")
-        # GPA up-projection as K-concatenation of the MLP's second Linear: 64 spare K columns carry the rank-L product in split-bf16 form,
-        # A' = [act | lat_hi | lat_lo | lat_hi | 1 | 1], W' = [W_fc2 | Wup_hi | Wup_hi | Wup_lo | b_hi | b_lo] (fp32-grade: the dropped
-        # lo.lo term is 2^-16 relative), so x + ff(x) + proj_up(.) (gaviko.py:187 after vision_transformer.py:34) is ONE GEMM and the
-        # main stream loses a full read-modify-write pass over the token stream per layer
-        self._fuse_up = (kind == "gaviko" and not self.fp32 and 3 * self.Lat + 2 <= 64 and L.diag_env("GAVIKO_HIP_FUSE_UP", "1") != "0")
+        self.method.flags(self, cfg)                   # the fusions of the frozen GAViKO path; all off for every other kind
         self.ldx = self.mlp + 64 if self._fuse_up else self.mlp      # row stride of the MLP hidden buffers
-        # First LayerNorm of layers 1.. folded into their qkv projection (vision_transformer.py:49,61-62): the fc2 GEMM of the layer below
-        # leaves the bf16 copy of its output rows and per-row (sum, sum of squares) partials, the prompt-fix kernel turns them into mean /
-        # rstd, and the qkv GEMM runs on the RAW rows against gamma o W with  rstd * (acc - mean * c1) + c2  in its epilogue -- one launch
-        # (and its dependency gap) less per layer on the main stream.  128-column tiles only (C % 128 == 0: ViT-B / ViT-L).
-        self._fold_ln1 = (self._fuse_up and self._fuse_proj and dim % 128 == 0 and L.diag_env("GAVIKO_HIP_FOLD_LN1", "1") != "0")
         self._fold: Dict[str, torch.Tensor] = {}
         self._fold_version = None
         self._fold_names = frozenset(self._fold_deps()) if self._fold_ln1 else frozenset()
@@ -363,51 +285,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         if self._fold_ln1:
             ws["xg16"] = z(M, C, bf16)                                          # bf16 copy of the global stream entering a folded layer
             ws["spart"] = torch.zeros((C // 64) * M * 2, device=device)         # per-row (sum, sum of squares) over 64-column groups
-        if self.kind == "gaviko":
-            Lt, P, BN = self.Lat, self.P, B * N
-            ws["Lc"] = [torch.zeros((BN, C), device=device) for _ in range((self.depth + 1) if train else 2)]
-            mk = lambda *s: torch.zeros(s, device=device)
-            ws["mw"] = [dict(mean=mk(BN), rstd=mk(BN), lat=mk(BN, Lt), qkv=mk(BN, 3 * Lt), ctx=mk(BN, Lt), lse=mk(BN)) for _ in range(nsave)]
-            ws["gp"] = [dict(zx=mk(M, Lt), xl=mk(M, Lt), zl=mk(BN, Lt), ll=mk(BN, Lt), imp=mk(B, P), gw=mk(B), enh=mk(B, P, Lt),
-                             prm=mk(B, P, Lt), qg=mk(B, P, Lt), ql=mk(B, P, Lt), cg=mk(B, P, Lt), cl=mk(B, P, Lt), lse_g=mk(B, P),
-                             lse_l=mk(B, P)) for _ in range(nsave)]
-        if self.kind == "evp":
-            mk = lambda *s_: torch.zeros(s_, device=device)
-            BN, Lp = B * N, self.Lp
-            ws["xc"] = z(BN, C, f32)
-            ws["hp"] = torch.zeros_like(ws["img"])
-            ws["hcols"] = z(BN, self.Kp, f32)
-            ws["hc"] = z(BN, 64, f32)
-            ws["ev"] = dict(e=mk(BN, Lp), s=mk(BN, Lp), pre=[mk(BN, Lp) for _ in range(nsave)], u=[mk(BN, Lp) for _ in range(nsave)],
-                            tmp=z(BN, C, f32))
-            if train:
-                ws["evb"] = dict(du=mk(BN, Lp), dpre=mk(BN, Lp), ds_tmp=mk(BN, Lp), ds=mk(BN, Lp))
-                ws["scratch"] = mk(max(ops.outer_scratch_elems(Lp, self.Kp), 128 * C))
-                ws["rscratch"] = mk(32 * (Lp * Lp + Lp + 64))
-        if self.kind == "dvpt":
-            mk = lambda *s_: torch.zeros(s_, device=device)
-            ws["dv"] = [dict(z=mk(M, self.Lat), enh=mk(B, self.P, self.Lat), lse=mk(B, self.P)) for _ in range(nsave)]
-        if self.kind == "adaptformer":
-            ws["xa"] = z(M, C, bf16)
-            ws["ad"] = [dict(mean=torch.zeros(M, device=device), rstd=torch.zeros(M, device=device), h16=z(M, self.adim, bf16))
-                        for _ in range(nsave)]
-            if train:
-                ws["dh16"] = z(M, self.adim, bf16)
-                ws["h32"] = torch.zeros((M, self.adim), device=device)
-                ws["dh32"] = torch.zeros((M, self.adim), device=device)
-        if self.kind == "melo":
-            ws["merge32"] = torch.zeros((3 * C, C), device=device)
-            if train:
-                mk = lambda *s_: torch.zeros(s_, device=device)
-                ws["dq32"], ws["dv32"] = mk(M, C), mk(M, C)
-                ws["lu"] = dict(uq=mk(M, self.r), uv=mk(M, self.r), duq=mk(M, self.r), duv=mk(M, self.r))
-        if self.kind == "vpt":
-            R = (self.depth if self.deep else 1) * self.P
-            ws["vproj"] = torch.zeros((R, C), device=device)
-            ws["Go"] = z(M, C, f32)                          # layer output before the deep-VPT re-pack
-            if train:
-                ws["dvproj"] = torch.zeros((R, C), device=device)
-                ws["dGv"] = z(M, C, f32)
+        self.method.forward_buffers(self, ws, B, device, train, nsave)      # the method's own slots (engine_methods.py)
         if train:
             ws["dG"] = [z(M, C, f32), z(M, C, f32)]          # ping-pong gradient of the global stream
             ws["dG16"] = z(M, C, bf16)
@@ -418,41 +296,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
             ws["dctx"] = z(M, C, bf16)
             ws["dqkv"] = z(M, 3 * C, bf16)
             ws["delta"] = torch.zeros((B, self.heads, T), device=device)
-            if self.kind == "gaviko":
-                Lt, P, BN = self.Lat, self.P, B * N
-                mk = lambda *s: torch.zeros(s, device=device)
-                ng = ops.gpa_gate_param_count(Lt, P)
-                ws["dL"] = [mk(BN, C), mk(BN, C)]
-                ws["dGb"] = ops.act_zeros(M, C, torch.float32, device)       # second layer-boundary gradient buffer (parity ping-pong)
-                ws["bw"] = dict(dcomb=mk(M, Lt), dimp=mk(B, P), dgw_part=mk(B, P), dqg=mk(B, P, Lt), dql=mk(B, P, Lt), dcg=mk(B, P, Lt),
-                                dcl=mk(B, P, Lt), delta_g=mk(B, P), delta_l=mk(B, P), dprm=mk(B, P, Lt), dcls=mk(B, Lt),
-                                gate_partials=mk(B, ng), dzx=mk(M, Lt), dzl=[mk(BN, Lt), mk(BN, Lt)],
-                                dctx=mk(BN, Lt), dqkv=mk(BN, 3 * Lt), wdelta=mk(BN), dlat=mk(BN, Lt), Q=mk(Lt, C), S=mk(Lt))
-                ws["scratch"] = mk(max(ops.outer_scratch_elems(Lt, C), 128 * C, 64 * 3 * Lt * Lt, 64 * ng))
-                ws["rscratch"] = mk(32 * (ng + 2 * Lt * Lt + 3 * Lt + 3 * Lt * Lt + 64))
-                ws["scratch_l"] = mk(max(ops.outer_scratch_elems(Lt, C), 128 * C))      # the MWSA chain runs on its own stream
-                ws["rscratch_l"] = mk(32 * (3 * Lt * Lt + Lt + 64))
-                if self._pgrad:                                                          # one scratch + ticket block per stream (gvk_param_grads)
-                    nct = (C + 63) // 64
-                    ws["pscratch"] = mk(ops.param_grads_scratch_elems(Lt, [nct, nct], [ng, Lt * Lt, Lt, Lt * Lt, Lt, Lt]))
-                    ws["pscratch_l"] = mk(ops.param_grads_scratch_elems(Lt, [nct, nct, (3 * Lt + 63) // 64], []))   # third job: the qkv weight, 3 Lat columns (two tiles from Lat = 24)
-                    ws["ptick"] = torch.zeros(ops.PGRAD_TICKETS, dtype=torch.int32, device=device)
-                    ws["ptick_l"] = torch.zeros(ops.PGRAD_TICKETS, dtype=torch.int32, device=device)
-            elif self.kind == "dvpt":
-                Lt, P = self.Lat, self.P
-                mk = lambda *s_: torch.zeros(s_, device=device)
-                ws["dvb"] = dict(dcomb=mk(M, Lt), dz=mk(M, Lt), delta=mk(B, P))
-                ws["scratch"] = mk(max(ops.outer_scratch_elems(Lt, C), 128 * C))
-                ws["rscratch"] = mk(32 * (Lt + 64))
-            elif self.kind == "evp":
-                pass                                        # scratch / rscratch sized with the EVP buffers above
-            else:
-                if self.kind == "ssf":
-                    ws["ssf_scratch"] = torch.zeros(64 * 2 * max(self.mlp, 3 * C), device=device)
-                    ws["ssf_tmp"] = torch.zeros(2 * C, device=device)
-                    ws["ssf_stat"] = [torch.zeros(M, device=device), torch.zeros(M, device=device)]
-                lat = {"adaptformer": 64, "melo": getattr(self, "r", 4)}.get(self.kind, 1)
-                ws["scratch"] = torch.zeros(max(128 * C, ops.outer_scratch_elems(lat, C)), device=device)
+            self.method.backward_buffers(self, ws, B, device)
         self._ws = self._wss[key] = ws       # one workspace (and one set of captured graphs) per (batch, mode)
         return ws
 
@@ -586,8 +430,6 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         # train() override (linear / bitfit / fft, melo) and for VPT's prompt_dropout.  bf16 path only.
         sv["bdrop"], sv["edrop"], sv["pdrop"] = (float(drop.get(k, 0.0)) for k in ("dropout", "emb_dropout", "prompt_dropout"))
         sv["feat"] = tuple(feat) if (feat and not train) else ()     # feature_forward: the layers whose entering stream is summarised
-        if (sv["bdrop"] > 0 or sv["edrop"] > 0 or sv["pdrop"] > 0) and self.kind not in ("vit", "melo", "vpt", "adaptformer", "gaviko", "dvpt", "evp", "ssf"):
-            raise L.GavikoHipError(f"backbone dropout > 0 in training mode: unknown kind {self.kind!r}")
         self.refresh_weights(need_dgrad=train)
         ws = self.workspace(B, img.device, train, keep_attn=keep_attn and not train, tag=ws_tag, feat=sv["feat"] or None)
         if img.data_ptr() != ws["img"].data_ptr():           # a caller that fills input_buffer() itself skips the copy-in launch
@@ -596,8 +438,9 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         # (`fft` / `bitfit` of the plain ViT; AdaptFormer(freeze_vit=False): adapters keep their own kernels, everything else is backbone)
         # Gaviko(freeze_vit=False): prompts / MWSA / GPA keep their own kernels, everything else is backbone)
         bb = frozenset()
-        if train and self.kind in _BB_KINDS:
-            bb = frozenset(n for n in self.trainable_names() if not n.startswith(self.names.head()) and not self._own_grad_kernels(n))
+        if train and self.method.backbone_trainable:
+            head, own = self.names.head(), self.method.owns
+            bb = frozenset(n for n in self.trainable_names() if not n.startswith(head) and not own(n))
         sv["bb"] = bb
         sv["wgrad"] = any(self.p[n].dim() >= 2 and n.endswith("weight") for n in bb)
         if bb:
@@ -776,16 +619,10 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         self._mark("f:head")
 
     def _final_stream(self, ws, train):
-        if self.kind == "vpt" and self.deep:
-            return ws["Go"]
-        return ws["G"][self.depth] if train else ws["G"][self.depth & 1]
+        return self.method.final_stream(self, ws, train)
 
     def _pool_rows(self):
-        if self.kind == "dvpt":                       # dvpt.py:80-83,205: 'cls' reads row 0 -- the FIRST PROMPT; 'mean' = prompts + cls
-            return (0, self.P + 1) if self.pool == "mean" else (0, 1)
-        if self.kind == "gaviko":
-            return 0, self.P + 1                      # gaviko.py:316 prompts + CLS
-        return (0, self.Ts[-1]) if self.pool == "mean" else (0, 1)
+        return self.method.pool_rows(self)
 
     def _masked_grad(self, ws, dy, p, seed, need32, M):
         """ws['dG16'] (the dgrad GEMM operand) = dy * mask; also returns the fp32 masked gradient when bias / weight gradients need it."""
@@ -878,7 +715,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         from .distributed import flat_order
         key = (tuple(self.trainable_names()), self.bucket_layers)
         if self._flat_names is None or self._flat_names[0] != key:
-            self._flat_names = (key, flat_order(key[0], self.cfg.get("share_factor", 1) if self.kind == "gaviko" else 1, self.bucket_layers))
+            self._flat_names = (key, flat_order(key[0], self.method.share_factor(self.cfg), self.bucket_layers))
         return self._flat_names[1]
 
     def set_bucket_layers(self, k: int) -> None:
@@ -893,7 +730,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
 
     def set_prune(self, on: bool) -> None:
         """Dead-row pruning on / off (see prune_dead_rows in __init__).  Recorded plans hold the launch lists, so they are dropped."""
-        on = bool(on) and self.kind == "gaviko" and not self.fp32
+        on = bool(on) and self.method.supports_prune and not self.fp32
         if on != self.prune_dead_rows:
             self.prune_dead_rows = on
             self._graphs.clear()
@@ -1250,29 +1087,13 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                           dx16=None if bot else ws["dG16"], rows=(B, self.P, T) if bot else None, proj=proj)
 
     def _grad_supported(self, name: str) -> bool:
-        # head: always; backbone tensors: the classes of _BB_KINDS (plain ViT `linear` / `bitfit` / `fft`, AdaptFormer and Gaviko with
-        # freeze_vit=False); everything else: the method's own tensors
-        return name.startswith(self.names.head()) or self.kind in _BB_KINDS or self._own_grad_kernels(name)
+        # head: always; backbone tensors: the classes whose backbone can train (plain ViT `linear` / `bitfit` / `fft`, AdaptFormer and Gaviko
+        # with freeze_vit=False, ...: every kind but MeLO); everything else: the method's own tensors
+        return name.startswith(self.names.head()) or self.method.backbone_trainable or self._own_grad_kernels(name)
 
     def _own_grad_kernels(self, name: str) -> bool:
         """The method's OWN trainable tensors (prompts, adapters, LoRA factors, ...): gradients from the method-specific kernels."""
-        if self.kind == "vit":
-            return False
-        if self.kind == "gaviko":
-            return ("local_attns" in name or "prompt_projs" in name or name in ("prompt_embeddings", "prompt_positional_embedding"))
-        if self.kind == "vpt":
-            return name in ("prompt_proj.weight", "prompt_proj.bias", "deep_prompt_embeddings", "prompt_embeddings")
-        if self.kind == "adaptformer":
-            return "adapter" in name
-        if self.kind == "melo":
-            return ".linear_a_" in name or ".linear_b_" in name
-        if self.kind == "ssf":
-            return "ssf_scale_" in name or "ssf_shift_" in name
-        if self.kind == "dvpt":
-            return "prompt" in name
-        if self.kind == "evp":
-            return "prompt_generator" in name
-        return False
+        return self.method.owns(name)
 
     def _needs_backbone_backward(self) -> bool:
         return any(not n.startswith(self.names.head()) for n in self.trainable_names())

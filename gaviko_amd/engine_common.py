@@ -1,6 +1,7 @@
 """Constants, switches and small helpers shared by the launch-plan engine (engine.py) and its halves (engine_gaviko.py: the MWSA / GPA
 side paths; engine_peft.py: AdaptFormer, LoRA, unfrozen-backbone gradients, EVP, DVPT, SSF; engine_analysis.py: the entry points of
-gaviko_amd.explain / uncertainty / features)."""
+gaviko_amd.explain / uncertainty / features).  The per-kind static facts -- geometry, flags, buffers, name patterns -- live in
+engine_methods.py; `Names` here turns its patterns into state_dict names."""
 from __future__ import annotations
 
 import os
@@ -8,6 +9,7 @@ import os
 import torch
 
 from . import lib as L
+from .engine_methods import METHOD_SPECS
 
 # How a step is issued after the GRAPH_WARMUP eager passes (env GAVIKO_HIP_GRAPHS):
 #   "plan"  (default, also "1") -- the library's launch plan: recorded once, replayed from one C loop on the real streams
@@ -77,33 +79,28 @@ def evp_highpass_operator(D: int, H: int, W: int, rate: float):
 
 
 class Names:
-    """Maps logical backbone tensors to the state_dict names of each reference class."""
+    """Maps logical backbone tensors to the state_dict names of each reference class, from the name patterns of the
+    kind's spec (engine_methods.py)."""
 
     def __init__(self, kind: str, lora_layers=None):
-        self.kind = kind
+        spec = METHOD_SPECS[kind]
+        self.kind, self.root, self.wraps_qkv = kind, spec.root, spec.wraps_qkv
         self.lora_layers = None if lora_layers is None else frozenset(lora_layers)     # MeLO: layers whose to_qkv is wrapped (melo.py:53-68)
-        self.root = {"vpt": "vision_transformer.", "melo": "lora_vit."}.get(kind, "")
+        self._attn, self._mlp = self.root + spec.attn_name, self.root + spec.mlp_name  # "%d" = the layer
+        self._conv, self._head = self.root + spec.conv_name, self.root + spec.head_name
 
     def attn(self, i):
-        if self.kind == "gaviko":
-            return f"transformer.attns.{i}"
-        if self.kind == "dvpt":
-            return f"transformer.layers.{i}.0.attn"
-        return f"{self.root}transformer.layers.{i}.0"
+        return self._attn % i
 
     def mlp(self, i):
-        if self.kind == "gaviko":
-            return f"transformer.mlps.{i}"
-        if self.kind == "dvpt":
-            return f"transformer.layers.{i}.0.mlp"
-        return f"{self.root}transformer.layers.{i}." + ("2" if self.kind == "adaptformer" else "1")
+        return self._mlp % i
 
     def conv(self):
-        return "conv_proj.proj" if self.kind == "evp" else f"{self.root}conv_proj.0"      # evp.py:292: a PatchEmbed, not a Sequential
+        return self._conv
 
     def qkv_weight(self, i):
-        wrapped = self.kind == "melo" and (self.lora_layers is None or i in self.lora_layers)
+        wrapped = self.wraps_qkv and (self.lora_layers is None or i in self.lora_layers)
         return self.attn(i) + (".to_qkv.qkv.weight" if wrapped else ".to_qkv.weight")
 
     def head(self):
-        return "mlp_head.head" if self.kind == "gaviko" else f"{self.root}mlp_head"
+        return self._head
