@@ -53,55 +53,61 @@ class GemmDesc(C.Structure):
     ]
 
 
-def _struct(name, ptrs, ints, floats=(), u64=(), i64=()):
-    """C struct with the header's field order: pointers, int32s, floats, uint64s, int64s."""
+STRUCTS = {"gvk_gemm_desc": GemmDesc}             # the header's struct name -> ctypes class (tests/test_abi.py compares the field order)
+
+
+def _struct(cname, ptrs, ints, floats=(), u64=(), i64=()):
+    """ctypes class of the header's struct `cname`, in its field order (pointers, int32s, floats, uint64s, int64s), registered in STRUCTS."""
     fields = [(f, C.c_void_p) for f in ptrs] + [(f, C.c_int32) for f in ints] + [(f, C.c_float) for f in floats] + \
              [(f, C.c_uint64) for f in u64] + [(f, C.c_int64) for f in i64]
-    return type(name, (C.Structure,), {"_fields_": fields})
+    STRUCTS[cname] = type(cname, (C.Structure,), {"_fields_": fields})
+    return STRUCTS[cname]
 
 
-SkinnyDownDesc = _struct("SkinnyDownDesc",
+SkinnyDownDesc = _struct("gvk_skinny_down_desc",
                          ["x", "w", "bias", "ln_gamma", "ln_beta", "mean", "rstd", "z", "y", "w2", "y2", "seed_ptr"],
                          ["M", "C", "L", "L2", "act", "w_layout", "act_in"], ["eps", "drop_p"], ["seed"])
-SkinnyUpDesc = _struct("SkinnyUpDesc", ["lat", "w", "bias", "res", "out", "lat_override", "seed_ptr", "ln_x", "ln_mean", "ln_rstd", "ln_gamma", "out_bf16",
-                                        "alpha_ptr", "gg_x", "w2", "bias2", "z2", "y2", "lat_b", "w_b",
-                                        "nx_w", "nx_bias", "nx_ln_gamma", "nx_ln_beta", "nx_mean", "nx_rstd", "nx_lat", "nx_w2", "nx_y2"],
+SkinnyUpDesc = _struct("gvk_skinny_up_desc",
+                       ["lat", "w", "bias", "res", "out", "lat_override", "seed_ptr", "ln_x", "ln_mean", "ln_rstd", "ln_gamma", "out_bf16",
+                        "alpha_ptr", "gg_x", "w2", "bias2", "z2", "y2", "lat_b", "w_b",
+                        "nx_w", "nx_bias", "nx_ln_gamma", "nx_ln_beta", "nx_mean", "nx_rstd", "nx_lat", "nx_w2", "nx_y2"],
                        ["M", "C", "L", "T", "P", "w_layout", "accumulate", "L2", "act2", "w2_layout", "nx_L2"], ["drop_p", "drop2_p", "nx_eps"],
                        ["seed", "seed2"])
-OuterDesc = _struct("OuterDesc", ["narrow", "wide", "lat_override", "mean", "rstd", "ln_gamma", "ln_beta", "scratch", "out", "colsum", "seed_ptr",
-                                  "narrow2", "wide2"],
+OuterDesc = _struct("gvk_outer_desc",
+                    ["narrow", "wide", "lat_override", "mean", "rstd", "ln_gamma", "ln_beta", "scratch", "out", "colsum", "seed_ptr", "narrow2", "wide2"],
                     ["M", "C", "L", "T", "P", "transposed", "accumulate", "wide_act", "M2"], ["drop_p"], ["seed"])
-WindowAttnDesc = _struct("WindowAttnDesc", ["qkv", "ctx", "lse", "dctx", "delta", "dqkv", "seed_ptr"],
+WindowAttnDesc = _struct("gvk_window_attn_desc", ["qkv", "ctx", "lse", "dctx", "delta", "dqkv", "seed_ptr"],
                          ["B", "D", "H", "W", "kd", "kh", "kw", "L"], ["scale", "drop_p"], ["seed"])
-GpaDesc = _struct("GpaDesc",
+GpaDesc = _struct("gvk_gpa_desc",
                   ["xl", "ll", "ca0_g", "ca0_b", "ca1_w", "ca1_b", "ca3_w", "ca3_b", "gl0_g", "gl0_b", "gl1_w", "gl1_b",
                    "wgq", "bgq", "wlq", "blq", "imp", "gw", "enh", "prm", "qg", "ql", "cg", "cl", "lse_g", "lse_l",
                    "dcomb", "zx", "zl", "dimp", "dgw_part", "dqg", "dql", "dcg", "dcl", "delta_g", "delta_l", "dprm",
                    "dcls", "gate_partials", "dzx", "dzl", "enh16"],
                   ["B", "T", "N", "P", "L", "ld16", "col16"], ["scale"])
-SsfColgradDesc = _struct("SsfColgradDesc", ["dy", "y0", "y1", "pos", "s", "t", "ds", "dt", "scratch"],
+SsfColgradDesc = _struct("gvk_ssf_colgrad_desc", ["dy", "y0", "y1", "pos", "s", "t", "ds", "dt", "scratch"],
                          ["M", "N", "ld_dy", "ld_y", "dy_f32", "y0_f32", "rows_in", "rows_out", "row_off", "y0_cols"], ["y0_mul", "y_mul"])
-DvptDesc = _struct("DvptDesc", ["z", "enh", "lse", "dcomb", "gate", "bu", "colsum_dy", "delta", "dz", "dgate"], ["B", "T", "P", "L", "C"], ["scale"])
-AdamDesc = _struct("AdamDesc", ["ptr_tab", "blk_tab", "grad", "m", "v", "norm_sq"], ["nblocks"],
+DvptDesc = _struct("gvk_dvpt_desc", ["z", "enh", "lse", "dcomb", "gate", "bu", "colsum_dy", "delta", "dz", "dgate"], ["B", "T", "P", "L", "C"], ["scale"])
+AdamDesc = _struct("gvk_adam_desc", ["ptr_tab", "blk_tab", "grad", "m", "v", "norm_sq"], ["nblocks"],
                    ["lr", "beta1", "beta2", "eps", "bias_c1", "bias_c2", "max_norm"])
-LossDesc = _struct("LossDesc", ["logits", "target", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"], ["gamma", "eps"], i64=["ignore_index"])
-LossMixedDesc = _struct("LossMixedDesc", ["logits", "target_a", "target_b", "lam", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"],
+LossDesc = _struct("gvk_loss_desc", ["logits", "target", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"], ["gamma", "eps"], i64=["ignore_index"])
+LossMixedDesc = _struct("gvk_loss_mixed_desc", ["logits", "target_a", "target_b", "lam", "weights", "loss", "dlogits", "meter"], ["B", "K", "kind", "reduction"],
                         ["gamma", "eps", "smoothing"], i64=["ignore_index"])
-DropoutDesc = _struct("DropoutDesc", ["x", "out32", "out16", "seed_ptr"], ["M", "N", "ld", "rows_in", "rows_out", "row_off"], ["drop_p"], ["seed"])
-RowProjDesc = _struct("RowProjDesc", ["w", "bias", "y", "z", "y_split"], ["L", "w_layout", "act", "ld_split", "col_split"])
-LnBwdDesc = _struct("LnBwdDesc", ["dy", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
+DropoutDesc = _struct("gvk_dropout_desc", ["x", "out32", "out16", "seed_ptr"], ["M", "N", "ld", "rows_in", "rows_out", "row_off"], ["drop_p"], ["seed"])
+RowProjDesc = _struct("gvk_rowproj_desc", ["w", "bias", "y", "z", "y_split"], ["L", "w_layout", "act", "ld_split", "col_split"])
+LnBwdDesc = _struct("gvk_ln_bwd_desc", ["dy", "x", "mean", "rstd", "gamma", "dres", "dx", "dx_bf16", "proj"],
                     ["M", "C", "groups", "rows_per_group", "group_stride", "dy_bf16"])
-AttentionDesc = _struct("AttentionDesc", ["qkv", "out", "lse", "dout", "delta", "dqkv", "seed_ptr", "ws"],
+AttentionDesc = _struct("gvk_attention_desc", ["qkv", "out", "lse", "dout", "delta", "dqkv", "seed_ptr", "ws"],
                         ["B", "T", "H", "ld_qkv", "ld_out", "f32", "need_rows"], ["scale", "drop_p"], ["seed", "ws_bytes"])
-ReduceJob = _struct("ReduceJob", ["a", "b", "out", "a2"], ["M", "J", "L", "accumulate", "M2"])
-PgradOuter = _struct("PgradOuter", ["narrow", "wide", "narrow2", "wide2", "lat_override", "mean", "rstd", "out", "colsum",
-                                    "aff_w", "aff_gamma", "aff_beta", "aff_dgamma", "aff_dbeta", "aff_dbias"],
+ReduceJob = _struct("gvk_reduce_job", ["a", "b", "out", "a2"], ["M", "J", "L", "accumulate", "M2"])
+PgradOuter = _struct("gvk_pgrad_outer",
+                     ["narrow", "wide", "narrow2", "wide2", "lat_override", "mean", "rstd", "out", "colsum",
+                      "aff_w", "aff_gamma", "aff_beta", "aff_dgamma", "aff_dbeta", "aff_dbias"],
                      ["M", "M2", "T", "P", "transposed", "accumulate", "C"], ["drop_p"], ["seed"])
-WindowColsumDesc = _struct("WindowColsumDesc", ["qkv", "lse", "w", "out"], ["B", "D", "H", "W", "kd", "kh", "kw", "L"], ["scale"])
-GpaMapsDesc = _struct("GpaMapsDesc", ["xl", "ll", "qg", "ql", "lse_g", "lse_l", "imp", "gw", "pg", "pl", "fused"], ["B", "T", "N", "P", "L"])
-FeatureTopkDesc = _struct("FeatureTopkDesc", ["q", "g", "exclude", "idx", "score", "scratch"], ["Nq", "Ng", "C", "k", "metric", "nslabs"],
+WindowColsumDesc = _struct("gvk_window_colsum_desc", ["qkv", "lse", "w", "out"], ["B", "D", "H", "W", "kd", "kh", "kw", "L"], ["scale"])
+GpaMapsDesc = _struct("gvk_gpa_maps_desc", ["xl", "ll", "qg", "ql", "lse_g", "lse_l", "imp", "gw", "pg", "pl", "fused"], ["B", "T", "N", "P", "L"])
+FeatureTopkDesc = _struct("gvk_feature_topk_desc", ["q", "g", "exclude", "idx", "score", "scratch"], ["Nq", "Ng", "C", "k", "metric", "nslabs"],
                           i64=["scratch_words"])
-HeadDesc = _struct("HeadDesc", ["g", "ln_gamma", "ln_beta", "wh", "bh", "logits", "pooled", "dlogits", "dg", "dwh", "dbh"],
+HeadDesc = _struct("gvk_head_desc", ["g", "ln_gamma", "ln_beta", "wh", "bh", "logits", "pooled", "dlogits", "dg", "dwh", "dbh"],
                    ["B", "T", "C", "K", "r0", "R", "accumulate"])
 
 (EPI_STORE_BF16, EPI_BIAS_RES_F32, EPI_BIAS_GELU_BF16, EPI_PATCH_F32, EPI_GELU_BWD_BF16, EPI_STORE_F32, EPI_BIAS_RES_F32_BF16,
@@ -233,9 +239,6 @@ NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, [
              "gvk_plan_event_record_fenced": (C.c_int, [_P]), "gvk_plan_event_stream_wait": (C.c_int, [C.c_int, C.c_int, _P]),
              "gvk_plan_set_timing": (C.c_int, [C.c_int]),
              "gvk_plan_event_elapsed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)])}
-STRUCTS = {"gvk_gemm_desc": GemmDesc, "gvk_skinny_down_desc": SkinnyDownDesc, "gvk_skinny_up_desc": SkinnyUpDesc,
-           "gvk_outer_desc": OuterDesc, "gvk_window_attn_desc": WindowAttnDesc, "gvk_gpa_desc": GpaDesc, "gvk_window_colsum_desc": WindowColsumDesc, "gvk_gpa_maps_desc": GpaMapsDesc, "gvk_head_desc": HeadDesc, "gvk_reduce_job": ReduceJob, "gvk_pgrad_outer": PgradOuter, "gvk_rowproj_desc": RowProjDesc, "gvk_attention_desc": AttentionDesc, "gvk_adam_desc": AdamDesc, "gvk_loss_desc": LossDesc, "gvk_loss_mixed_desc": LossMixedDesc, "gvk_dropout_desc": DropoutDesc, "gvk_ssf_colgrad_desc": SsfColgradDesc, "gvk_dvpt_desc": DvptDesc,
-           "gvk_feature_topk_desc": FeatureTopkDesc}
 
 # diag library only (include/gaviko_hip_diag.h): bound when GAVIKO_HIP_DIAG=1 selects libgaviko_hip_diag.so
 DIAG_SIGNATURES = {}
@@ -258,19 +261,13 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m gaviko_amd.build` (hipcc, gfx950). "
             "gaviko_amd has no CPU or eager fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in NO_STREAM.items():
+    protos = {**NO_STREAM, **{name: (C.c_int, args) for name, args in SIGNATURES.items()}}
+    if DIAG:
+        protos.update(DIAG_NO_STREAM)
+        protos.update((name, (C.c_int, args)) for name, args in DIAG_SIGNATURES.items())
+    for name, (res, args) in protos.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = C.c_int, args
-    if DIAG:
-        for name, (res, args) in DIAG_NO_STREAM.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        for name, args in DIAG_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = C.c_int, args
     if lib.gvk_abi_version() != ABI_VERSION:
         raise GavikoHipError(f"{LIB_PATH} has ABI version {lib.gvk_abi_version()}, these bindings describe {ABI_VERSION}: rebuild with "
                              "`python -m gaviko_amd.build`")
@@ -305,3 +302,22 @@ def stream_ptr() -> int:
 
 def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
+
+
+class _Launch:
+    """launch.gvk_x(a, b, ..., M, N) calls the stream-taking entry point gvk_x of SIGNATURES: every torch.Tensor argument goes as its device
+    pointer, everything else (None, ints, floats, ctypes.byref(...) and ctypes arrays) as it is, the current stream is appended, and a
+    non-zero return code raises GavikoHipError naming gvk_x.  The symbol is looked up on the loaded library at every call."""
+
+    def __getattr__(self, name):                  # first use of a name only: the callable then lives in the instance
+        if name not in SIGNATURES and not (DIAG and name in DIAG_SIGNATURES):
+            raise AttributeError(f"{name} is not a stream-taking entry point of gaviko_amd.lib.SIGNATURES")
+
+        def call(*args):
+            fn = getattr(load(), name)
+            check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], stream_ptr()), name)
+        setattr(self, name, call)
+        return call
+
+
+launch = _Launch()

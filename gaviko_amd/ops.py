@@ -76,10 +76,7 @@ def gemm_nt(a, w, M, out0, *, epilogue, out1=None, bias=None, res=None, aux=None
     _chk(ln_c1, torch.float32, "gemm ln_c1", N)
     _chk(stat_part, torch.float32, "gemm stat_part", (N // 64) * M * 2)
     _chk(stat_pivot, torch.float32, "gemm stat_pivot", M)
-    if adt == torch.float32:
-        L.check(L.load().gvk_gemm_nt_f32(C.byref(d), L.stream_ptr()), "gvk_gemm_nt_f32")
-    else:
-        L.check(L.load().gvk_gemm_nt_bf16(C.byref(d), L.stream_ptr()), "gvk_gemm_nt_bf16")
+    (L.launch.gvk_gemm_nt_f32 if adt == torch.float32 else L.launch.gvk_gemm_nt_bf16)(C.byref(d))
 
 
 def cast_bf16(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
@@ -87,7 +84,7 @@ def cast_bf16(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     if out is None:
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     _chk(out, torch.bfloat16, "cast out", x.numel())
-    L.check(L.load().gvk_cast_f32_bf16(L.ptr(x), L.ptr(out), x.numel(), L.stream_ptr()), "gvk_cast_f32_bf16")
+    L.launch.gvk_cast_f32_bf16(x, out, x.numel())
     return out
 
 
@@ -96,8 +93,7 @@ def pack_split_bf16(a, dst, col0, rows, b=None, weight_side=False):
     _chk(a, torch.float32, "pack a", rows * a.shape[-1])
     _chk(dst, torch.bfloat16, "pack dst", rows * dst.shape[-1])
     _chk(b, torch.float32, "pack b", rows)
-    L.check(L.load().gvk_pack_split_bf16(L.ptr(a), a.shape[-1], L.ptr(b), L.ptr(dst), dst.shape[-1], col0, rows, int(weight_side), L.stream_ptr()),
-            "gvk_pack_split_bf16")
+    L.launch.gvk_pack_split_bf16(a, a.shape[-1], b, dst, dst.shape[-1], col0, rows, int(weight_side))
 
 
 def layernorm_fwd_fix(x, gamma, beta, M, C_, *, y16, mean, rstd, enh, lat, wup, T, P, L_, eps=1e-5):
@@ -111,8 +107,7 @@ def layernorm_fwd_fix(x, gamma, beta, M, C_, *, y16, mean, rstd, enh, lat, wup, 
     _chk(enh, torch.float32, "ln_fix enh", (M // T) * P * L_)
     _chk(lat, torch.float32, "ln_fix lat", M * L_)
     _chk(wup, torch.float32, "ln_fix wup", C_ * L_)
-    L.check(L.load().gvk_layernorm_fwd_fix(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y16), L.ptr(mean), L.ptr(rstd), M, C_, eps, L.ptr(enh),
-                                           L.ptr(lat), L.ptr(wup), T, P, L_, L.stream_ptr()), "gvk_layernorm_fwd_fix")
+    L.launch.gvk_layernorm_fwd_fix(x, gamma, beta, y16, mean, rstd, M, C_, eps, enh, lat, wup, T, P, L_)
 
 
 def prompt_up_fix(enh, lat, w, out, B, T, P, C_, L_):
@@ -121,7 +116,7 @@ def prompt_up_fix(enh, lat, w, out, B, T, P, C_, L_):
     _chk(lat, torch.float32, "prompt_up_fix lat", B * T * L_)
     _chk(w, torch.float32, "prompt_up_fix w", C_ * L_)
     _chk(out, torch.float32, "prompt_up_fix out", B * T * C_)
-    L.check(L.load().gvk_prompt_up_fix(L.ptr(enh), L.ptr(lat), L.ptr(w), L.ptr(out), B, T, P, C_, L_, L.stream_ptr()), "gvk_prompt_up_fix")
+    L.launch.gvk_prompt_up_fix(enh, lat, w, out, B, T, P, C_, L_)
 
 
 def prompt_up_fix_stats(enh, lat, w, out, out16, part, mean, rstd, B, T, P, C_, L_, eps=1e-5, pivot=None):
@@ -137,8 +132,7 @@ def prompt_up_fix_stats(enh, lat, w, out, out16, part, mean, rstd, B, T, P, C_, 
     _chk(mean, torch.float32, "prompt_up_fix mean", B * T)
     _chk(rstd, torch.float32, "prompt_up_fix rstd", B * T)
     _chk(pivot, torch.float32, "prompt_up_fix pivot", B * T)
-    L.check(L.load().gvk_prompt_up_fix_stats(L.ptr(enh), L.ptr(lat), L.ptr(w), L.ptr(out), L.ptr(out16), L.ptr(part), nparts, L.ptr(pivot), L.ptr(mean), L.ptr(rstd),
-                                             B, T, P, C_, L_, eps, L.stream_ptr()), "gvk_prompt_up_fix_stats")
+    L.launch.gvk_prompt_up_fix_stats(enh, lat, w, out, out16, part, nparts, pivot, mean, rstd, B, T, P, C_, L_, eps)
 
 
 def copy_(dst: torch.Tensor, src: torch.Tensor) -> None:
@@ -146,7 +140,7 @@ def copy_(dst: torch.Tensor, src: torch.Tensor) -> None:
     (gvk_copy_async), recorded into a launch plan like any other launch."""
     if dst.dtype != src.dtype or not dst.is_contiguous() or not src.is_contiguous() or dst.numel() < src.numel():
         raise L.GavikoHipError("copy_: need contiguous tensors of one dtype with dst at least as large as src")
-    L.check(L.load().gvk_copy_async(L.ptr(dst), L.ptr(src), src.numel() * src.element_size(), L.stream_ptr()), "gvk_copy_async")
+    L.launch.gvk_copy_async(dst, src, src.numel() * src.element_size())
 
 
 def to_operand(x: torch.Tensor, out: torch.Tensor = None, dtype=torch.bfloat16) -> torch.Tensor:
@@ -168,7 +162,7 @@ def transpose_operand(x: torch.Tensor, out: torch.Tensor = None, dtype=torch.bfl
     if out is None:
         out = torch.empty((cols, rows), dtype=torch.float32, device=x.device)
     _chk(out, torch.float32, "transpose out", rows * cols)
-    L.check(L.load().gvk_transpose_f32(L.ptr(x), L.ptr(out), rows, cols, L.stream_ptr()), "gvk_transpose_f32")
+    L.launch.gvk_transpose_f32(x, out, rows, cols)
     return out
 
 
@@ -178,8 +172,7 @@ def transpose_any(x: torch.Tensor, out: torch.Tensor, rows: int, cols: int) -> N
         raise L.GavikoHipError("transpose_any: x and out must both be bf16 or both fp32")
     _chk(x, x.dtype, "transpose_any x", rows * cols)
     _chk(out, x.dtype, "transpose_any out", rows * cols)
-    fn = L.load().gvk_transpose_f32 if x.dtype == torch.float32 else L.load().gvk_transpose_bf16
-    L.check(fn(L.ptr(x), L.ptr(out), rows, cols, L.stream_ptr()), "gvk_transpose")
+    (L.launch.gvk_transpose_f32 if x.dtype == torch.float32 else L.launch.gvk_transpose_bf16)(x, out, rows, cols)
 
 
 def colsum_any(x, out, ones, zeros, junk, scratch, M, N, *, ld=None, rows_in=0, rows_out=0, row_off=0):
@@ -192,18 +185,18 @@ def memset_zero(t: torch.Tensor) -> None:
     The tensor must start 16-byte aligned and span a multiple of 4 bytes."""
     if not t.is_contiguous():
         raise L.GavikoHipError("memset_zero: tensor must be contiguous")
-    L.check(L.load().gvk_memset_async(L.ptr(t), 0, t.numel() * t.element_size(), L.stream_ptr()), "gvk_memset_async")
+    L.launch.gvk_memset_async(t, 0, t.numel() * t.element_size())
 
 
 def seed_advance(seed: torch.Tensor, inc: int) -> None:
     if seed.dtype != torch.int64 or seed.numel() != 1:
         raise L.GavikoHipError("seed_advance: the dropout epoch is one int64 device word")
-    L.check(L.load().gvk_seed_advance(L.ptr(seed), inc, L.stream_ptr()), "gvk_seed_advance")
+    L.launch.gvk_seed_advance(seed, inc)
 
 
 def scale_(t: torch.Tensor, alpha: float) -> None:
     _chk(t, torch.float32, "scale_")
-    L.check(L.load().gvk_scale_f32(L.ptr(t), alpha, t.numel(), L.stream_ptr()), "gvk_scale_f32")
+    L.launch.gvk_scale_f32(t, alpha, t.numel())
 
 
 def transpose_cast_bf16(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
@@ -213,7 +206,7 @@ def transpose_cast_bf16(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
     if out is None:
         out = torch.empty((cols, rows), dtype=torch.bfloat16, device=x.device)
     _chk(out, torch.bfloat16, "transpose_cast out", rows * cols)
-    L.check(L.load().gvk_transpose_cast_f32_bf16(L.ptr(x), L.ptr(out), rows, cols, L.stream_ptr()), "gvk_transpose_cast_f32_bf16")
+    L.launch.gvk_transpose_cast_f32_bf16(x, out, rows, cols)
     return out
 
 
@@ -226,10 +219,10 @@ def patchify(img: torch.Tensor, out: torch.Tensor, patch) -> None:
     n = (D // pd) * (H // ph) * (W // pw)
     if out.dtype == torch.float32:
         _chk(out, torch.float32, "patchify out", B * n * pd * ph * pw)
-        L.check(L.load().gvk_patchify_f32(L.ptr(img), L.ptr(out), B, D, H, W, pd, ph, pw, L.stream_ptr()), "gvk_patchify_f32")
+        L.launch.gvk_patchify_f32(img, out, B, D, H, W, pd, ph, pw)
         return
     _chk(out, torch.bfloat16, "patchify out", B * n * pd * ph * pw)
-    L.check(L.load().gvk_patchify_bf16(L.ptr(img), L.ptr(out), B, D, H, W, pd, ph, pw, L.stream_ptr()), "gvk_patchify_bf16")
+    L.launch.gvk_patchify_bf16(img, out, B, D, H, W, pd, ph, pw)
 
 
 def unpatchify(dcols: torch.Tensor, out: torch.Tensor, patch, *, x=None, x0=None, alpha=1.0, beta=0.0, nsum=1) -> None:
@@ -248,8 +241,7 @@ def unpatchify(dcols: torch.Tensor, out: torch.Tensor, patch, *, x=None, x0=None
             _chk(t, torch.float32, "unpatchify " + n, out.numel())
             if tuple(t.shape) != tuple(out.shape):
                 raise L.GavikoHipError(f"unpatchify {n}: shape {tuple(t.shape)} != out {tuple(out.shape)}")
-    L.check(L.load().gvk_unpatchify_f32(L.ptr(dcols), L.ptr(out), L.ptr(x), L.ptr(x0), B, D, H, W, pd, ph, pw, int(nsum), float(alpha),
-                                        float(beta), L.stream_ptr()), "gvk_unpatchify_f32")
+    L.launch.gvk_unpatchify_f32(dcols, out, x, x0, B, D, H, W, pd, ph, pw, int(nsum), float(alpha), float(beta))
 
 
 def patch_reduce(vol: torch.Tensor, out: torch.Tensor, patch, absval=True) -> None:
@@ -260,8 +252,7 @@ def patch_reduce(vol: torch.Tensor, out: torch.Tensor, patch, absval=True) -> No
         raise L.GavikoHipError("patch_reduce: single-channel volumes only (channels=1)")
     pd, ph, pw = patch
     _chk(out, torch.float32, "patch_reduce out", B * (D // pd) * (H // ph) * (W // pw))
-    L.check(L.load().gvk_patch_reduce_f32(L.ptr(vol), L.ptr(out), B, D, H, W, pd, ph, pw, int(bool(absval)), L.stream_ptr()),
-            "gvk_patch_reduce_f32")
+    L.launch.gvk_patch_reduce_f32(vol, out, B, D, H, W, pd, ph, pw, int(bool(absval)))
 
 
 # ---- perturbation of the input volume at patch granularity (csrc/perturb.hip) ----
@@ -289,7 +280,7 @@ def patch_rank(rel: torch.Tensor, rank: torch.Tensor = None) -> torch.Tensor:
     _chk(rank, torch.int32, "patch_rank rank")
     if tuple(rank.shape) != (S, N):
         raise L.GavikoHipError(f"patch_rank rank: shape {tuple(rank.shape)} != rel {tuple(rel.shape)}")
-    L.check(L.load().gvk_patch_rank(L.ptr(rel), L.ptr(rank), S, N, L.stream_ptr()), "gvk_patch_rank")
+    L.launch.gvk_patch_rank(rel, rank, S, N)
     return rank
 
 
@@ -302,8 +293,7 @@ def patch_mask_rank(rank: torch.Tensor, src: torch.Tensor, lo: torch.Tensor, hi:
     Bout, N = mask.shape
     for t, n in ((src, "src"), (lo, "lo"), (hi, "hi")):
         _tab(t, "patch_mask_rank " + n, Bout)
-    L.check(L.load().gvk_patch_mask_rank(L.ptr(rank), L.ptr(src), L.ptr(lo), L.ptr(hi), L.ptr(mask), Bout, rank.shape[0], N, L.stream_ptr()),
-            "gvk_patch_mask_rank")
+    L.launch.gvk_patch_mask_rank(rank, src, lo, hi, mask, Bout, rank.shape[0], N)
 
 
 def patch_mask_box(boxes: torch.Tensor, mask: torch.Tensor, grid) -> None:
@@ -314,7 +304,7 @@ def patch_mask_box(boxes: torch.Tensor, mask: torch.Tensor, grid) -> None:
     if mask.dim() != 2 or mask.shape[0] < 1 or mask.shape[1] != nd * nh * nw or min(nd, nh, nw) < 1:
         raise L.GavikoHipError(f"patch_mask_box: expected mask [Bout, {nd * nh * nw}] for the grid {(nd, nh, nw)}, got {tuple(mask.shape)}")
     _tab(boxes, "patch_mask_box boxes", mask.shape[0] * 6)
-    L.check(L.load().gvk_patch_mask_box(L.ptr(boxes), L.ptr(mask), mask.shape[0], nd, nh, nw, L.stream_ptr()), "gvk_patch_mask_box")
+    L.launch.gvk_patch_mask_box(boxes, mask, mask.shape[0], nd, nh, nw)
 
 
 def perturb_volume(x: torch.Tensor, mask: torch.Tensor, src: torch.Tensor, out: torch.Tensor, patch, *, fill_scalar=None, base=None) -> None:
@@ -354,8 +344,7 @@ def perturb_volume(x: torch.Tensor, mask: torch.Tensor, src: torch.Tensor, out: 
         raise L.GavikoHipError("perturb_volume: out must not overlap base")
     if Bout * D * H * W >= 1 << 31:
         raise L.GavikoHipError(f"perturb_volume: {Bout} x {D * H * W} voxels per launch exceed the kernel's 32-bit index range")
-    L.check(L.load().gvk_perturb_volume(L.ptr(x), L.ptr(mask), L.ptr(src), L.ptr(fill_scalar), L.ptr(base), nbase, L.ptr(out), Bout, S, D, H, W,
-                                        pd, ph, pw, L.stream_ptr()), "gvk_perturb_volume")
+    L.launch.gvk_perturb_volume(x, mask, src, fill_scalar, base, nbase, out, Bout, S, D, H, W, pd, ph, pw)
 
 
 def perturb_scores(logits: torch.Tensor, src: torch.Tensor, target: torch.Tensor, slot: torch.Tensor, prob: torch.Tensor, logit: torch.Tensor,
@@ -382,9 +371,7 @@ def perturb_scores(logits: torch.Tensor, src: torch.Tensor, target: torch.Tensor
     if (logit is not None and logit.numel() != nslots) or (rows is not None and rows.numel() != nslots * K):
         raise L.GavikoHipError(f"perturb_scores: {nslots} slots; logit needs as many and rows {nslots} x {K}")
     S = target.numel() if prob is not None else 0
-    L.check(L.load().gvk_perturb_scores(L.ptr(logits), L.ptr(src) if prob is not None else None, L.ptr(target) if prob is not None else None,
-                                        L.ptr(slot), L.ptr(prob), L.ptr(logit), L.ptr(rows), Bout, S, K, nslots, L.stream_ptr()),
-            "gvk_perturb_scores")
+    L.launch.gvk_perturb_scores(logits, src if prob is not None else None, target if prob is not None else None, slot, prob, logit, rows, Bout, S, K, nslots)
 
 
 def curve_auc(prob: torch.Tensor, ks: torch.Tensor, N: int, auc: torch.Tensor = None) -> torch.Tensor:
@@ -397,7 +384,7 @@ def curve_auc(prob: torch.Tensor, ks: torch.Tensor, N: int, auc: torch.Tensor = 
     if auc is None:
         auc = torch.empty(S, dtype=torch.float32, device=prob.device)
     _chk(auc, torch.float32, "curve_auc auc", S)
-    L.check(L.load().gvk_curve_auc(L.ptr(prob), L.ptr(ks), L.ptr(auc), S, P, int(N), L.stream_ptr()), "gvk_curve_auc")
+    L.launch.gvk_curve_auc(prob, ks, auc, S, P, int(N))
     return auc
 
 
@@ -411,8 +398,7 @@ def layernorm_fwd(x, gamma, beta, M, C_, *, y16=None, y32=None, mean=None, rstd=
     _chk(y32, torch.float32, "ln y32", M * C_)
     _chk(mean, torch.float32, "ln mean", M)
     _chk(rstd, torch.float32, "ln rstd", M)
-    L.check(L.load().gvk_layernorm_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y16), L.ptr(y32), L.ptr(mean), L.ptr(rstd),
-                                       M, C_, eps, L.stream_ptr()), "gvk_layernorm_fwd")
+    L.launch.gvk_layernorm_fwd(x, gamma, beta, y16, y32, mean, rstd, M, C_, eps)
 
 
 ROWPROJ_L = 20      # default latent width (configs/gaviko.yaml prompt_latent_dim)
@@ -451,8 +437,7 @@ def layernorm_fwd_proj(x, gamma, beta, M, C_, *, y16, mean=None, rstd=None, eps=
     _chk(mean, torch.float32, "ln mean", M)
     _chk(rstd, torch.float32, "ln rstd", M)
     d = _rowproj(M, C_, w, y, bias, z, L_, w_layout, act, y_split, col_split)
-    L.check(L.load().gvk_layernorm_fwd_proj(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y16), L.ptr(mean), L.ptr(rstd), M, C_, eps,
-                                            C.byref(d), L.stream_ptr()), "gvk_layernorm_fwd_proj")
+    L.launch.gvk_layernorm_fwd_proj(x, gamma, beta, y16, mean, rstd, M, C_, eps, C.byref(d))
 
 
 def layernorm_bwd_up(dy, x, mean, rstd, gamma, M, C_, *, dx, dres, dx16, lat, w, L_, w_layout):
@@ -465,8 +450,7 @@ def layernorm_bwd_up(dy, x, mean, rstd, gamma, M, C_, *, dx, dres, dx16, lat, w,
     _chk(gamma, torch.float32, "ln_bwd_up gamma", C_)
     _chk(lat, torch.float32, "ln_bwd_up lat", M * L_)
     _chk(w, torch.float32, "ln_bwd_up w", L_ * C_)
-    L.check(L.load().gvk_layernorm_bwd_up(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx), L.ptr(dx16),
-                                          L.ptr(lat), L.ptr(w), w_layout, M, C_, L_, L.stream_ptr()), "gvk_layernorm_bwd_up")
+    L.launch.gvk_layernorm_bwd_up(dy, x, mean, rstd, gamma, dres, dx, dx16, lat, w, w_layout, M, C_, L_)
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None, rows=None, proj=None):
@@ -494,7 +478,7 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, M, C_, *, dx, dres=None, dx16=None, 
         pj = _rowproj(M, C_, proj["w"], proj["y"], None, None, proj.get("L_", ROWPROJ_L), proj.get("w_layout", 1), 0)
     d = L.LnBwdDesc(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dres), L.ptr(dx), L.ptr(dx16),
                     C.cast(C.pointer(pj), C.c_void_p) if pj is not None else None, M, C_, int(g), int(rpg), int(gs), int(dy_bf16))
-    L.check(L.load().gvk_layernorm_bwd(C.byref(d), L.stream_ptr()), "gvk_layernorm_bwd")
+    L.launch.gvk_layernorm_bwd(C.byref(d))
 
 
 def layernorm_bwd_affine(dy, x, mean, rstd, dgamma, dbeta, scratch, M, C_, accumulate=False):
@@ -503,8 +487,7 @@ def layernorm_bwd_affine(dy, x, mean, rstd, dgamma, dbeta, scratch, M, C_, accum
     _chk(dgamma, torch.float32, "ln_affine dgamma", C_)
     _chk(dbeta, torch.float32, "ln_affine dbeta", C_)
     _chk(scratch, torch.float32, "ln_affine scratch", 128 * C_)
-    L.check(L.load().gvk_layernorm_bwd_affine(L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(dgamma), L.ptr(dbeta),
-                                              L.ptr(scratch), M, C_, int(accumulate), L.stream_ptr()), "gvk_layernorm_bwd_affine")
+    L.launch.gvk_layernorm_bwd_affine(dy, x, mean, rstd, dgamma, dbeta, scratch, M, C_, int(accumulate))
 
 
 LOG2E = 1.4426950408889634
@@ -514,7 +497,7 @@ def qkv_prescale(qkv, rows, H, scale):
     """In place: q block of a raw bf16 to_qkv output -> q * scale * log2(e), the form the bf16 attention kernels take (the engine gets it from the
     qkv projection's epilogue instead: gemm_nt(scale_cols=H*64, col_scale=scale*LOG2E))."""
     _chk(qkv, torch.bfloat16, "qkv_prescale qkv", rows * 3 * H * 64)
-    L.check(L.load().gvk_qkv_prescale_bf16(L.ptr(qkv), rows, H, qkv.shape[-1], scale, L.stream_ptr()), "gvk_qkv_prescale_bf16")
+    L.launch.gvk_qkv_prescale_bf16(qkv, rows, H, qkv.shape[-1], scale)
 
 
 def _prescaled_copy(qkv, rows, H, scale):
@@ -535,7 +518,7 @@ def attention_fwd(qkv, out, lse, B, T, H, scale, drop_p=0.0, seed=0, seed_ptr=No
         qkv = _prescaled_copy(qkv, B * T, H, scale)
     d = L.AttentionDesc(qkv=L.ptr(qkv), out=L.ptr(out), lse=L.ptr(lse), seed_ptr=L.ptr(seed_ptr) if drop else None, B=B, T=T, H=H,
                         ld_qkv=3 * inner, ld_out=inner, f32=int(f32), scale=scale, drop_p=float(drop_p), seed=int(seed) if drop else 0)
-    L.check(L.load().gvk_attention_fwd(C.byref(d), L.stream_ptr()), "gvk_attention_fwd")
+    L.launch.gvk_attention_fwd(C.byref(d))
 
 
 def attention_colsum(qkv, lse, w, out, B, T, H, q0=0, q1=None):
@@ -551,8 +534,7 @@ def attention_colsum(qkv, lse, w, out, B, T, H, q0=0, q1=None):
         raise L.GavikoHipError(f"colsum w: expected [B, >= T] = [{B}, >= {T}], got {tuple(w.shape)}")
     if not 0 <= q0 < q1 <= T:
         raise L.GavikoHipError(f"colsum: query rows [{q0}, {q1}) outside [0, {T})")
-    L.check(L.load().gvk_attention_colsum_bf16(L.ptr(qkv), L.ptr(lse), L.ptr(w), ld_w, L.ptr(out), B, T, H, 3 * H * 64, int(q0), int(q1),
-                                               L.stream_ptr()), "gvk_attention_colsum_bf16")
+    L.launch.gvk_attention_colsum_bf16(qkv, lse, w, ld_w, out, B, T, H, 3 * H * 64, int(q0), int(q1))
 
 
 def rollout_step(r_in, colsum, r_out, B, T, H):
@@ -560,7 +542,7 @@ def rollout_step(r_in, colsum, r_out, B, T, H):
     _chk(r_in, torch.float32, "rollout r_in", B * T)
     _chk(r_out, torch.float32, "rollout r_out", B * T)
     _chk(colsum, torch.float32, "rollout colsum", B * H * T)
-    L.check(L.load().gvk_rollout_step(L.ptr(r_in), L.ptr(colsum), L.ptr(r_out), B, T, H, L.stream_ptr()), "gvk_rollout_step")
+    L.launch.gvk_rollout_step(r_in, colsum, r_out, B, T, H)
 
 
 def attention_gradcolsum(qkv, lse, dctx, w, out, B, T, H, q0=0, q1=None):
@@ -577,8 +559,7 @@ def attention_gradcolsum(qkv, lse, dctx, w, out, B, T, H, q0=0, q1=None):
         raise L.GavikoHipError(f"gradcolsum w: expected [B, >= T] = [{B}, >= {T}], got {tuple(w.shape)}")
     if not 0 <= q0 < q1 <= T:
         raise L.GavikoHipError(f"gradcolsum: query rows [{q0}, {q1}) outside [0, {T})")
-    L.check(L.load().gvk_attention_gradcolsum_bf16(L.ptr(qkv), L.ptr(lse), L.ptr(dctx), H * 64, L.ptr(w), ld_w, L.ptr(out), B, T, H, 3 * H * 64,
-                                                   int(q0), int(q1), L.stream_ptr()), "gvk_attention_gradcolsum_bf16")
+    L.launch.gvk_attention_gradcolsum_bf16(qkv, lse, dctx, H * 64, w, ld_w, out, B, T, H, 3 * H * 64, int(q0), int(q1))
 
 
 def relevance_step(r_in, cs, r_out, B, T, H):
@@ -586,7 +567,7 @@ def relevance_step(r_in, cs, r_out, B, T, H):
     _chk(r_in, torch.float32, "relevance r_in", B * T)
     _chk(r_out, torch.float32, "relevance r_out", B * T)
     _chk(cs, torch.float32, "relevance cs", B * H * T)
-    L.check(L.load().gvk_relevance_step(L.ptr(r_in), L.ptr(cs), L.ptr(r_out), B, T, H, L.stream_ptr()), "gvk_relevance_step")
+    L.launch.gvk_relevance_step(r_in, cs, r_out, B, T, H)
 
 
 def _desc(cls, what, **kw):
@@ -606,18 +587,15 @@ def _desc(cls, what, **kw):
 
 
 def skinny_down(**kw):
-    d = _desc(L.SkinnyDownDesc, "skinny_down", **kw)
-    L.check(L.load().gvk_skinny_down(C.byref(d), L.stream_ptr()), "gvk_skinny_down")
+    L.launch.gvk_skinny_down(C.byref(_desc(L.SkinnyDownDesc, "skinny_down", **kw)))
 
 
 def skinny_up(**kw):
-    d = _desc(L.SkinnyUpDesc, "skinny_up", **kw)
-    L.check(L.load().gvk_skinny_up(C.byref(d), L.stream_ptr()), "gvk_skinny_up")
+    L.launch.gvk_skinny_up(C.byref(_desc(L.SkinnyUpDesc, "skinny_up", **kw)))
 
 
 def outer_reduce(**kw):
-    d = _desc(L.OuterDesc, "outer_reduce", **kw)
-    L.check(L.load().gvk_outer_reduce(C.byref(d), L.stream_ptr()), "gvk_outer_reduce")
+    L.launch.gvk_outer_reduce(C.byref(_desc(L.OuterDesc, "outer_reduce", **kw)))
 
 
 OUTER_MAX_ROWS = 10240        # rows one gvk_outer_reduce launch covers (64 slabs x 160 rows), second source included
@@ -682,8 +660,7 @@ def param_grads(outer, small, scratch, tickets, C_, Lat, seed_ptr=None):
     _chk(scratch, torch.float32, "param_grads scratch")
     if tickets is None or tickets.dtype != torch.int32 or not tickets.is_cuda:
         raise L.GavikoHipError("param_grads: tickets must be an int32 tensor on the HIP device (zero at allocation)")
-    L.check(L.load().gvk_param_grads(arr, len(outer), jobs, len(small), L.ptr(scratch), scratch.numel(), L.ptr(tickets), tickets.numel(),
-                                     L.ptr(seed_ptr), C_, Lat, L.stream_ptr()), "gvk_param_grads")
+    L.launch.gvk_param_grads(arr, len(outer), jobs, len(small), scratch, scratch.numel(), tickets, tickets.numel(), seed_ptr, C_, Lat)
 
 
 def param_grads_scratch_elems(Lat, col_tiles, small_outputs):
@@ -698,7 +675,7 @@ def small_wgrad(a, b, out, scratch, M, J, Lb, accumulate=False):
         _chk(t, torch.float32, "small_wgrad " + n)
     if scratch.numel() < 64 * J * Lb or a.numel() < M * J or b.numel() < M * Lb or out.numel() < J * Lb:
         raise L.GavikoHipError("small_wgrad: buffer too small")
-    L.check(L.load().gvk_small_wgrad(L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(scratch), M, J, Lb, int(accumulate), L.stream_ptr()), "gvk_small_wgrad")
+    L.launch.gvk_small_wgrad(a, b, out, scratch, M, J, Lb, int(accumulate))
 
 
 def colsum(x, out, scratch, M, C_, accumulate=False):
@@ -706,27 +683,23 @@ def colsum(x, out, scratch, M, C_, accumulate=False):
         _chk(t, torch.float32, "colsum " + n)
     if scratch.numel() < 64 * C_ or x.numel() < M * C_ or out.numel() < C_:
         raise L.GavikoHipError("colsum: buffer too small")
-    L.check(L.load().gvk_colsum(L.ptr(x), L.ptr(out), L.ptr(scratch), M, C_, int(accumulate), L.stream_ptr()), "gvk_colsum")
+    L.launch.gvk_colsum(x, out, scratch, M, C_, int(accumulate))
 
 
 def window_attn_fwd(**kw):
-    d = _desc(L.WindowAttnDesc, "window_attn", **kw)
-    L.check(L.load().gvk_window_attn_fwd(C.byref(d), L.stream_ptr()), "gvk_window_attn_fwd")
+    L.launch.gvk_window_attn_fwd(C.byref(_desc(L.WindowAttnDesc, "window_attn", **kw)))
 
 
 def window_attn_bwd(**kw):
-    d = _desc(L.WindowAttnDesc, "window_attn", **kw)
-    L.check(L.load().gvk_window_attn_bwd(C.byref(d), L.stream_ptr()), "gvk_window_attn_bwd")
+    L.launch.gvk_window_attn_bwd(C.byref(_desc(L.WindowAttnDesc, "window_attn", **kw)))
 
 
 def gpa_fwd(**kw):
-    d = _desc(L.GpaDesc, "gpa", **kw)
-    L.check(L.load().gvk_gpa_fwd(C.byref(d), L.stream_ptr()), "gvk_gpa_fwd")
+    L.launch.gvk_gpa_fwd(C.byref(_desc(L.GpaDesc, "gpa", **kw)))
 
 
 def gpa_bwd(**kw):
-    d = _desc(L.GpaDesc, "gpa", **kw)
-    L.check(L.load().gvk_gpa_bwd(C.byref(d), L.stream_ptr()), "gvk_gpa_bwd")
+    L.launch.gvk_gpa_bwd(C.byref(_desc(L.GpaDesc, "gpa", **kw)))
 
 
 _MAP_WIDTHS = (4, 8, 16, 20, 32)
@@ -749,7 +722,7 @@ def window_attn_colsum(qkv, lse, w, out, B, D, H, W, kd, kh, kw, L_, scale):
         raise L.GavikoHipError("window_attn_colsum: qkv, lse, w and out are all required")
     d = _desc(L.WindowColsumDesc, "window_attn_colsum", qkv=qkv, lse=lse, w=w, out=out, B=B, D=D, H=H, W=W, kd=kd, kh=kh, kw=kw, L=L_,
               scale=float(scale))
-    L.check(L.load().gvk_window_attn_colsum(C.byref(d), L.stream_ptr()), "gvk_window_attn_colsum")
+    L.launch.gvk_window_attn_colsum(C.byref(d))
 
 
 def gpa_attn_maps(xl, ll, qg, ql, lse_g, lse_l, imp, gw, B, T, N, P, L_, *, global_=None, local=None, fused=None):
@@ -776,7 +749,7 @@ def gpa_attn_maps(xl, ll, qg, ql, lse_g, lse_l, imp, gw, B, T, N, P, L_, *, glob
         _chk(t, torch.float32, "gpa_attn_maps " + name, B * P * N)
     d = _desc(L.GpaMapsDesc, "gpa_attn_maps", xl=xl, ll=ll, qg=qg, ql=ql, lse_g=lse_g, lse_l=lse_l, imp=imp, gw=gw, pg=global_, pl=local,
               fused=fused, B=B, T=T, N=N, P=P, L=L_)
-    L.check(L.load().gvk_gpa_attn_maps(C.byref(d), L.stream_ptr()), "gvk_gpa_attn_maps")
+    L.launch.gvk_gpa_attn_maps(C.byref(d))
 
 
 def gpa_gate_param_count(Lat, P):
@@ -787,25 +760,22 @@ def rows_broadcast(out, src, add, B, T, row_off, R, C_):
     _chk(out, torch.float32, "rows_broadcast out", B * T * C_)
     _chk(src, torch.float32, "rows_broadcast src", R * C_)
     _chk(add, torch.float32, "rows_broadcast add", R * C_)
-    L.check(L.load().gvk_rows_broadcast(L.ptr(out), L.ptr(src), L.ptr(add), B, T, row_off, R, C_, L.stream_ptr()), "gvk_rows_broadcast")
+    L.launch.gvk_rows_broadcast(out, src, add, B, T, row_off, R, C_)
 
 
 def rows_batch_sum(dg, out, out2, B, T, row_off, R, C_, accumulate=False):
     _chk(dg, torch.float32, "rows_batch_sum dg", B * T * C_)
     _chk(out, torch.float32, "rows_batch_sum out", R * C_)
     _chk(out2, torch.float32, "rows_batch_sum out2", R * C_)
-    L.check(L.load().gvk_rows_batch_sum(L.ptr(dg), L.ptr(out), L.ptr(out2), B, T, row_off, R, C_, int(accumulate), L.stream_ptr()),
-            "gvk_rows_batch_sum")
+    L.launch.gvk_rows_batch_sum(dg, out, out2, B, T, row_off, R, C_, int(accumulate))
 
 
 def head_fwd(**kw):
-    d = _desc(L.HeadDesc, "head", **kw)
-    L.check(L.load().gvk_head_fwd(C.byref(d), L.stream_ptr()), "gvk_head_fwd")
+    L.launch.gvk_head_fwd(C.byref(_desc(L.HeadDesc, "head", **kw)))
 
 
 def head_bwd(**kw):
-    d = _desc(L.HeadDesc, "head", **kw)
-    L.check(L.load().gvk_head_bwd(C.byref(d), L.stream_ptr()), "gvk_head_bwd")
+    L.launch.gvk_head_bwd(C.byref(_desc(L.HeadDesc, "head", **kw)))
 
 
 def attention_bwd_workspace(B, T, H, device):
@@ -846,7 +816,7 @@ def attention_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, scale, drop_p=0.0, 
                         seed_ptr=L.ptr(seed_ptr) if drop else None, ws=L.ptr(ws), B=B, T=T, H=H, ld_qkv=3 * inner, ld_out=inner, f32=int(f32),
                         need_rows=need_rows, scale=scale, drop_p=float(drop_p), seed=int(seed) if drop else 0,
                         ws_bytes=ws.numel() * 4 if ws is not None else 0)
-    L.check(L.load().gvk_attention_bwd(C.byref(d), L.stream_ptr()), "gvk_attention_bwd")
+    L.launch.gvk_attention_bwd(C.byref(d))
 
 
 def small_linear_fwd(x, w, b, out, R, K, C_):
@@ -854,27 +824,26 @@ def small_linear_fwd(x, w, b, out, R, K, C_):
         _chk(t, torch.float32, "small_linear " + n)
     if x.numel() < R * K or w.numel() < C_ * K or out.numel() < R * C_:
         raise L.GavikoHipError("small_linear_fwd: buffer too small")
-    L.check(L.load().gvk_small_linear_fwd(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(out), R, K, C_, L.stream_ptr()), "gvk_small_linear_fwd")
+    L.launch.gvk_small_linear_fwd(x, w, b, out, R, K, C_)
 
 
 def small_linear_bwd(x, w, dout, dw, db, dx, R, K, C_, accumulate=False):
     for t, n in ((x, "x"), (w, "w"), (dout, "dout"), (dw, "dw"), (db, "db"), (dx, "dx")):
         _chk(t, torch.float32, "small_linear_bwd " + n)
-    L.check(L.load().gvk_small_linear_bwd(L.ptr(x), L.ptr(w), L.ptr(dout), L.ptr(dw), L.ptr(db), L.ptr(dx), R, K, C_, int(accumulate),
-                                          L.stream_ptr()), "gvk_small_linear_bwd")
+    L.launch.gvk_small_linear_bwd(x, w, dout, dw, db, dx, R, K, C_, int(accumulate))
 
 
 def vpt_repack_fwd(inp, prompt, out, B, Tin, Tout, P, skip, C_):
     _chk(inp, torch.float32, "vpt_repack in", B * Tin * C_)
     _chk(prompt, torch.float32, "vpt_repack prompt", P * C_)
     _chk(out, torch.float32, "vpt_repack out", B * Tout * C_)
-    L.check(L.load().gvk_vpt_repack_fwd(L.ptr(inp), L.ptr(prompt), L.ptr(out), B, Tin, Tout, P, skip, C_, L.stream_ptr()), "gvk_vpt_repack_fwd")
+    L.launch.gvk_vpt_repack_fwd(inp, prompt, out, B, Tin, Tout, P, skip, C_)
 
 
 def vpt_repack_bwd(dout, din, B, Tin, Tout, P, skip, C_):
     _chk(dout, torch.float32, "vpt_repack_bwd dout", B * Tout * C_)
     _chk(din, torch.float32, "vpt_repack_bwd din", B * Tin * C_)
-    L.check(L.load().gvk_vpt_repack_bwd(L.ptr(dout), L.ptr(din), B, Tin, Tout, P, skip, C_, L.stream_ptr()), "gvk_vpt_repack_bwd")
+    L.launch.gvk_vpt_repack_bwd(dout, din, B, Tin, Tout, P, skip, C_)
 
 
 def cast_bf16_f32_strided(inp, out, M, C_, ld_in, col0=0):
@@ -882,11 +851,11 @@ def cast_bf16_f32_strided(inp, out, M, C_, ld_in, col0=0):
     if inp.dtype == torch.float32:
         _chk(inp, torch.float32, "copy_strided in", M * ld_in)
         _chk(out, torch.float32, "copy_strided out", M * C_)
-        L.check(L.load().gvk_copy_f32_strided(inp.data_ptr() + 4 * col0, L.ptr(out), M, C_, ld_in, L.stream_ptr()), "gvk_copy_f32_strided")
+        L.launch.gvk_copy_f32_strided(inp.data_ptr() + 4 * col0, out, M, C_, ld_in)
         return
     _chk(inp, torch.bfloat16, "cast_bf16_f32 in", M * ld_in)
     _chk(out, torch.float32, "cast_bf16_f32 out", M * C_)
-    L.check(L.load().gvk_cast_bf16_f32_strided(inp.data_ptr() + 2 * col0, L.ptr(out), M, C_, ld_in, L.stream_ptr()), "gvk_cast_bf16_f32_strided")
+    L.launch.gvk_cast_bf16_f32_strided(inp.data_ptr() + 2 * col0, out, M, C_, ld_in)
 
 
 def lora_merge(w, a_q, b_q, a_v, b_v, out, C_, r, s):
@@ -894,8 +863,7 @@ def lora_merge(w, a_q, b_q, a_v, b_v, out, C_, r, s):
         _chk(t, torch.float32, "lora_merge " + n)
     if w.numel() != 3 * C_ * C_ or out.numel() < 3 * C_ * C_ or a_q.numel() != r * C_ or b_q.numel() != C_ * r:
         raise L.GavikoHipError("lora_merge: shape mismatch")
-    L.check(L.load().gvk_lora_merge_f32(L.ptr(w), L.ptr(a_q), L.ptr(b_q), L.ptr(a_v), L.ptr(b_v), L.ptr(out), C_, r, float(s), L.stream_ptr()),
-            "gvk_lora_merge_f32")
+    L.launch.gvk_lora_merge_f32(w, a_q, b_q, a_v, b_v, out, C_, r, float(s))
 
 
 def reduce_batch(jobs, scratch):
@@ -921,7 +889,7 @@ def reduce_batch(jobs, scratch):
             raise L.GavikoHipError("reduce_batch: a2 goes with column sums of the same width only")
         arr[k] = L.ReduceJob(L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(a2), M, J, Lb, int(bool(acc)), 0 if a2 is None else a2.shape[0])
     _chk(scratch, torch.float32, "reduce_batch scratch", 32 * total)
-    L.check(L.load().gvk_reduce_batch(arr, len(jobs), L.ptr(scratch), L.stream_ptr()), "gvk_reduce_batch")
+    L.launch.gvk_reduce_batch(arr, len(jobs), scratch)
 
 
 def ln_lowrank_affine(Q, S, W, gamma, beta, dW, dgamma, dbeta, dbias, Lat, C_, accumulate=False):
@@ -929,8 +897,7 @@ def ln_lowrank_affine(Q, S, W, gamma, beta, dW, dgamma, dbeta, dbias, Lat, C_, a
         _chk(t, torch.float32, "ln_lowrank_affine " + n)
     if Q.numel() < Lat * C_ or W.numel() < Lat * C_ or dW.numel() < Lat * C_ or S.numel() < Lat:
         raise L.GavikoHipError("ln_lowrank_affine: buffer too small")
-    L.check(L.load().gvk_ln_lowrank_affine(L.ptr(Q), L.ptr(S), L.ptr(W), L.ptr(gamma), L.ptr(beta), L.ptr(dW), L.ptr(dgamma), L.ptr(dbeta),
-                                           L.ptr(dbias), Lat, C_, int(bool(accumulate)), L.stream_ptr()), "gvk_ln_lowrank_affine")
+    L.launch.gvk_ln_lowrank_affine(Q, S, W, gamma, beta, dW, dgamma, dbeta, dbias, Lat, C_, int(bool(accumulate)))
 
 
 # ---- SSF (model/ssf.py): effective parameters and scale/shift gradients ---------------------------------------------------
@@ -944,15 +911,14 @@ def ssf_fold_weight(w, s, out, out_t=None):
         raise L.GavikoHipError("ssf_fold_weight: outputs must be bf16 or fp32 (both the same)")
     _chk(out, out.dtype, "ssf_fold_weight out", N * K)
     _chk(out_t, out.dtype, "ssf_fold_weight out_t", N * K)
-    L.check(L.load().gvk_ssf_fold_weight(L.ptr(w), L.ptr(s), L.ptr(out), L.ptr(out_t), N, K, int(out.dtype == torch.float32), L.stream_ptr()),
-            "gvk_ssf_fold_weight")
+    L.launch.gvk_ssf_fold_weight(w, s, out, out_t, N, K, int(out.dtype == torch.float32))
 
 
 def ssf_fold_vec(a, s, t, out):
     n = s.numel()
     for x, nm in ((a, "a"), (s, "s"), (t, "t"), (out, "out")):
         _chk(x, torch.float32, "ssf_fold_vec " + nm, n)
-    L.check(L.load().gvk_ssf_fold_vec(L.ptr(a), L.ptr(s), L.ptr(t), L.ptr(out), n, L.stream_ptr()), "gvk_ssf_fold_vec")
+    L.launch.gvk_ssf_fold_vec(a, s, t, out, n)
 
 
 def ssf_colgrad(dy, y0, s, t, ds, dt, scratch, M, N, *, y1=None, pos=None, ld_dy=None, ld_y=None, rows_in=0, rows_out=0, row_off=0,
@@ -969,40 +935,36 @@ def ssf_colgrad(dy, y0, s, t, ds, dt, scratch, M, N, *, y1=None, pos=None, ld_dy
                          scratch=L.ptr(scratch), M=M, N=N, ld_dy=N if ld_dy is None else ld_dy, ld_y=N if ld_y is None else ld_y,
                          dy_f32=int(dy.dtype == torch.float32), y0_f32=int(y0.dtype == torch.float32), rows_in=rows_in, rows_out=rows_out,
                          row_off=row_off, y0_cols=int(y0_cols), y0_mul=float(y0_mul), y_mul=float(y_mul))
-    L.check(L.load().gvk_ssf_colgrad(C.byref(d), L.stream_ptr()), "gvk_ssf_colgrad")
+    L.launch.gvk_ssf_colgrad(C.byref(d))
 
 
 def ssf_ln_grad(dgamma_eff, dbeta_eff, gamma, beta, ds, dt):
     n = gamma.numel()
     for x, nm in ((dgamma_eff, "dgamma'"), (dbeta_eff, "dbeta'"), (gamma, "gamma"), (beta, "beta"), (ds, "ds"), (dt, "dt")):
         _chk(x, torch.float32, "ssf_ln_grad " + nm, n)
-    L.check(L.load().gvk_ssf_ln_grad(L.ptr(dgamma_eff), L.ptr(dbeta_eff), L.ptr(gamma), L.ptr(beta), L.ptr(ds), L.ptr(dt), n, L.stream_ptr()),
-            "gvk_ssf_ln_grad")
+    L.launch.gvk_ssf_ln_grad(dgamma_eff, dbeta_eff, gamma, beta, ds, dt, n)
 
 
 def ssf_head_grad(g, mean, rstd, wh, dlogits, gamma, beta, ds, dt, B, T, C_, K, r0, R):
     for x, nm in ((g, "g"), (mean, "mean"), (rstd, "rstd"), (wh, "wh"), (dlogits, "dlogits"), (gamma, "gamma"), (beta, "beta"), (ds, "ds"), (dt, "dt")):
         _chk(x, torch.float32, "ssf_head_grad " + nm)
-    L.check(L.load().gvk_ssf_head_grad(L.ptr(g), L.ptr(mean), L.ptr(rstd), L.ptr(wh), L.ptr(dlogits), L.ptr(gamma), L.ptr(beta), L.ptr(ds),
-                                       L.ptr(dt), B, T, C_, K, r0, R, L.stream_ptr()), "gvk_ssf_head_grad")
+    L.launch.gvk_ssf_head_grad(g, mean, rstd, wh, dlogits, gamma, beta, ds, dt, B, T, C_, K, r0, R)
 
 
 # ---- DVPT (model/dvpt.py) ------------------------------------------------------------------------------------------------
 def dvpt_fwd(**kw):
-    d = _desc(L.DvptDesc, "dvpt_fwd", **kw)
-    L.check(L.load().gvk_dvpt_fwd(C.byref(d), L.stream_ptr()), "gvk_dvpt_fwd")
+    L.launch.gvk_dvpt_fwd(C.byref(_desc(L.DvptDesc, "dvpt_fwd", **kw)))
 
 
 def dvpt_bwd(**kw):
-    d = _desc(L.DvptDesc, "dvpt_bwd", **kw)
-    L.check(L.load().gvk_dvpt_bwd(C.byref(d), L.stream_ptr()), "gvk_dvpt_bwd")
+    L.launch.gvk_dvpt_bwd(C.byref(_desc(L.DvptDesc, "dvpt_bwd", **kw)))
 
 
 def scale_dev_(t: torch.Tensor, alpha: torch.Tensor) -> None:
     """t *= alpha[0] with alpha a device scalar (no host read)."""
     _chk(t, torch.float32, "scale_dev_ x")
     _chk(alpha, torch.float32, "scale_dev_ alpha", 1)
-    L.check(L.load().gvk_scale_dev(L.ptr(t), L.ptr(alpha), t.numel(), L.stream_ptr()), "gvk_scale_dev")
+    L.launch.gvk_scale_dev(t, alpha, t.numel())
 
 
 # ---- EVP (model/evp.py) --------------------------------------------------------------------------------------------------
@@ -1012,7 +974,7 @@ def evp_highpass(img, hp, depth_mask, out):
     _chk(hp, torch.float32, "evp_highpass hp", H * H)
     _chk(depth_mask, torch.int32, "evp_highpass depth_mask", D)
     _chk(out, torch.float32, "evp_highpass out", img.numel())
-    L.check(L.load().gvk_evp_highpass(L.ptr(img), L.ptr(hp), L.ptr(depth_mask), L.ptr(out), B * ch, D, H, W, L.stream_ptr()), "gvk_evp_highpass")
+    L.launch.gvk_evp_highpass(img, hp, depth_mask, out, B * ch, D, H, W)
 
 
 def evp_highpass_sign(img, hp, depth_mask, dout, out):
@@ -1023,8 +985,7 @@ def evp_highpass_sign(img, hp, depth_mask, dout, out):
     _chk(depth_mask, torch.int32, "evp_highpass_sign depth_mask", D)
     _chk(dout, torch.float32, "evp_highpass_sign dout", img.numel())
     _chk(out, torch.float32, "evp_highpass_sign out", img.numel())
-    L.check(L.load().gvk_evp_highpass_sign(L.ptr(img), L.ptr(hp), L.ptr(depth_mask), L.ptr(dout), L.ptr(out), B * ch, D, H, W, L.stream_ptr()),
-            "gvk_evp_highpass_sign")
+    L.launch.gvk_evp_highpass_sign(img, hp, depth_mask, dout, out, B * ch, D, H, W)
 
 
 def evp_highpass_linear(x, op, depth_mask, out, accumulate=False):
@@ -1036,47 +997,45 @@ def evp_highpass_linear(x, op, depth_mask, out, accumulate=False):
     _chk(out, torch.float32, "evp_highpass_linear out", x.numel())
     if out.data_ptr() == x.data_ptr():
         raise L.GavikoHipError("evp_highpass_linear: out must not alias x")
-    L.check(L.load().gvk_evp_highpass_linear(L.ptr(x), L.ptr(op), L.ptr(depth_mask), L.ptr(out), int(bool(accumulate)), B * ch, D, H, W,
-                                             L.stream_ptr()), "gvk_evp_highpass_linear")
+    L.launch.gvk_evp_highpass_linear(x, op, depth_mask, out, int(bool(accumulate)), B * ch, D, H, W)
 
 
 def pad2d(src, rows, cols, dst, drows, dcols, *, ld_src=None, ld_dst=None, transpose=False):
     """dst[drows x dcols] = src[rows x cols] (optionally transposed) zero-padded."""
     _chk(src, torch.float32, "pad2d src")
     _chk(dst, torch.float32, "pad2d dst")
-    L.check(L.load().gvk_pad2d_f32(L.ptr(src), cols if ld_src is None else ld_src, rows, cols, int(transpose), L.ptr(dst),
-                                   dcols if ld_dst is None else ld_dst, drows, dcols, L.stream_ptr()), "gvk_pad2d_f32")
+    L.launch.gvk_pad2d_f32(src, cols if ld_src is None else ld_src, rows, cols, int(transpose), dst, dcols if ld_dst is None else ld_dst, drows, dcols)
 
 
 def add2d(a, lda, b, ldb, out, ldo, rows, cols):
     for t, n in ((a, "a"), (b, "b"), (out, "out")):
         _chk(t, torch.float32, "add2d " + n)
-    L.check(L.load().gvk_add2d_f32(L.ptr(a), lda, L.ptr(b), ldb, L.ptr(out), ldo, rows, cols, L.stream_ptr()), "gvk_add2d_f32")
+    L.launch.gvk_add2d_f32(a, lda, b, ldb, out, ldo, rows, cols)
 
 
 def gelu_fwd(x, y):
     _chk(x, torch.float32, "gelu_fwd x")
     _chk(y, torch.float32, "gelu_fwd y", x.numel())
-    L.check(L.load().gvk_gelu_fwd_f32(L.ptr(x), L.ptr(y), x.numel(), L.stream_ptr()), "gvk_gelu_fwd_f32")
+    L.launch.gvk_gelu_fwd_f32(x, y, x.numel())
 
 
 def gelu_bwd(dy, x, dx):
     for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")):
         _chk(t, torch.float32, "gelu_bwd " + n, x.numel())
-    L.check(L.load().gvk_gelu_bwd_f32(L.ptr(dy), L.ptr(x), L.ptr(dx), x.numel(), L.stream_ptr()), "gvk_gelu_bwd_f32")
+    L.launch.gvk_gelu_bwd_f32(dy, x, dx, x.numel())
 
 
 def rows_patch(tok, src, pos, B, T, N, C_, row_off, accumulate):
     _chk(tok, torch.float32, "rows_patch tok", B * T * C_)
     _chk(src, torch.float32, "rows_patch src", B * N * C_)
     _chk(pos, torch.float32, "rows_patch pos", N * C_)
-    L.check(L.load().gvk_rows_patch(L.ptr(tok), L.ptr(src), L.ptr(pos), B, T, N, C_, row_off, int(accumulate), L.stream_ptr()), "gvk_rows_patch")
+    L.launch.gvk_rows_patch(tok, src, pos, B, T, N, C_, row_off, int(accumulate))
 
 
 def rows_gather(tok, dst, B, T, N, C_, row_off):
     _chk(tok, torch.float32, "rows_gather tok", B * T * C_)
     _chk(dst, torch.float32, "rows_gather dst", B * N * C_)
-    L.check(L.load().gvk_rows_gather(L.ptr(tok), L.ptr(dst), B, T, N, C_, row_off, L.stream_ptr()), "gvk_rows_gather")
+    L.launch.gvk_rows_gather(tok, dst, B, T, N, C_, row_off)
 
 
 # ---- loss seed (train.py:176-179, 283/306, 327-328) -------------------------------------------------------------------------
@@ -1105,7 +1064,7 @@ def loss_fwd_bwd(logits, target, loss, dlogits, kind, gamma=0.0, eps=1e-16, igno
     d = L.LossDesc(logits=L.ptr(logits), target=L.ptr(target), weights=L.ptr(weights) if weights is not None else None,
                    loss=L.ptr(loss), dlogits=L.ptr(dlogits), meter=L.ptr(meter) if meter is not None else None,
                    B=B, K=K, kind=kind, reduction={"mean": 0, "sum": 1, "none": 2}[reduction], gamma=gamma, eps=eps, ignore_index=ignore_index)
-    L.check(L.load().gvk_loss_fwd_bwd(C.byref(d), L.stream_ptr()), "gvk_loss_fwd_bwd")
+    L.launch.gvk_loss_fwd_bwd(C.byref(d))
 
 
 def loss_mixed_fwd_bwd(logits, target_a, target_b, lam, loss, dlogits, kind, gamma=0.0, eps=1e-16, smoothing=0.0, ignore_index=-100, weights=None,
@@ -1144,7 +1103,7 @@ def loss_mixed_fwd_bwd(logits, target_a, target_b, lam, loss, dlogits, kind, gam
                         loss=L.ptr(loss), dlogits=L.ptr(dlogits), meter=L.ptr(meter) if meter is not None else None,
                         B=B, K=K, kind=kind, reduction={"mean": 0, "sum": 1, "none": 2}[reduction], gamma=gamma, eps=eps, smoothing=smoothing,
                         ignore_index=ignore_index)
-    L.check(L.load().gvk_loss_mixed_fwd_bwd(C.byref(d), L.stream_ptr()), "gvk_loss_mixed_fwd_bwd")
+    L.launch.gvk_loss_mixed_fwd_bwd(C.byref(d))
 
 
 # ---- data side + evaluation metrics (train.py:38-62, eval.py:103-122) --------------------------------------------------------
@@ -1156,7 +1115,7 @@ def volume_minmax(x: torch.Tensor, partials: torch.Tensor) -> None:
     _chk(x, torch.float32, "volume_minmax x")
     B = x.shape[0]
     _chk(partials, torch.float32, "volume_minmax partials", B * L.load().gvk_minmax_partials())
-    L.check(L.load().gvk_volume_minmax(L.ptr(x), L.ptr(partials), B, x.numel() // B, L.stream_ptr()), "gvk_volume_minmax")
+    L.launch.gvk_volume_minmax(x, partials, B, x.numel() // B)
 
 
 def rescale_intensity(x, partials, y, out_min=0.0, out_max=1.0, minmax=None) -> None:
@@ -1165,8 +1124,7 @@ def rescale_intensity(x, partials, y, out_min=0.0, out_max=1.0, minmax=None) -> 
     B = x.shape[0]
     if minmax is not None:
         _chk(minmax, torch.float32, "rescale_intensity minmax", 2 * B)
-    L.check(L.load().gvk_rescale_intensity(L.ptr(x), L.ptr(partials), L.ptr(y), L.ptr(minmax) if minmax is not None else None, B, x.numel() // B,
-                                           out_min, out_max, L.stream_ptr()), "gvk_rescale_intensity")
+    L.launch.gvk_rescale_intensity(x, partials, y, minmax, B, x.numel() // B, out_min, out_max)
 
 
 def spatial_transform(x, out, mats, flags, partials) -> None:
@@ -1175,8 +1133,7 @@ def spatial_transform(x, out, mats, flags, partials) -> None:
     B, D, H, W = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
     _chk(mats, torch.float32, "spatial_transform mats", 12 * B)
     _chk(flags, torch.int32, "spatial_transform flags", B)
-    L.check(L.load().gvk_spatial_transform(L.ptr(x), L.ptr(out), L.ptr(mats), L.ptr(flags), L.ptr(partials), B, D, H, W, L.stream_ptr()),
-            "gvk_spatial_transform")
+    L.launch.gvk_spatial_transform(x, out, mats, flags, partials, B, D, H, W)
 
 
 BLUR_MAX_RADIUS, BLUR_TAPS, BIAS_COEFFS = 16, 33, 20                     # GVK_BLUR_MAX_RADIUS, its table row length, GVK_BIAS_COEFFS
@@ -1199,8 +1156,7 @@ def gaussian_blur3d(x, out, scratch, weights, radius, max_radius) -> None:
     _chk(scratch, torch.float32, "gaussian_blur3d scratch", x.numel())
     _chk(weights, torch.float32, "gaussian_blur3d weights", 3 * BLUR_TAPS * B)
     _chk(radius, torch.int32, "gaussian_blur3d radius", 3 * B)
-    L.check(L.load().gvk_gaussian_blur3d(L.ptr(x), L.ptr(out), L.ptr(scratch), L.ptr(weights), L.ptr(radius), int(max_radius), B, D, H, W,
-                                         L.stream_ptr()), "gvk_gaussian_blur3d")
+    L.launch.gvk_gaussian_blur3d(x, out, scratch, weights, radius, int(max_radius), B, D, H, W)
 
 
 def intensity_pointwise(x, y, kind, noise, seeds, coeff, order=3) -> None:
@@ -1211,8 +1167,7 @@ def intensity_pointwise(x, y, kind, noise, seeds, coeff, order=3) -> None:
     _chk(noise, torch.float32, "intensity_pointwise noise", 2 * B)
     _chk(seeds, torch.int64, "intensity_pointwise seeds", B)
     _chk(coeff, torch.float32, "intensity_pointwise coeff", BIAS_COEFFS * B)
-    L.check(L.load().gvk_intensity_pointwise(L.ptr(x), L.ptr(y), L.ptr(kind), L.ptr(noise), L.ptr(seeds), L.ptr(coeff), int(order), B, D, H, W,
-                                             L.stream_ptr()), "gvk_intensity_pointwise")
+    L.launch.gvk_intensity_pointwise(x, y, kind, noise, seeds, coeff, int(order), B, D, H, W)
 
 
 MOTION_MAX_TRANSFORMS, MOTION_MAX_W = 4, 256                             # GVK_MOTION_MAX_TRANSFORMS, GVK_MOTION_MAX_W
@@ -1228,8 +1183,7 @@ def motion_artifact(x, out, mats, ctab, live, partials, K) -> None:
     _chk(ctab, torch.float32, "motion_artifact ctab", (max(K, 0) + 1) * W * B)
     _chk(live, torch.int32, "motion_artifact live", B)
     _chk(partials, torch.float32, "motion_artifact partials", B * L.load().gvk_minmax_partials())
-    L.check(L.load().gvk_motion_artifact(L.ptr(x), L.ptr(out), L.ptr(mats), L.ptr(ctab), L.ptr(live), L.ptr(partials), K, B, D, H, W, L.stream_ptr()),
-            "gvk_motion_artifact")
+    L.launch.gvk_motion_artifact(x, out, mats, ctab, live, partials, K, B, D, H, W)
 
 
 ELASTIC_MAX_CONTROL_POINTS = 16                                           # GVK_ELASTIC_MAX_CONTROL_POINTS
@@ -1249,8 +1203,7 @@ def elastic_deform(x, out, ctrl, live, partials, field=None) -> None:
     _chk(partials, torch.float32, "elastic_deform partials", B * L.load().gvk_minmax_partials())
     if field is not None:
         _chk(field, torch.float32, "elastic_deform field", 3 * x.numel())
-    L.check(L.load().gvk_elastic_deform(L.ptr(x), L.ptr(out), L.ptr(field) if field is not None else None, L.ptr(ctrl), L.ptr(live), L.ptr(partials),
-                                        B, D, H, W, n0, n1, n2, L.stream_ptr()), "gvk_elastic_deform")
+    L.launch.gvk_elastic_deform(x, out, field, ctrl, live, partials, B, D, H, W, n0, n1, n2)
 
 
 NORMALIZE_SLABS, NORMALIZE_STATS, NORMALIZE_MAX_PERCENTILES = 128, 8, 4     # GVK_NORMALIZE_SLABS, _STATS, _MAX_PERCENTILES
@@ -1297,8 +1250,7 @@ def volume_stats(x: torch.Tensor, mask=None, want_std: bool = True, stats: torch
     if partials is None:
         partials = torch.empty(B * NORMALIZE_SLABS * 4, dtype=torch.float64, device=x.device)
     _chk(partials, torch.float64, "volume_stats partials", B * NORMALIZE_SLABS * 4)
-    L.check(L.load().gvk_volume_stats(L.ptr(x), L.ptr(partials), L.ptr(stats), L.ptr(count), mode, t, int(bool(want_std)), B, V, L.stream_ptr()),
-            "gvk_volume_stats")
+    L.launch.gvk_volume_stats(x, partials, stats, count, mode, t, int(bool(want_std)), B, V)
     return stats, count
 
 
@@ -1320,8 +1272,7 @@ def volume_order_stats(x: torch.Tensor, stats: torch.Tensor, percentiles, pairs:
     _chk(ws, torch.int32, "volume_order_stats workspace", B * NORMALIZE_ORDER_WS_WORDS)
     _chk(pairs, torch.float32, "volume_order_stats pairs", 2 * B * len(q))
     _chk(cutoffs, torch.float32, "volume_order_stats cutoffs", B * len(q))
-    L.check(L.load().gvk_volume_order_stats(L.ptr(x), L.ptr(stats), L.ptr(ws), L.ptr(pairs), L.ptr(cutoffs), len(q), *qf, B, V, L.stream_ptr()),
-            "gvk_volume_order_stats")
+    L.launch.gvk_volume_order_stats(x, stats, ws, pairs, cutoffs, len(q), *qf, B, V)
     return pairs, cutoffs
 
 
@@ -1347,8 +1298,7 @@ def normalize_intensity(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, m
         params = torch.empty((B, 8), dtype=torch.float64, device=x.device)
     _chk(status, torch.int32, "normalize_intensity status", B)
     _chk(params, torch.float64, "normalize_intensity params", 8 * B)
-    L.check(L.load().gvk_normalize_intensity(L.ptr(x), L.ptr(y), L.ptr(stats), L.ptr(cutoffs) if Q else None, Q, L.ptr(params), L.ptr(status), mode,
-                                             float(out_min), float(out_max), B, V, L.stream_ptr()), "gvk_normalize_intensity")
+    L.launch.gvk_normalize_intensity(x, y, stats, cutoffs if Q else None, Q, params, status, mode, float(out_min), float(out_max), B, V)
     return status
 
 
@@ -1365,8 +1315,7 @@ def axis_circular_conv(x, out, ctab, axis, live) -> None:
     _chk(ctab, torch.float32, "axis_circular_conv ctab", AXIS_CONV_MAX_N * B)
     _chk(axis, torch.int32, "axis_circular_conv axis", B)
     _chk(live, torch.int32, "axis_circular_conv live", B)
-    L.check(L.load().gvk_axis_circular_conv(L.ptr(x), L.ptr(out), L.ptr(ctab), L.ptr(axis), L.ptr(live), B, D, H, W, L.stream_ptr()),
-            "gvk_axis_circular_conv")
+    L.launch.gvk_axis_circular_conv(x, out, ctab, axis, live, B, D, H, W)
 
 
 def gamma_spike(x, out, kind, gamma, amp, nspikes, tab, stats) -> None:
@@ -1381,8 +1330,7 @@ def gamma_spike(x, out, kind, gamma, amp, nspikes, tab, stats) -> None:
     _chk(nspikes, torch.int32, "gamma_spike nspikes", B)
     _chk(tab, torch.float32, "gamma_spike tab", B * SPIKE_MAX * 2 * (D + H + W))
     _chk(stats, torch.float64, "gamma_spike stats", B * NORMALIZE_STATS)
-    L.check(L.load().gvk_gamma_spike(L.ptr(x), L.ptr(out), L.ptr(kind), L.ptr(gamma), L.ptr(amp), L.ptr(nspikes), L.ptr(tab), L.ptr(stats), B, D, H, W,
-                                     L.stream_ptr()), "gvk_gamma_spike")
+    L.launch.gvk_gamma_spike(x, out, kind, gamma, amp, nspikes, tab, stats, B, D, H, W)
 
 
 def axis_gather2(x, out, src, w, axis, live) -> None:
@@ -1396,8 +1344,7 @@ def axis_gather2(x, out, src, w, axis, live) -> None:
         raise L.GavikoHipError(f"axis_gather2: src [B = {B}][n_max][2] and w [B][n_max] expected")
     _chk(axis, torch.int32, "axis_gather2 axis", B)
     _chk(live, torch.int32, "axis_gather2 live", B)
-    L.check(L.load().gvk_axis_gather2(L.ptr(x), L.ptr(out), L.ptr(src), L.ptr(w), L.ptr(axis), L.ptr(live), int(src.shape[1]), B, D, H, W,
-                                      L.stream_ptr()), "gvk_axis_gather2")
+    L.launch.gvk_axis_gather2(x, out, src, w, axis, live, int(src.shape[1]), B, D, H, W)
 
 
 MIX_COPY, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2                                  # mode[b] of batch_mix (GVK_MIX_*)
@@ -1423,7 +1370,7 @@ def batch_mix(x, out, mode, lam, perm, box) -> None:
     if ((lo < 0) | (hi < lo) | (hi > np.array([D, H, W]))).any():
         raise L.GavikoHipError(f"batch_mix: boxes (d0, d1, h0, h1, w0, w1) must be half-open ranges inside the volume {(D, H, W)}")
     tabs = [torch.from_numpy(t).to(x.device) for t in (mode, lam, perm, box)]
-    L.check(L.load().gvk_batch_mix(L.ptr(x), L.ptr(out), *[L.ptr(t) for t in tabs], B, D, H, W, L.stream_ptr()), "gvk_batch_mix")
+    L.launch.gvk_batch_mix(x, out, *tabs, B, D, H, W)
 
 
 def eval_rows(logits, target, proba, pred, confusion) -> None:
@@ -1434,7 +1381,7 @@ def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(confusion, torch.int64, "eval_rows confusion", K * K)
     if target.dtype != torch.int64 or target.numel() != N or not target.is_contiguous():
         raise ValueError("eval_rows target must be a contiguous int64 [N] tensor")
-    L.check(L.load().gvk_eval_rows(L.ptr(logits), L.ptr(target), L.ptr(proba), L.ptr(pred), L.ptr(confusion), N, K, L.stream_ptr()), "gvk_eval_rows")
+    L.launch.gvk_eval_rows(logits, target, proba, pred, confusion, N, K)
 
 
 def ovr_auc_counts(proba, target, counts) -> None:
@@ -1445,7 +1392,7 @@ def ovr_auc_counts(proba, target, counts) -> None:
     _chk(counts, torch.int64, "ovr_auc counts", 3 * K)
     if not target.is_cuda or target.dtype != torch.int64 or target.numel() != N or not target.is_contiguous():
         raise ValueError("ovr_auc_counts target must be a contiguous int64 [N] tensor on the device")
-    L.check(L.load().gvk_ovr_auc_counts(L.ptr(proba), L.ptr(target), L.ptr(counts), N, K, L.stream_ptr()), "gvk_ovr_auc_counts")
+    L.launch.gvk_ovr_auc_counts(proba, target, counts, N, K)
 
 
 def dropout_rows(x, drop_p, seed, seed_ptr, out32=None, out16=None, M=None, N=None, rows_in=0, rows_out=0, row_off=0):
@@ -1460,7 +1407,7 @@ def dropout_rows(x, drop_p, seed, seed_ptr, out32=None, out16=None, M=None, N=No
         _chk(out16, torch.bfloat16, "dropout_rows out16")
     d = L.DropoutDesc(x=L.ptr(x), out32=L.ptr(out32) if out32 is not None else None, out16=L.ptr(out16) if out16 is not None else None,
                       seed_ptr=L.ptr(seed_ptr), M=M, N=N, ld=ld, rows_in=rows_in, rows_out=rows_out, row_off=row_off, drop_p=float(drop_p), seed=int(seed))
-    L.check(L.load().gvk_dropout_rows(C.byref(d), L.stream_ptr()), "gvk_dropout_rows")
+    L.launch.gvk_dropout_rows(C.byref(d))
 
 
 # ---- predictive uncertainty and calibration (csrc/uncertainty.hip) ----
@@ -1485,7 +1432,7 @@ def tta_volumes(x: torch.Tensor, src: torch.Tensor, flip: torch.Tensor, out: tor
         raise L.GavikoHipError("tta_volumes: out must not overlap x")
     if Bout * D * H * W >= 1 << 31:
         raise L.GavikoHipError(f"tta_volumes: {Bout} x {D * H * W} voxels per launch exceed the kernel's 32-bit index range")
-    L.check(L.load().gvk_tta_volumes(L.ptr(x), L.ptr(src), L.ptr(flip), L.ptr(out), Bout, S, D, H, W, L.stream_ptr()), "gvk_tta_volumes")
+    L.launch.gvk_tta_volumes(x, src, flip, out, Bout, S, D, H, W)
 
 
 def predictive_stats(member_logits: torch.Tensor, B: int, S: int, out: dict = None) -> dict:
@@ -1513,9 +1460,8 @@ def predictive_stats(member_logits: torch.Tensor, B: int, S: int, out: dict = No
         _chk(out[k], dt, "predictive_stats " + k)
         if tuple(out[k].shape) != shape:
             raise L.GavikoHipError(f"predictive_stats {k}: expected {shape}, got {tuple(out[k].shape)}")
-    L.check(L.load().gvk_predictive_stats(L.ptr(member_logits), L.ptr(out["probs"]), L.ptr(out["pred"]), L.ptr(out["entropy"]),
-                                          L.ptr(out["expected_entropy"]), L.ptr(out["mutual_info"]), L.ptr(out["variation_ratio"]),
-                                          L.ptr(out["std"]), L.ptr(out["votes"]), B, S, K, L.stream_ptr()), "gvk_predictive_stats")
+    L.launch.gvk_predictive_stats(member_logits, out["probs"], out["pred"], out["entropy"], out["expected_entropy"], out["mutual_info"], out["variation_ratio"],
+                                  out["std"], out["votes"], B, S, K)
     return out
 
 
@@ -1542,8 +1488,7 @@ def calibration_bins(proba: torch.Tensor, target: torch.Tensor, nbins: int, out:
         _chk(out[k], dt, "calibration_bins " + k)
         if out[k].numel() != n:
             raise L.GavikoHipError(f"calibration_bins {k}: expected {n} entries, got {tuple(out[k].shape)}")
-    L.check(L.load().gvk_calibration_bins(L.ptr(proba), L.ptr(target), L.ptr(out["count"]), L.ptr(out["correct"]), L.ptr(out["conf_sum"]),
-                                          L.ptr(out["brier"]), L.ptr(out["nll"]), N, K, nbins, L.stream_ptr()), "gvk_calibration_bins")
+    L.launch.gvk_calibration_bins(proba, target, out["count"], out["correct"], out["conf_sum"], out["brier"], out["nll"], N, K, nbins)
     return out
 
 
@@ -1604,9 +1549,8 @@ def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, rep
     if confusion.numel() != R * K * K or auc_counts.numel() != R * K * 3:
         raise L.GavikoHipError(f"bootstrap_counts: expected confusion [{R}, {K}, {K}] and auc_counts [{R}, {K}, 3], got {tuple(confusion.shape)} and "
                                f"{tuple(auc_counts.shape)}")
-    L.check(L.load().gvk_bootstrap_counts(L.ptr(labels), L.ptr(pred), L.ptr(tables["order"]), L.ptr(tables["gstart"]), L.ptr(tables["gend"]),
-                                          L.ptr(tables["class_rows"]), L.ptr(tables["class_off"]), L.ptr(confusion), L.ptr(auc_counts), N, K, R,
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0, L.stream_ptr()), "gvk_bootstrap_counts")
+    L.launch.gvk_bootstrap_counts(labels, pred, tables["order"], tables["gstart"], tables["gend"], tables["class_rows"], tables["class_off"], confusion,
+                                  auc_counts, N, K, R, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0)
     return confusion, auc_counts
 
 
@@ -1674,10 +1618,9 @@ def risk_coverage_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict,
         out["accepted"] = torch.empty(N, dtype=torch.int32, device=dev)
         out["errors"] = torch.empty(N, dtype=torch.int32, device=dev)
     need_d = torch.tensor(need, dtype=torch.int32, device=dev) if Q else None
-    L.check(L.load().gvk_risk_coverage(L.ptr(labels), L.ptr(pred), L.ptr(tables["order"]), L.ptr(tables["gend"]), L.ptr(tables["class_rows"]),
-                                       L.ptr(class_off), L.ptr(need_d), L.ptr(out["aurc"]), L.ptr(out["at"]) if Q else None, L.ptr(out["total"]),
-                                       L.ptr(out.get("accepted")), L.ptr(out.get("errors")), N, K, Q, R, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                       1 if stratified else 0, 1 if resample else 0, L.stream_ptr()), "gvk_risk_coverage")
+    L.launch.gvk_risk_coverage(labels, pred, tables["order"], tables["gend"], tables["class_rows"], class_off, need_d, out["aurc"], out["at"] if Q else None,
+                               out["total"], out.get("accepted"), out.get("errors"), N, K, Q, R, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0,
+                               1 if resample else 0)
     return out
 
 
@@ -1704,7 +1647,7 @@ def temperature_fit(logits: torch.Tensor, target: torch.Tensor, t_min: float = 0
     _chk(state, torch.float64, "temperature_fit state")
     if state.numel() != 8:
         raise L.GavikoHipError(f"temperature_fit state: expected 8 entries, got {tuple(state.shape)}")
-    L.check(L.load().gvk_temperature_fit(L.ptr(logits), L.ptr(target), L.ptr(state), N, K, t_min, t_max, L.stream_ptr()), "gvk_temperature_fit")
+    L.launch.gvk_temperature_fit(logits, target, state, N, K, t_min, t_max)
     return state
 
 
@@ -1744,7 +1687,7 @@ def token_pool(g: torch.Tensor, B: int, T: int, C: int, r0: int, R: int, out: to
     if out is None:
         out = torch.empty((B, C), dtype=torch.float32, device=g.device)
     _chk(out, torch.float32, "token_pool out", B * C)
-    L.check(L.load().gvk_token_pool(L.ptr(g), L.ptr(out), B, T, C, r0, R, L.stream_ptr()), "gvk_token_pool")
+    L.launch.gvk_token_pool(g, out, B, T, C, r0, R)
     return out
 
 
@@ -1771,7 +1714,7 @@ def l2_normalize_rows(x: torch.Tensor, out: torch.Tensor = None, norm: torch.Ten
         _chk(norm, torch.float32, "l2_normalize_rows norm")
         if norm.numel() != N:
             raise L.GavikoHipError(f"l2_normalize_rows norm: expected {N} entries, got {tuple(norm.shape)}")
-    L.check(L.load().gvk_l2_normalize_rows(L.ptr(x), L.ptr(out), L.ptr(norm), N, C_, float(eps), L.stream_ptr()), "gvk_l2_normalize_rows")
+    L.launch.gvk_l2_normalize_rows(x, out, norm, N, C_, float(eps))
     return out
 
 
@@ -1796,15 +1739,14 @@ def feature_topk(q: torch.Tensor, g: torch.Tensor, k: int, metric: str = "ip", e
                                + (", one excluded per query)" if exclude is not None else ")"))
     if slabs is not None and (isinstance(slabs, bool) or not isinstance(slabs, int) or slabs < 1):
         raise L.GavikoHipError(f"feature_topk: slabs = {slabs!r}: expected None or a positive int")
-    lib = L.load()
-    nslabs = lib.gvk_feature_topk_slabs(Nq, Ng, 0 if slabs is None else slabs)
+    nslabs = L.load().gvk_feature_topk_slabs(Nq, Ng, 0 if slabs is None else slabs)
     words = 2 * Nq * nslabs * k
     scratch = torch.empty(words, dtype=torch.int32, device=q.device)
     idx = torch.empty((Nq, k), dtype=torch.int32, device=q.device)
     score = torch.empty((Nq, k), dtype=torch.float32, device=q.device)
     d = L.FeatureTopkDesc(q=L.ptr(q), g=L.ptr(g), exclude=L.ptr(exclude) if exclude is not None else None, idx=L.ptr(idx), score=L.ptr(score),
                           scratch=L.ptr(scratch), Nq=Nq, Ng=Ng, C=C_, k=k, metric=TOPK_METRICS[metric], nslabs=nslabs, scratch_words=words)
-    L.check(lib.gvk_feature_topk(C.byref(d), L.stream_ptr()), "gvk_feature_topk")
+    L.launch.gvk_feature_topk(C.byref(d))
     return idx, score
 
 
@@ -1832,8 +1774,7 @@ def knn_vote(idx: torch.Tensor, score: torch.Tensor, labels: torch.Tensor, num_c
         raise L.GavikoHipError(f"knn_vote: temperature = {temperature!r} (must be positive)")
     probs = torch.empty((Nq, K), dtype=torch.float32, device=idx.device)
     pred = torch.empty(Nq, dtype=torch.int32, device=idx.device)
-    L.check(L.load().gvk_knn_vote(L.ptr(idx), L.ptr(score), L.ptr(labels), L.ptr(probs), L.ptr(pred), Nq, labels.numel(), k, K,
-                                  1 if weights == "softmax" else 0, float(temperature), L.stream_ptr()), "gvk_knn_vote")
+    L.launch.gvk_knn_vote(idx, score, labels, probs, pred, Nq, labels.numel(), k, K, 1 if weights == "softmax" else 0, float(temperature))
     return probs, pred
 
 
@@ -1852,5 +1793,5 @@ def class_means(x: torch.Tensor, labels: torch.Tensor, num_classes: int):
         raise L.GavikoHipError(f"class_means: num_classes = {K!r} outside [1, 65535]")
     mean = torch.empty((K, C_), dtype=torch.float32, device=x.device)
     count = torch.empty(K, dtype=torch.int32, device=x.device)
-    L.check(L.load().gvk_class_means(L.ptr(x), L.ptr(labels), L.ptr(mean), L.ptr(count), N, C_, K, L.stream_ptr()), "gvk_class_means")
+    L.launch.gvk_class_means(x, labels, mean, count, N, C_, K)
     return mean, count

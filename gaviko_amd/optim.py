@@ -170,19 +170,18 @@ class FusedAdamOneCycle:
     def step(self) -> None:
         L.require_device()
         tb = self._bind()
-        lib, st = L.load(), L.stream_ptr()
         lr, b1 = self.current()
         self.t += 1
         norm_ptr = None
         if self.max_norm is not None:
-            L.check(lib.gvk_sumsq(L.ptr(tb["flat"]), tb["total"], L.ptr(tb["scratch"]), L.ptr(tb["norm_sq"]), st), "gvk_sumsq")
+            L.launch.gvk_sumsq(tb["flat"], tb["total"], tb["scratch"], tb["norm_sq"])
             norm_ptr = L.ptr(tb["norm_sq"])
         d = L.AdamDesc(ptr_tab=L.ptr(tb["ptr"]), blk_tab=L.ptr(tb["blk"]), grad=L.ptr(tb["flat"]), m=L.ptr(self.m), v=L.ptr(self.v),
                        norm_sq=norm_ptr, nblocks=tb["nblocks"], lr=lr, beta1=b1, beta2=self.beta2, eps=self.eps,
                        # torch.optim.Adam: bias_correction1 = 1 - beta1 ** step with the group's CURRENT beta1 (which OneCycleLR cycles)
                        bias_c1=1.0 - b1 ** self.t, bias_c2=1.0 - self.beta2 ** self.t,
                        max_norm=float(self.max_norm if self.max_norm is not None else 0.0))
-        L.check(lib.gvk_adam_step(C.byref(d), st), "gvk_adam_step")
+        L.launch.gvk_adam_step(C.byref(d))
         if self.model is not None:
             # the kernel writes parameters through raw pointers, so torch's version counters do not move: tell the engine, which keeps
             # bf16 / transposed operand shadows of the backbone weights (`--method fft` trains them)
