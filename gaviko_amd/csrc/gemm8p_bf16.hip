@@ -190,9 +190,10 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs p) {
   __builtin_amdgcn_sched_barrier(0);
 
   // one k-tile.  ST = which of its four phases still have a unit to issue (bit p = phase p); VM0 / VM1 / VM3 = the counted vmcnt
-  // closing the load sections of phases 0 / 1 / 3 (63 = no wait; phase 2's successor reads nothing new).
+  // closing the load sections of phases 0 / 1 / 3 (63 = no wait; phase 2's successor reads nothing new).  SIDE: phase 2's load section requests
+  // the epilogue's side rows (k-tile nt-2: the slot behind the stream's last unit).
   // Unit issued by phase p of k-tile t:  VAR 0: S_{4t+p+6} = u2, u3 of t+1, u0, u1 of t+2;   VAR 1: S_{4t+p+7} = u3 of t+1, u0, u1, u2 of t+2.
-#define GVK_KTILE(T, ST, VM0, VM1, VM3, SB)                                                                      \
+#define GVK_KTILE(T, ST, VM0, VM1, VM3, SB, SIDE)                                                                 \
   {                                                                                                          \
     const int tt_ = (T);                                                                                     \
     const char* base_ = smem + (tt_ & 1) * kBuf;                                                             \
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs p) {
     GVK_VMCNT(VM1);                                                                                          \
     GVK_COMPUTE(0, 1, w1, ((ST) & 2) != 0, 0, tt_ + 2, (SB) < 0 ? -1 : (SB) + 4)                                                       \
     GVK_READ_A(1, base_)                                                                                     \
+    if constexpr (SIDE) pre.issue(p, m0 + 128 * wr, n0 + 64 * wc, l15, lq);                                  \
     if constexpr (VAR == 0 && ((ST) & 4) != 0 && (GVK_ABLATE & 1) == 0) GVK_STAGE(0, tt_ + 2)                                         \
     GVK_COMPUTE(1, 1, w1, ((ST) & 4) != 0, 1, tt_ + 2, (SB) < 0 ? -1 : (SB) + 8)                                                       \
     if constexpr (VAR == 0 && ((ST) & 8) != 0 && (GVK_ABLATE & 1) == 0) GVK_STAGE(1, tt_ + 2)                                         \
@@ -213,6 +215,18 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs p) {
     GVK_COMPUTE(1, 0, w0, ((ST) & 8) != 0, 2, tt_ + 2, (SB) < 0 ? -1 : (SB) + 12)                                                       \
   }
 
+  // The epilogue's residual / GELU' rows (EpiPrefetch, gemm_epilogue.hpp) are requested in k-tile nt-2 behind the last LDS-DMA of the
+  // stream: six phases ahead of the epilogue.  The requests complete behind the units (one in-order queue), so the three counted waits
+  // that follow leave NPRE more in flight.  The wave's whole side tile would take 64 (GELU') / 128 (residual) registers beside the 226 the
+  // loop holds of the 256 that two waves per SIMD have: the first PF row groups go out here -- they cover the round trip the epilogue
+  // used to start with -- and the epilogue requests the rest one row group ahead of its stores, as before.
+#ifdef GVK_STAMPS
+  constexpr int PF = 0;                            // (the probe build borrows p.aux for its stamps)
+#else
+  constexpr int PF = EPI == GVK_EPI_GELU_BWD_BF16 ? 3 : EPI == GVK_EPI_BIAS_RES_F32 ? 1 : 0;
+#endif
+  EpiPrefetch<EPI, 4, PF> pre;
+  constexpr int NPRE = PF > 0 ? EpiPrefetch<EPI, 4, PF>::kLoads : 0;
   const int nt = p.K / BK;                         // >= 2 (checked on the host)
   GVK_STAGE(0, 0) GVK_STAGE(1, 0) GVK_STAGE(2, 0) GVK_STAGE(3, 0)
   GVK_STAGE(0, 1) GVK_STAGE(1, 1)
@@ -228,21 +242,21 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs p) {
   GVK_STAMP(1)
   int t = 0;
 #ifdef GVK_STAMPS
-  for (; t < nt - 3; ++t) GVK_KTILE(t, 15, 8, 8, 8, -1)
+  for (; t < nt - 3; ++t) GVK_KTILE(t, 15, 8, 8, 8, -1, false)
   GVK_STAMP(2)
-  if (nt >= 3) { GVK_KTILE(t, 15, 8, 8, 8, 4) ++t; }   // one steady-state k-tile with a stamp at every barrier: st_[4 .. 19]
+  if (nt >= 3) { GVK_KTILE(t, 15, 8, 8, 8, 4, false) ++t; }   // one steady-state k-tile with a stamp at every barrier: st_[4 .. 19]
   GVK_STAMP(20)
 #else
-  for (; t < nt - 2; ++t) GVK_KTILE(t, 15, 8, 8, 8, -1)
+  for (; t < nt - 2; ++t) GVK_KTILE(t, 15, 8, 8, 8, -1, false)
 #endif
   if constexpr (VAR == 1) {
-    GVK_KTILE(t, 1, 8, 8, 4, -1)                   // k-tile nt-2: one unit of the stream is left (u3 of the last k-tile)
+    GVK_KTILE(t, 1, 8, 8, 4 + NPRE, -1, PF > 0)    // k-tile nt-2: one unit of the stream is left (u3 of the last k-tile)
     ++t;
-    GVK_KTILE(t, 0, 2, 0, 63, -1)                  // k-tile nt-1
+    GVK_KTILE(t, 0, 2 + NPRE, NPRE, 63, -1, false) // k-tile nt-1
   } else {
-    GVK_KTILE(t, 3, 8, 8, 4, -1)                   // k-tile nt-2: the last two units of the stream
+    GVK_KTILE(t, 3, 8, 8, 4 + NPRE, -1, PF > 0)    // k-tile nt-2: the last two units of the stream, then the side rows
     ++t;
-    GVK_KTILE(t, 0, 2, 0, 63, -1)                  // k-tile nt-1
+    GVK_KTILE(t, 0, 2 + NPRE, NPRE, 63, -1, false) // k-tile nt-1
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();       // balance the barrier count
 #undef GVK_KTILE
@@ -263,7 +277,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(GemmArgs p) {
   const bf16* aux_keep = p.aux;
   p.aux = nullptr;
 #endif
-  gemm_epilogue<EPI, false, 8, 4>(p, acc, m0 + 128 * wr, n0 + 64 * wc, l15, lq);
+  gemm_epilogue<EPI, false, 8, 4, PF>(p, acc, m0 + 128 * wr, n0 + 64 * wc, l15, lq, pre);
 #ifdef GVK_STAMPS
   __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0): the epilogue's stores have left
   GVK_STAMP(22)

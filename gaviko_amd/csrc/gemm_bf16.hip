@@ -122,6 +122,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(GemmArgs p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // The epilogue's residual / GELU' tile is requested by the main loop (EpiPrefetch, gemm_epilogue.hpp) in the kernels that run ONE round of
+  // workgroups with three or four stages: there no later tile hides the round trip.  The two-stage loop drains the whole queue at
+  // every barrier (a load carried through it would be waited for at once), a split-K piece does not know whether it will run the epilogue,
+  // and the dropout instantiations are not the product's hot path: those load in the epilogue as before.
+  constexpr int PF = (NS >= 3 && !DROP && !SPLITK && kEpiSideOperand<EPI>) ? MT : 0;
+  EpiPrefetch<EPI, NT, PF> pre;
+  constexpr int NPRE = PF > 0 ? EpiPrefetch<EPI, NT, PF>::kLoads : 0;
+
   int nt = p.K / BK;
   if constexpr (SPLITK) nt = min(p.kt_per, nt - piece * p.kt_per);
   if constexpr (BK == 64) {
@@ -181,22 +189,30 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(GemmArgs p) {
     } else {
     // NS stages: tiles 0..NS-1 are requested up front, tile t+NS as soon as tile t's buffer is free.  A wave's LDS-DMA instructions
     // complete in order, so "tile t+1 has landed" is vmcnt(PER_TILE * #tiles requested after t+1): NS-2 in the steady state.
-    static_assert((NS - 1) * PER_TILE <= 63, "vmcnt is a 6-bit counter");
+    static_assert((NS - 1) * PER_TILE <= 63 && (NS - 2) * PER_TILE + NPRE <= 63, "vmcnt is a 6-bit counter");
 #pragma unroll
     for (int sgi = 0; sgi < NS; ++sgi)
       if (sgi < nt) stage(sgi, sgi);
+    // Fewer k-tiles than stages: every tile is requested already, so the epilogue's side tile follows them here.  It completes behind them
+    // (one in-order queue), so every counted wait from here on leaves NPRE more requests in flight and means what it meant.
+    const bool pre_early = PF > 0 && nt < NS;
+    if (pre_early) pre.issue(p, m0 + wm * WM, n0 + wn * WN, l15, lq);
+#define GVK_VMCNT_(N_) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N_) & 0xF) | (((N_) >> 4) << 14))
     {
       const int ahead = min(nt, NS) - 1;                   // tiles that may still be in flight once tile 0 is in
-      if (ahead >= 3) __builtin_amdgcn_s_waitcnt(0x0F70 | ((3 * PER_TILE) & 0xF) | (((3 * PER_TILE) >> 4) << 14));
-      else if (ahead == 2) __builtin_amdgcn_s_waitcnt(0x0F70 | ((2 * PER_TILE) & 0xF) | (((2 * PER_TILE) >> 4) << 14));
-      else if (ahead == 1) __builtin_amdgcn_s_waitcnt(0x0F70 | (PER_TILE & 0xF) | ((PER_TILE >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      if (ahead >= 3) GVK_VMCNT_(3 * PER_TILE);            // (nt >= NS: nothing was requested early)
+      else if (ahead == 2) { if (pre_early) GVK_VMCNT_(2 * PER_TILE + NPRE); else GVK_VMCNT_(2 * PER_TILE); }
+      else if (ahead == 1) { if (pre_early) GVK_VMCNT_(PER_TILE + NPRE); else GVK_VMCNT_(PER_TILE); }
+      else { if (pre_early) GVK_VMCNT_(NPRE); else GVK_VMCNT_(0); }
     }
+#undef GVK_VMCNT_
     __builtin_amdgcn_s_barrier();
     GVK_LOAD_FRAGS(smem, smem + A_BYTES, 0, xa0, wb0)
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    // AHEAD = tiles requested after tile T+1 when tile T reaches its barrier (a literal: s_waitcnt takes an immediate); LAST: no tile T+1
-#define GVK_TILE3(T, BUF, PREFETCH, AHEAD, LAST)                                                            \
+    // AHEAD = tiles requested after tile T+1 when tile T reaches its barrier (a literal: s_waitcnt takes an immediate); LAST: no tile T+1;
+    // SIDE: request the epilogue's side tile in the slot where tile T+NS's LDS-DMA would go; XV = side requests already behind the tiles
+    // the wait is for (NPRE once the side tile is out, else 0)
+#define GVK_TILE3(T, BUF, PREFETCH, AHEAD, LAST, SIDE, XV)                                                  \
     {                                                                                                       \
       const int buf = (BUF);                                                                                \
       const int nxt = buf == NS - 1 ? 0 : buf + 1;                                                          \
@@ -207,9 +223,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(GemmArgs p) {
       GVK_MMA(xa0, wb0)                                                                                     \
       __builtin_amdgcn_sched_barrier(0);                                                                    \
       /* this wave's share of tile T+1 landed, its reads of tile T done; the barrier extends both to all waves */ \
-      __builtin_amdgcn_s_waitcnt(0x0070 | (((AHEAD) * PER_TILE) & 0xF) | ((((AHEAD) * PER_TILE) >> 4) << 14)); \
+      __builtin_amdgcn_s_waitcnt(0x0070 | (((AHEAD) * PER_TILE + (XV)) & 0xF) | ((((AHEAD) * PER_TILE + (XV)) >> 4) << 14)); \
       __builtin_amdgcn_s_barrier();                                                                         \
       if (PREFETCH) stage(buf, (T) + NS);                                                                   \
+      if constexpr (SIDE) pre.issue(p, m0 + wm * WM, n0 + wn * WN, l15, lq);                                \
       if (!(LAST)) GVK_LOAD_FRAGS(smem + nxt * STAGE, smem + nxt * STAGE + A_BYTES, 0, xa0, wb0)            \
       __builtin_amdgcn_sched_barrier(0);                                                                    \
       GVK_MMA(xa1, wb1)                                                                                     \
@@ -217,17 +234,39 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(GemmArgs p) {
       __builtin_amdgcn_s_waitcnt(0xC07F);                                                                   \
     }
     int t = 0, b = 0;
-    for (; t < nt - NS; ++t) {
-      GVK_TILE3(t, b, true, NS - 2, false)
-      b = b == NS - 1 ? 0 : b + 1;
+    if (PF == 0 || nt >= NS) {
+      for (; t < nt - NS; ++t) {
+        GVK_TILE3(t, b, true, NS - 2, false, false, 0)
+        b = b == NS - 1 ? 0 : b + 1;
+      }
     }
-    for (; t < nt; ++t) {                                  // the last (up to) NS tiles request nothing
-      const int r = nt - 1 - t;                            // tiles left after this one; r - 1 of them may still be in flight
-      if (NS > 3 && r == 3) GVK_TILE3(t, b, false, 2, false)
-      else if (r == 2) GVK_TILE3(t, b, false, 1, false)
-      else if (r == 1) GVK_TILE3(t, b, false, 0, false)
-      else GVK_TILE3(t, b, false, 0, true)
-      b = b == NS - 1 ? 0 : b + 1;
+    if constexpr (PF == 0) {
+      for (; t < nt; ++t) {                                // the last (up to) NS tiles request nothing
+        const int r = nt - 1 - t;                          // tiles left after this one; r - 1 of them may still be in flight
+        if (NS > 3 && r == 3) GVK_TILE3(t, b, false, 2, false, false, 0)
+        else if (r == 2) GVK_TILE3(t, b, false, 1, false, false, 0)
+        else if (r == 1) GVK_TILE3(t, b, false, 0, false, false, 0)
+        else GVK_TILE3(t, b, false, 0, true, false, 0)
+        b = b == NS - 1 ? 0 : b + 1;
+      }
+    } else if (nt >= NS) {
+      // The last NS tiles in straight-line code: the first of them requests the side tile behind the loop's last LDS-DMA, NS - 1 k-tiles
+      // (two L2 round trips) ahead of the epilogue.  No loop around the request: a load whose destination is carried round a back edge makes
+      // the compiler's wait-count pass drain the queue in front of it.
+#define GVK_NEXT_BUF b = b == NS - 1 ? 0 : b + 1; ++t;
+      if constexpr (NS > 3) { GVK_TILE3(t, b, false, 2, false, true, 0) GVK_NEXT_BUF }
+      GVK_TILE3(t, b, false, 1, false, NS == 3, NS == 3 ? 0 : NPRE) GVK_NEXT_BUF
+      GVK_TILE3(t, b, false, 0, false, false, NPRE) GVK_NEXT_BUF
+      GVK_TILE3(t, b, false, 0, true, false, NPRE)
+#undef GVK_NEXT_BUF
+    } else {
+      for (; t < nt; ++t) {                                // fewer k-tiles than stages: the side tile went out in front of the loop
+        const int r = nt - 1 - t;
+        if (r == 2) GVK_TILE3(t, b, false, 1, false, false, NPRE)
+        else if (r == 1) GVK_TILE3(t, b, false, 0, false, false, NPRE)
+        else GVK_TILE3(t, b, false, 0, true, false, NPRE)
+        b = b == NS - 1 ? 0 : b + 1;
+      }
     }
 #undef GVK_TILE3
     }
@@ -282,7 +321,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(GemmArgs p) {
       }
     }
   }
-  gemm_epilogue<EPI, DROP, MT, NT>(p, acc, m0 + wm * WM, n0 + wn * WN, l15, lq);
+  gemm_epilogue<EPI, DROP, MT, NT, PF>(p, acc, m0 + wm * WM, n0 + wn * WN, l15, lq, pre);
 }
 
 template <int BM, int BN, int EPI, bool DROP = false, int NS = 2, int NW = 4, bool SPLITK = false>

@@ -53,12 +53,64 @@ __device__ __forceinline__ int swz_a128(int row) { return (row >> 1) & 7; }
 // so those 16 rows again hit 16 distinct (parity, slot) pairs.
 __device__ __forceinline__ int swz_w(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }
 
+// Side operand of the epilogues that read one per output element: the fp32 residual (BIAS_RES_F32, BIAS_RES_F32_BF16) or the bf16
+// GELU' / pre-activation tile (GELU_BWD_BF16).  Its addresses are known at kernel entry, so the main loops request the first PF row groups
+// of the wave's tile behind their last LDS-DMA and the epilogue finds them in registers instead of starting an L2 / HBM round trip when the
+// k loop has drained.  (Issued by 200 workgroups at the same moment with nothing left to overlap, that trip was the difference between
+// the out-projection forward and its dgrad, same loop: 19.3 vs 16.6 us.)
+template <int EPI>
+constexpr bool kEpiSideOperand = EPI == GVK_EPI_BIAS_RES_F32 || EPI == GVK_EPI_BIAS_RES_F32_BF16 || EPI == GVK_EPI_GELU_BWD_BF16;
+
+template <int EPI, int NT, int PF>
+struct EpiPrefetch {
+  static constexpr int NP = NT / 2;
+  static constexpr bool kRes = EPI == GVK_EPI_BIAS_RES_F32 || EPI == GVK_EPI_BIAS_RES_F32_BF16;
+  static constexpr bool kStat = EPI == GVK_EPI_BIAS_RES_F32_BF16;
+  static constexpr int kLoads = PF * (NP * (kRes ? 2 : 1) + (kStat ? 1 : 0));    // vector-memory instructions per wave: what the loops' counted vmcnt waits add
+  u32x4 q[PF > 0 ? PF : 1][NP][2];                           // [row group][column pair][kRes: the two 16-byte halves of eight floats]
+  float pv[PF > 0 ? PF : 1];                                 // kStat: the row's pivot (0 without stat_pivot: an empty range)
+
+  // Exactly the elements the epilogue consumes: row group i of the wave's tile = rows mbase + 16 i + l15, eight columns at nbase + 32 jp + 8 lq.
+  // The loads are BUFFER loads whose range is the live part of the wave's tile: rows mbase .. min(M, mbase + 16 PF) - 1.  A lane whose row is
+  // past M is out of range, which the hardware answers with zeros WITHOUT forming the address -- the epilogue's `m < p.M` as a range check
+  // (columns need none: N is a multiple of the tile's columns).  Unlike a branch around the loads this issues the same kLoads instructions
+  // in every wave, whatever M is: the counted waits of the main loop depend on that.
+  // In place (res == out0, the engine's residual stream): a workgroup reads only the tile it alone later writes, and writes it only in its
+  // epilogue, so the earlier read sees the same bytes the epilogue's own load saw.
+  __device__ __forceinline__ void issue(const GemmArgs& p, const int mbase, const int nbase, const int l15, const int lq) {
+    if constexpr (PF > 0) {
+      constexpr int ES = kRes ? 4 : 2;                       // bytes per element
+      const int ld = kRes ? p.ldres : p.ldaux;
+      const int live = __builtin_amdgcn_readfirstlane(min(p.M - mbase, 16 * PF));
+      const char* base = (kRes ? (const char*)p.res : (const char*)p.aux) + ((size_t)mbase * ld + nbase) * ES;
+      const unsigned bytes = live > 0 ? (unsigned)(((live - 1) * ld + 16 * NT) * ES) : 0u;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < PF; ++i)
+#pragma unroll
+        for (int jp = 0; jp < NP; ++jp) {
+          const int off = ((i * 16 + l15) * ld + 32 * jp + 8 * lq) * ES;
+          q[i][jp][0] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+          if constexpr (kRes) q[i][jp][1] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0);
+        }
+      if constexpr (kStat) {
+        const __amdgpu_buffer_rsrc_t rp =
+            __builtin_amdgcn_make_buffer_rsrc((void*)(p.stat_pivot + mbase), 0, (p.stat_pivot != nullptr && live > 0) ? (unsigned)live * 4u : 0u, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < PF; ++i) pv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, (i * 16 + l15) * 4, 0, 0));
+      }
+    }
+  }
+};
+
 // Epilogue of one wave: acc[i][j] is the 16x16 tile at rows mbase + 16 i, columns nbase + 32 (j >> 1) (+ the interleave above).
 // Loads and stores retire through ONE in-order counter (vmcnt), so a side load issued behind the previous row's stores would wait for
 // them: the column-only bias is fetched once, and the per-row operands (residual / GELU' input / position rows) of row i+1 are requested
-// before row i is stored.
-template <int EPI, bool DROP, int MT, int NT>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[MT][NT], const int mbase, const int nbase, const int l15, const int lq) {
+// before row i is stored.  Row groups i < PF come from `pre` (requested by the main loop, EpiPrefetch above), the others are loaded here.
+template <int EPI, bool DROP, int MT, int NT, int PF = 0>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[MT][NT], const int mbase, const int nbase, const int l15, const int lq,
+                                              const EpiPrefetch<EPI, NT, PF>& pre = EpiPrefetch<EPI, NT, PF>{}) {
+  static_assert(PF == 0 || (kEpiSideOperand<EPI> && PF <= MT), "prefetched row groups: side-operand epilogues only");
   static_assert(NT % 2 == 0, "tile pairs");
   constexpr int NP = NT / 2;
   constexpr bool kRes = EPI == GVK_EPI_BIAS_RES_F32 || EPI == GVK_EPI_BIAS_RES_F32_BF16;
@@ -109,10 +161,26 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[MT
     }
   };
   Side cur, nxt;
-  fetch(0, cur);
+  if constexpr (PF == 0) fetch(0, cur);
+  // Bias and prefetched rows are waited for HERE, once and outside the `m < p.M` branches: left to the compiler the wait lands inside every
+  // row's branch and, merged with the path around it, becomes a vmcnt(0) that also waits for the previous row's stores.  With nothing but
+  // stores outstanding the prefetched rows leave back to back.
+  else __builtin_amdgcn_s_waitcnt(0x0F70);
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    if (i + 1 < MT) fetch(i + 1, nxt);
+    if (i + 1 < MT && i + 1 >= PF) fetch(i + 1, nxt);
+    if (i < PF) {                                            // the same bits the loads above would have brought
+      if constexpr (kStat) cur.pv = pre.pv[i];
+#pragma unroll
+      for (int jp = 0; jp < NP; ++jp) {
+        if constexpr (kRes) {
+          cur.r0[jp] = __builtin_bit_cast(f32x4, pre.q[i][jp][0]);
+          cur.r1[jp] = __builtin_bit_cast(f32x4, pre.q[i][jp][1]);
+        } else if constexpr (kAux) {
+          cur.a8[jp] = __builtin_bit_cast(bf16x8, pre.q[i][jp][0]);
+        }
+      }
+    }
     const int m = mbase + i * 16 + l15;
     [[maybe_unused]] float ps1 = 0.f, ps2 = 0.f;             // kStat: this lane's share of the row's (sum, sum of squares)
     if (m < p.M) {
