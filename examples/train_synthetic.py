@@ -9,7 +9,10 @@
     validation: accuracy / quadratic kappa / macro OvR AUC                           gaviko_amd.metrics       (eval.py:103-122)
     best-model checkpoint with the trainable tensors only                            gaviko_amd.utils         (train.py:460-485)
 
-usage: python examples/train_synthetic.py [--method gaviko] [--backbone vit-t16] [--epochs 3] [--samples 8] [--out /tmp/gaviko_run]"""
+With --ragged the volumes have shapes and spacings of their own (VolumeDataset + collate_ragged) and data.Conform brings each batch onto
+the (120,160,160) grid on the device (Resample to 1 mm, CropOrPad) before the transforms above.
+
+usage: python examples/train_synthetic.py [--ragged] [--method gaviko] [--backbone vit-t16] [--epochs 3] [--samples 8] [--out /tmp/gaviko_run]"""
 import argparse
 import os
 import sys
@@ -24,8 +27,9 @@ from gaviko_amd.registry import build_model  # noqa: E402
 from gaviko_amd.utils import load_pretrained  # noqa: E402
 
 
-def make_dataset(root, n, num_classes, seed=0):
-    """n synthetic (120,160,160) volumes per subset whose class shows in a coarse intensity pattern; CSV with the reference's columns."""
+def make_dataset(root, n, num_classes, seed=0, ragged=False):
+    """n synthetic (120,160,160) volumes per subset whose class shows in a coarse intensity pattern; CSV with the reference's columns.
+    ragged: every volume gets a shape of its own around (130, 170, 170) and a spacing around (0.9, 0.95, 0.95), stored under 'spacing'."""
     import pandas as pd
     os.makedirs(root, exist_ok=True)
     rng = np.random.default_rng(seed)
@@ -33,10 +37,12 @@ def make_dataset(root, n, num_classes, seed=0):
     for subset, count in (("train", n), ("val", max(num_classes, n // 2)), ("test", max(num_classes, n // 2))):
         for i in range(count):
             k = i % num_classes
-            v = rng.standard_normal((120, 160, 160)).astype(np.float32) * 40 + 500
-            v[k * 20:(k + 1) * 20] += 400.0                              # a bright slab whose depth position is the label
+            shape = tuple(int(s) for s in rng.integers((110, 150, 150), (150, 190, 190))) if ragged else (120, 160, 160)
+            v = rng.standard_normal(shape).astype(np.float32) * 40 + 500
+            v[k * shape[0] // 6:(k + 1) * shape[0] // 6] += 400.0        # a bright slab whose depth position is the label
             name = f"{subset}_{i}.npz"
-            np.savez(os.path.join(root, name), data=v)
+            extra = dict(spacing=np.array([120.0, 160.0, 160.0]) / shape * rng.uniform(0.97, 1.03, 3)) if ragged else {}
+            np.savez(os.path.join(root, name), data=v, **extra)
             rows.append(dict(mri_path=name, kl_grade=k, subset=subset))
     csv = os.path.join(root, "data.csv")
     pd.DataFrame(rows).to_csv(csv, index=False)
@@ -44,14 +50,16 @@ def make_dataset(root, n, num_classes, seed=0):
 
 
 def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False,
-        motion_augment=False, batch_mix=False):
+        motion_augment=False, batch_mix=False, ragged=False):
     dev = torch.device("cuda:0")
     K = 5
-    csv = make_dataset(os.path.join(out, "data"), samples, K, seed)
+    csv = make_dataset(os.path.join(out, "data"), samples, K, seed, ragged)
     config = {"data": dict(data_path=csv, image_folder=os.path.join(out, "data"), batch_size=batch_size, num_workers=0,
                            intensity_augment=intensity_augment,          # train.py:43-51: the OneOf(intensity_augment) stage, on the device
                            motion_augment=motion_augment,                # ... with tio.RandomMotion as its fourth member (needs the stage)
-                           **({"batch_mix": dict(seed=seed)} if batch_mix else {})),   # Mixup / CutMix of the batch, timm's defaults
+                           **({"batch_mix": dict(seed=seed)} if batch_mix else {}),    # Mixup / CutMix of the batch, timm's defaults
+                           # raw scans of any shape and spacing: resampled to 1 mm, cropped / padded onto the model's grid, on the device
+                           **({"conform": dict(target_shape=(120, 160, 160), spacing=1.0, padding_mode="minimum")} if ragged else {})),
               "model": dict(method=method, backbone=backbone, image_size=160, image_patch_size=16, frames=120, frame_patch_size=12, num_classes=K,
                             channels=1, pool="cls", dim_head=64, dropout=0.1, emb_dropout=0.1, freeze_vit=True, num_prompts=8, prompt_dim=64,
                             prompt_dropout=0.1, deep_prompt=method == "deep_vpt", prompt_latent_dim=20, local_dim=20, local_k=(6, 6, 6),
@@ -69,11 +77,12 @@ def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gavi
     opt = FusedAdamOneCycle(model, lr=lr, eps=1e-8, max_norm=1.0, max_lr=lr, total_steps=total_steps, pct_start=0.3, div_factor=10,
                             final_div_factor=1000)
     history, best_acc, best_path = [], -1.0, None
+    to_grid = (lambda batch: pre.conform(batch.to(dev, non_blocking=True))) if pre.conform is not None else (lambda batch: batch.to(dev, non_blocking=True))
     for epoch in range(epochs):
         model.train()
         meter.reset()
         for inputs, labels in train_loader:
-            inputs, target = pre.train_transforms(inputs.to(dev, non_blocking=True)), labels.to(dev)
+            inputs, target = pre.train_transforms(to_grid(inputs)), labels.to(dev)
             if pre.batch_mix is not None:                                 # after the normaliser; the target becomes a data.MixedTarget
                 inputs, target = pre.batch_mix(inputs, target)
             loss = criterion(model(inputs), target)
@@ -85,7 +94,7 @@ def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gavi
         ev = metrics.Evaluator(K, dev)
         with torch.no_grad():
             for inputs, labels in val_loader:
-                ev.update(model(pre.val_transforms(inputs.to(dev))), labels.to(dev))
+                ev.update(model(pre.val_transforms(to_grid(inputs))), labels.to(dev))
         r = ev.compute()
         history.append(dict(epoch=epoch, train_loss=train_loss, train_acc=train_acc, val_acc=r["accuracy"], val_kappa=r["quadratic_kappa"], val_auc=r["auc"]))
         log(f"epoch {epoch}: train loss {train_loss:.4f} acc {train_acc:.3f} | val acc {r['accuracy']:.3f} kappa {r['quadratic_kappa']:.3f} auc {r['auc']}")
@@ -107,8 +116,9 @@ if __name__ == "__main__":
     ap.add_argument("--intensity-augment", action="store_true", help="add noise / bias field / blur (one of, p=0.75) to the train transforms")
     ap.add_argument("--motion-augment", action="store_true", help="with --intensity-augment: add k-space motion as the fourth member of that group")
     ap.add_argument("--batch-mix", action="store_true", help="Mixup / CutMix of each training batch (data.BatchMix, timm's defaults) with the mixed-target loss")
+    ap.add_argument("--ragged", action="store_true", help="synthetic volumes of unequal shape and spacing, brought onto the grid by data.Conform")
     a = ap.parse_args()
     res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment,
-              batch_mix=a.batch_mix)
+              batch_mix=a.batch_mix, ragged=a.ragged)
     print("checkpoint:", res["checkpoint"])
     print("results   :", res["results_csv"])

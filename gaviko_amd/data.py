@@ -53,9 +53,18 @@ are pinned against the literal np.fft algorithms and float64 restatements (`test
 CutMix of the normalised batch in one streaming launch (`csrc/batchmix.hip`), with the mixed target returned as the pair `MixedTarget` that
 the fused losses take (`losses.py`, `gvk_loss_mixed_fwd_bwd`).  It has its own random stream, so DeviceCompose's is untouched; partners come
 from a permutation, not timm's flipped batch.  The kernel is pinned against a float64 restatement (`tests/batchmix_ref.py`).
+
+Everything above starts from a batch that is already on the model's grid; the reference's data set was resampled offline.  `Conform` is
+torchio's first stage for scans that are not: `Resample` to a spacing or `Resize`, then `CropOrPad`, on a `RaggedBatch` of volumes of unequal
+shape and spacing (`VolumeDataset`, `collate_ragged`), as up to three streaming passes over the packed buffer (`csrc/conform.hip`).  The classes
+keep torchio's names and arguments; the geometry (edge-aligned positions, Cardoso et al.'s antialiasing sigma, centred crop / pad) is this
+module's own definition, on the array axes and in the samples' own spacing units, with no orientation or affine handling.  Parity vs torchio /
+SimpleITK is UNPINNED; the tables are pinned against F.interpolate and scipy.ndimage.gaussian_filter1d, the kernels against a float64
+restatement (`tests/conform_ref.py`).
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import NamedTuple, Optional, Sequence
@@ -103,6 +112,89 @@ class CustomDatasetPrediction(CustomDataset):
 
     def __getitem__(self, index):
         return self._volume(index)
+
+
+class VolumeDataset(Dataset):
+    """The CSV columns of `CustomDataset`, for scans that are NOT on the model's grid yet: returns (volume, spacing, label) with the raw
+    float32 volume (1, D, H, W) of whatever shape the file holds and spacing float64 [3] = npz[spacing_key] in array-axis order, (1, 1, 1)
+    where the file has no such key.  Batches of it are built by `collate_ragged` and brought onto the grid by `Conform`."""
+
+    def __init__(self, dataframe, image_folder=None, spacing_key: str = "spacing"):
+        self.df, self.image_folder, self.spacing_key = dataframe, image_folder, spacing_key
+
+    def _path(self, index):
+        p = self.df.loc[index]["mri_path"]
+        return p if not self.image_folder else os.path.join(self.image_folder, p)
+
+    def _volume(self, index):
+        with np.load(self._path(index)) as npz:
+            vol = np.ascontiguousarray(npz["data"], dtype=np.float32)
+            spacing = np.asarray(npz[self.spacing_key], dtype=np.float64).reshape(-1) if self.spacing_key in npz.files else np.ones(3)
+        if vol.ndim != 3 or spacing.shape != (3,) or not (spacing > 0).all():
+            raise ValueError(f"{self._path(index)}: a (D, H, W) volume and three positive spacings expected, got {vol.shape} and {spacing}")
+        return torch.from_numpy(vol[None]), torch.from_numpy(spacing)
+
+    def __getitem__(self, index):
+        return (*self._volume(index), self.df.loc[index]["kl_grade"])
+
+    def __len__(self):
+        return len(self.df)
+
+
+class VolumeDatasetPrediction(VolumeDataset):
+    """`VolumeDataset` without the label: (volume, spacing)."""
+
+    def __getitem__(self, index):
+        return self._volume(index)
+
+
+class RaggedBatch(NamedTuple):
+    """A batch of volumes of unequal shape, packed: data float32 [total] holds every volume's voxels in [D][H][W] order one after another,
+    sample b at elements offsets[b] .. offsets[b] + prod(shapes[b]); offsets int64 [B + 1], shapes int32 [B][3], spacing float64 [B][3] (array-axis
+    order).  Only `data` ever goes to the device: offsets, shapes and spacing are what the host builds the tables of `Conform` from, and they
+    stay where the host can read them without waiting for the GPU.  len() is B."""
+    data: torch.Tensor
+    offsets: torch.Tensor
+    shapes: torch.Tensor
+    spacing: torch.Tensor
+
+    def __len__(self):
+        return int(self.shapes.shape[0])
+
+    def to(self, device, non_blocking: bool = False):
+        return RaggedBatch(self.data.to(device, non_blocking=non_blocking), self.offsets, self.shapes, self.spacing)
+
+    def pin_memory(self):
+        return RaggedBatch(self.data.pin_memory(), self.offsets, self.shapes, self.spacing)
+
+    def volume(self, b: int) -> torch.Tensor:
+        """Sample b as a [D][H][W] view of the packed buffer."""
+        o, s = int(self.offsets[b]), [int(v) for v in self.shapes[b]]
+        return self.data[o:o + s[0] * s[1] * s[2]].view(*s)
+
+
+RAGGED_ALIGN = 4          # collate_ragged starts every sample at a multiple of 4 elements (16 bytes); the kernels do not rely on it
+
+
+def collate_ragged(samples):
+    """`collate_fn` for `VolumeDataset`: samples (volume, spacing, label) -> (RaggedBatch, labels), samples (volume, spacing) -> RaggedBatch.
+    A volume is (1, D, H, W) or (D, H, W), a tensor or an array."""
+    vols = [torch.as_tensor(s[0], dtype=torch.float32) for s in samples]
+    vols = [v[0] if v.dim() == 4 and v.shape[0] == 1 else v for v in vols]
+    if any(v.dim() != 3 or v.numel() == 0 for v in vols):
+        raise ValueError(f"collate_ragged: volumes are (1, D, H, W) or (D, H, W), got {[tuple(v.shape) for v in vols]}")
+    offsets, end = [], 0
+    for v in vols:
+        offsets.append(-(-end // RAGGED_ALIGN) * RAGGED_ALIGN)
+        end = offsets[-1] + v.numel()
+    data = torch.zeros(end, dtype=torch.float32)
+    for o, v in zip(offsets, vols):
+        data[o:o + v.numel()] = v.reshape(-1)
+    batch = RaggedBatch(data, torch.tensor(offsets + [end], dtype=torch.int64), torch.tensor([list(v.shape) for v in vols], dtype=torch.int32),
+                        torch.stack([torch.as_tensor(s[1], dtype=torch.float64).reshape(3) for s in samples]))
+    if len(samples[0]) == 2:
+        return batch
+    return batch, torch.as_tensor(np.asarray([s[2] for s in samples]))
 
 
 # ---- device transforms ----------------------------------------------------------------------------------------------------------
@@ -881,6 +973,219 @@ class DeviceCompose:
         return x
 
 
+# ---- geometry: torchio's first stage (Resample / Resize / CropOrPad) for a ragged batch ---------------------------------------------------
+# Per sample and array axis, with input length n, input spacing s and target length N (this module's own definitions; parity with torchio
+# / SimpleITK is unpinned, module docstring):
+#   Resample to spacing t: r = t / s, intermediate length m = max(1, floor(n / r + 1e-9)); Resize to N: r = n / N, m = N.  Intermediate index
+#     u reads the input position p = (u + 0.5) r - 0.5 (edges aligned).
+#   linear: p clamped to [0, n - 1], taps floor(p) and min(floor(p) + 1, n - 1) with weights 1 - g and g (F.interpolate, align_corners=False,
+#     no antialiasing); nearest: the tap min(floor(p + 0.5), n - 1) ('nearest-exact'; antialias is ignored).
+#   antialias, linear, r > 1: the axis is first smoothed by a Gaussian of sigma = sqrt((r^2 - 1) / (8 ln 2)) voxels (Cardoso et al.), truncated
+#     at int(4 sigma + 0.5), normalised, the edge value repeated (scipy.ndimage.gaussian_filter1d(mode='nearest')).  Filter and interpolation are
+#     linear maps along one axis: they are composed into one banded row of at most 2 radius + 2 taps.
+#   CropOrPad from m to N, d = N - m: padding puts ceil(d / 2) voxels in front and floor(d / 2) behind, cropping removes ceil(-d / 2) in front
+#     and floor(-d / 2) behind; output index q is intermediate index u = q - c, c the signed front pad, and a voxel with u outside [0, m) on
+#     any axis is the pad value.
+def _positive_triple(v, name, kind):
+    t = _triple(v, name, kind)
+    if any(not x > 0 for x in t):
+        raise ValueError(f"{name}: positive values, not {v!r}")
+    return t
+
+
+def _interpolation(v, name):
+    if v not in ("nearest", "linear"):
+        raise NotImplementedError(f"{name}: image_interpolation 'nearest' and 'linear' are built, not {v!r}")
+    return v
+
+
+class CropOrPad:
+    """tio.CropOrPad(target_shape, padding_mode=0): centred crop and / or pad to target_shape (a number or one length per array axis).
+    padding_mode is a number or 'minimum' (the sample's own input minimum, taken on the device)."""
+
+    def __init__(self, target_shape, padding_mode=0, mask_name=None, labels=None):
+        if mask_name is not None or labels is not None:
+            raise NotImplementedError("CropOrPad: target_shape and padding_mode (a number or 'minimum') are built; mask_name and labels are not")
+        if isinstance(padding_mode, str) and padding_mode != "minimum" or isinstance(padding_mode, bool) or \
+                not isinstance(padding_mode, (str, int, float, np.integer, np.floating)):
+            raise NotImplementedError(f"CropOrPad: padding_mode is a number or 'minimum'; {padding_mode!r} is not built")
+        if not isinstance(padding_mode, str) and not math.isfinite(padding_mode):
+            raise ValueError("CropOrPad: a finite pad value")
+        self.target_shape = _positive_triple(target_shape, "CropOrPad target_shape", int)
+        self.padding_mode = padding_mode if isinstance(padding_mode, str) else float(padding_mode)
+
+
+class Resize:
+    """tio.Resize(target_shape, image_interpolation='linear'): every sample is resampled to target_shape whatever its spacing.  antialias
+    (not torchio's: it resizes without) smooths an axis that shrinks as `Resample` does."""
+
+    def __init__(self, target_shape, image_interpolation: str = "linear", antialias: bool = True):
+        self.target_shape = _positive_triple(target_shape, "Resize target_shape", int)
+        self.image_interpolation, self.antialias = _interpolation(image_interpolation, "Resize"), bool(antialias)
+
+
+class Resample:
+    """tio.Resample(target=1, image_interpolation='linear', antialias): every sample is resampled to the spacing `target` (a number or one
+    spacing per array axis, in the units of the samples' own spacing).  A reference image or path as target is not built."""
+
+    def __init__(self, target=1.0, image_interpolation: str = "linear", antialias: bool = True):
+        if isinstance(target, (str, bytes, os.PathLike)) or isinstance(target, bool) or \
+                not isinstance(target, (int, float, np.integer, np.floating, tuple, list, np.ndarray)):
+            raise NotImplementedError(f"Resample: target is a spacing (a number or one per array axis); {target!r} (a reference image or path) is not built")
+        self.target = _positive_triple(target.tolist() if isinstance(target, np.ndarray) else target, "Resample target", float)
+        self.image_interpolation, self.antialias = _interpolation(image_interpolation, "Resample"), bool(antialias)
+
+
+def _conform_stages(transforms):
+    """(the one Resample or Resize or None, the one CropOrPad or None, target_shape) of a Conform's transforms."""
+    transforms = list(transforms)
+    res = [t for t in transforms if isinstance(t, (Resample, Resize))]
+    crop = [t for t in transforms if isinstance(t, CropOrPad)]
+    if len(res) + len(crop) != len(transforms) or len(res) > 1 or len(crop) > 1 or not transforms or (res and crop and transforms[0] is crop[0]):
+        raise NotImplementedError("Conform: at most one Resample or Resize, followed by at most one CropOrPad, is built")
+    if not crop and isinstance(res[0], Resample):
+        raise ValueError("Conform: a Resample alone gives every sample its own output shape; follow it with a CropOrPad")
+    return (res[0] if res else None), (crop[0] if crop else None), (crop[0] if crop else res[0]).target_shape
+
+
+def _conform_axis(n: int, r: float, m: int, N: int, interpolation: str, antialias: bool):
+    """One axis of one sample, all in float64: (start int64 [N], rows [N][K], inside bool [N], c).  Row q of the composed map (Gaussian,
+    interpolation, crop / pad) reads the inputs start[q] .. start[q] + K - 1; K is the widest band of the axis and start[q] + K <= n."""
+    u = np.arange(m)
+    p = (u + 0.5) * r - 0.5
+    A = np.zeros((m, n), dtype=np.float64)
+    if interpolation == "nearest":
+        A[u, np.clip(np.floor(p + 0.5).astype(np.int64), 0, n - 1)] = 1.0
+    else:
+        p = np.clip(p, 0.0, float(n - 1))
+        i0 = np.floor(p).astype(np.int64)
+        g = p - i0
+        np.add.at(A, (u, i0), 1.0 - g)
+        np.add.at(A, (u, np.minimum(i0 + 1, n - 1)), g)
+        if antialias and r > 1.0:
+            sigma = math.sqrt((r * r - 1.0) / (8.0 * math.log(2.0)))
+            radius = int(4.0 * sigma + 0.5)
+            k = np.arange(-radius, radius + 1, dtype=np.float64)
+            w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+            w /= w.sum()
+            G, j = np.zeros((n, n), dtype=np.float64), np.arange(n)
+            for kk, wk in zip(range(-radius, radius + 1), w):
+                np.add.at(G, (j, np.clip(j + kk, 0, n - 1)), wk)
+            A = A @ G
+    nz = A != 0.0
+    first, last = nz.argmax(axis=1), n - 1 - nz[:, ::-1].argmax(axis=1)
+    K = int((last - first + 1).max())
+    first = np.minimum(first, n - K)
+    rows_m = A[u[:, None], first[:, None] + np.arange(K)[None, :]]
+    d = N - m
+    c = -(-d // 2) if d >= 0 else -((1 - d) // 2)                     # the signed front pad: ceil(d / 2), or minus ceil(-d / 2)
+    uu = np.arange(N) - c
+    inside = (uu >= 0) & (uu < m)
+    uu = np.clip(uu, 0, m - 1)
+    return np.where(inside, first[uu], 0), np.where(inside[:, None], rows_m[uu], 0.0), inside, c
+
+
+class ConformTables(NamedTuple):
+    """The host tables of one `Conform` call, the three axes concatenated at offsets 0, D, D + H: start int32 [B][D + H + W], weights float32
+    [B][D + H + W][T] (T = the largest band of the batch), inside bool [B][D + H + W], taps int32 [B][3] (each sample's own band per axis),
+    geometry float64 [B][3][2] = (r, c) per sample and axis."""
+    start: np.ndarray
+    weights: np.ndarray
+    inside: np.ndarray
+    taps: np.ndarray
+    geometry: np.ndarray
+
+    def axis(self, b: int, a: int, target_shape):
+        """(start [N], weights [N][T], inside [N]) of sample b along axis a."""
+        off = int(sum(target_shape[:a]))
+        rows = slice(off, off + int(target_shape[a]))
+        return self.start[b, rows], self.weights[b, rows], self.inside[b, rows]
+
+
+_conform_axis_cached = functools.lru_cache(maxsize=1024)(_conform_axis)      # scans of one protocol repeat their shapes
+
+
+def conform_tables(shapes, spacing, transforms, target_shape, dtype=np.float32) -> ConformTables:
+    """The banded tables (section comment above) that bring samples of `shapes` [B][3] and `spacing` [B][3] onto target_shape through
+    `transforms` (what `Conform` takes).  Float64 throughout, the weights rounded to float32 once (dtype=np.float64 keeps them unrounded: tests).  A pure crop, pad or identity yields one tap
+    of weight exactly 1.  A band wider than ops.CONFORM_MAX_TAPS = 16 (antialiasing at a factor above about 4.5) is refused."""
+    res, crop, want = _conform_stages(transforms)
+    N = tuple(int(v) for v in target_shape)
+    if N != tuple(want):
+        raise ValueError(f"conform_tables: the transforms end on {tuple(want)}, not on target_shape {N}")
+    shapes = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
+    spacing = np.asarray(spacing, dtype=np.float64).reshape(-1, 3)
+    if len(shapes) != len(spacing) or len(shapes) < 1 or (shapes < 1).any() or not (spacing > 0).all():
+        raise ValueError("conform_tables: shapes [B][3] of positive lengths and spacing [B][3] of positive spacings expected")
+    B, S = len(shapes), sum(N)
+    per, geometry, taps = [], np.zeros((B, 3, 2), dtype=np.float64), np.ones((B, 3), dtype=np.int32)
+    for b in range(B):
+        for a in range(3):
+            n = int(shapes[b, a])
+            if isinstance(res, Resample):
+                r = res.target[a] / float(spacing[b, a])
+                m = max(1, int(math.floor(n / r + 1e-9)))
+            elif isinstance(res, Resize):
+                r, m = n / float(res.target_shape[a]), res.target_shape[a]
+            else:
+                r, m = 1.0, n
+            interp, anti = (res.image_interpolation, res.antialias) if res is not None else ("nearest", False)
+            start, rows, inside, c = _conform_axis_cached(n, r, m, N[a] if crop is not None else m, interp, anti)
+            if rows.shape[1] > ops.CONFORM_MAX_TAPS:
+                raise ValueError(f"conform_tables: sample {b}, axis {a}: antialiased resampling by the factor {r:.4g} needs {rows.shape[1]} taps; "
+                                 f"at most {ops.CONFORM_MAX_TAPS} are built (factors up to about 4.5)")
+            per.append((start, rows, inside))
+            geometry[b, a], taps[b, a] = (r, c), rows.shape[1]
+    T = int(taps.max())
+    start, weights, inside = np.zeros((B, S), np.int32), np.zeros((B, S, T), dtype), np.zeros((B, S), bool)
+    off = np.concatenate([[0], np.cumsum(N)])
+    for b in range(B):
+        for a in range(3):
+            s, w, i = per[b * 3 + a]
+            rows = slice(off[a], off[a + 1])
+            start[b, rows], weights[b, rows, :w.shape[1]], inside[b, rows] = s, w, i
+    return ConformTables(start, weights, inside, taps, geometry)
+
+
+class Conform:
+    """Raw volumes of any shape and spacing onto the model's grid, on the device, in one call: `x = conform(ragged.to(device))` gives float32
+    [B, 1, D, H, W] for a `RaggedBatch`.  transforms: at most one `Resample` or `Resize`, followed by at most one `CropOrPad` (a Resample alone
+    is refused: its output shape would differ per sample).  The host builds one banded table per sample and axis (`conform_tables`); the
+    device gathers and contracts (`ops.conform_volumes`, csrc/conform.hip).  An axis that is only cropped, padded or already conforming, and
+    every axis under 'nearest', moves bits.  `last_geometry` float64 [B][3][2] holds (r, c) of the last call per sample and axis: output index q
+    sits at the input position (q - c + 0.5) r - 0.5 of the scan's own grid."""
+
+    def __init__(self, transforms: Sequence):
+        self.transforms = list(transforms)
+        self.resample, self.crop, self.target_shape = _conform_stages(self.transforms)
+        self.last_geometry = None
+
+    def __call__(self, ragged: RaggedBatch) -> torch.Tensor:
+        if not ragged.data.is_cuda:
+            raise RuntimeError("Conform runs on the GPU: move the batch first, ragged.to(device) (there is no CPU path)")
+        shapes, offsets = ragged.shapes.cpu().numpy(), ragged.offsets.cpu().numpy()
+        t = conform_tables(shapes, ragged.spacing.cpu().numpy(), self.transforms, self.target_shape)
+        self.last_geometry = t.geometry
+        mode = self.crop.padding_mode if self.crop is not None else 0.0
+        partials = None
+        if mode == "minimum" and not t.inside.all():                      # the pad value = the sample's own minimum, never read here
+            partials = ops.ragged_minmax(ragged.data, offsets, shapes)
+        out = ops.conform_volumes(ragged.data, offsets, shapes, t.start, t.weights, t.inside, t.taps, self.target_shape,
+                                  pad_value=0.0 if mode == "minimum" else mode, partials=partials)
+        return out.unsqueeze(1)
+
+
+def conform_from_config(c) -> Conform:
+    """config['data']['conform']: target_shape, one of spacing (-> Resample) / resize (-> Resize) or neither, and optionally
+    image_interpolation, antialias, padding_mode."""
+    known = {"target_shape", "spacing", "resize", "image_interpolation", "antialias", "padding_mode", "spacing_key"}
+    if "target_shape" not in c or set(c) - known or ("spacing" in c and "resize" in c):
+        raise ValueError(f"config['data']['conform']: target_shape and at most one of spacing / resize, with the options {sorted(known)}; got {sorted(c)}")
+    opts = dict(image_interpolation=c.get("image_interpolation", "linear"), antialias=c.get("antialias", True))
+    stages = [Resample(c["spacing"], **opts)] if "spacing" in c else [Resize(c["resize"], **opts)] if "resize" in c else []
+    return Conform(stages + [CropOrPad(c["target_shape"], c.get("padding_mode", 0))])
+
+
 class MixedTarget(NamedTuple):
     """The target of a mixed batch, kept as the pair it came from: row i is class a[i] with weight lam[i] and class b[i] with 1 - lam[i].
     a, b int64 [B], lam float32 [B], device tensors.  The fused losses take it as `target` (losses._FusedLoss.forward)."""
@@ -1034,7 +1339,11 @@ class DataPreprocessor:
     the last step of all three splits (`normalizer`), config['data']['artifact_augment'] (default False) adds RandomGhosting, RandomSpike,
     RandomGamma and RandomAnisotropy to the intensity OneOf (`artifacts=True`; it needs intensity_augment).  config['data']['batch_mix'] (absent by
     default: `batch_mix` is None) is a dict of `BatchMix` arguments and builds the `batch_mix` attribute, to call on the training batch and its
-    labels after `train_transforms`."""
+    labels after `train_transforms`.  config['data']['conform'] (absent by default: `conform` is None and nothing changes) is a dict with
+    target_shape and spacing (`Resample`) or resize (`Resize`), optionally image_interpolation, antialias, padding_mode and spacing_key
+    (`conform_from_config`): the loaders then read raw volumes of any shape (`VolumeDataset` + `collate_ragged`, batches are
+    (RaggedBatch, labels)) and the `conform` attribute brings a batch onto the grid, `x = pre.conform(ragged.to(device))`, before
+    `train_transforms` / `val_transforms`."""
 
     def __init__(self, config, seed: Optional[int] = None):
         self.config = config
@@ -1047,12 +1356,19 @@ class DataPreprocessor:
                                                                             eval_transforms(norm), eval_transforms(norm))
         mix = config["data"].get("batch_mix")
         self.batch_mix = BatchMix(**mix) if mix is not None else None
+        conform = config["data"].get("conform")
+        self.conform = conform_from_config(conform) if conform is not None else None
 
     def preprocess(self, df=None):
         import pandas as pd
         d = self.config["data"]
         df = pd.read_csv(d["data_path"])
         sub = {s: df[df["subset"] == s].reset_index(drop=True) for s in ("train", "val", "test")}
+        if self.conform is not None:
+            ds = {s: VolumeDataset(sub[s], image_folder=d["image_folder"], spacing_key=d["conform"].get("spacing_key", "spacing")) for s in sub}
+            mk = lambda s, shuffle: DataLoader(ds[s], batch_size=d["batch_size"], shuffle=shuffle, num_workers=d["num_workers"], pin_memory=True,  # noqa: E731
+                                               collate_fn=collate_ragged)
+            return mk("train", True), mk("val", False), mk("test", False), ds["train"], ds["val"], ds["test"]
         ds = {s: CustomDataset(sub[s], transforms=None, image_folder=d["image_folder"]) for s in sub}
         mk = lambda s, shuffle: DataLoader(ds[s], batch_size=d["batch_size"], shuffle=shuffle, num_workers=d["num_workers"], pin_memory=True)  # noqa: E731
         return mk("train", True), mk("val", False), mk("test", False), ds["train"], ds["val"], ds["test"]

@@ -109,6 +109,8 @@ FeatureTopkDesc = _struct("gvk_feature_topk_desc", ["q", "g", "exclude", "idx", 
                           i64=["scratch_words"])
 HeadDesc = _struct("gvk_head_desc", ["g", "ln_gamma", "ln_beta", "wh", "bh", "logits", "pooled", "dlogits", "dg", "dwh", "dbh"],
                    ["B", "T", "C", "K", "r0", "R", "accumulate"])
+ConformDesc = _struct("gvk_conform_desc", ["data", "scratch", "out", "src_off", "dst_off", "meta", "start", "inside", "weights", "partials"],
+                      ["B", "D", "H", "W", "T", "npass", "pad_min", "p0d0", "p0d1", "p0d2", "p1d0", "p1d1", "p1d2", "p2d0", "p2d1", "p2d2"], ["pad_value"])
 
 (EPI_STORE_BF16, EPI_BIAS_RES_F32, EPI_BIAS_GELU_BF16, EPI_PATCH_F32, EPI_GELU_BWD_BF16, EPI_STORE_F32, EPI_BIAS_RES_F32_BF16,
  EPI_BIAS_RELU_BF16, EPI_RELU_BWD_BF16) = range(9)
@@ -226,6 +228,8 @@ SIGNATURES = {
     "gvk_feature_topk": [C.POINTER(FeatureTopkDesc), _P],
     "gvk_knn_vote": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "gvk_class_means": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_ragged_minmax": [_P, _P, _P, _P, _I, _P],
+    "gvk_conform_volumes": [C.POINTER(ConformDesc), _P],
 }
 NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, []), "gvk_abi_version": (C.c_int, []),
              "gvk_attention_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

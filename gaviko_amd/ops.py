@@ -1373,6 +1373,151 @@ def batch_mix(x, out, mode, lam, perm, box) -> None:
     L.launch.gvk_batch_mix(x, out, *tabs, B, D, H, W)
 
 
+CONFORM_MAX_TAPS, CONFORM_META = 16, 16                                    # GVK_CONFORM_MAX_TAPS, GVK_CONFORM_META
+CONFORM_KEEP, CONFORM_GATHER, CONFORM_CONTRACT, CONFORM_DONE = 0, 1, 2, 3  # axis modes of a conform pass (include/gaviko_hip.h)
+
+
+def _ragged(data, offsets, shapes, what):
+    """The checks every ragged launch shares: data float32 [total] on the device, offsets [B] or [B + 1] and shapes [B][3] HOST arrays with
+    every sample inside the buffer.  Returns (offsets int64 [B], shapes int64 [B][3], counts int64 [B])."""
+    _chk(data, torch.float32, f"{what} data")
+    shapes = np.ascontiguousarray(shapes, dtype=np.int64).reshape(-1, 3)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    B = len(shapes)
+    if B < 1 or len(offsets) not in (B, B + 1):
+        raise L.GavikoHipError(f"{what}: shapes [B][3] and offsets [B] or [B + 1] expected (host arrays)")
+    offsets = offsets[:B]
+    if (shapes < 1).any():
+        raise L.GavikoHipError(f"{what}: every axis of every sample has at least one voxel")
+    counts = shapes.prod(axis=1)
+    if (offsets < 0).any() or (offsets + counts > data.numel()).any():
+        raise L.GavikoHipError(f"{what}: a sample lies outside the packed buffer of {data.numel()} elements")
+    return offsets, shapes, counts
+
+
+def ragged_minmax(data, offsets, shapes, partials=None) -> torch.Tensor:
+    """Per-sample (min, max) partials of a packed buffer of unequal volumes (data.RaggedBatch), in the layout of `minmax_partials` /
+    `volume_minmax`: sample b is the prod(shapes[b]) elements at data + offsets[b], any alignment.  offsets and shapes are HOST arrays,
+    checked here and then uploaded.  Returns partials (allocated unless given)."""
+    offsets, shapes, counts = _ragged(data, offsets, shapes, "ragged_minmax")
+    B = len(shapes)
+    if partials is None:
+        partials = minmax_partials(B, data.device)
+    _chk(partials, torch.float32, "ragged_minmax partials", B * L.load().gvk_minmax_partials())
+    L.launch.gvk_ragged_minmax(data, torch.from_numpy(offsets).to(data.device), torch.from_numpy(counts).to(data.device), partials, B)
+    return partials
+
+
+def conform_plan(shapes, target_shape, start, weights, inside, taps):
+    """The passes of `conform_volumes` for HOST tables (data.conform_tables): an axis whose inside rows are all single taps of weight
+    exactly 1 is gathered (bits moved) in the sample's first pass; every other axis is contracted in a pass of its own, the axis of largest
+    reduction N / n first, so a sample takes max(1, contracted axes) passes and the batch the most any sample takes.  Returns a dict: npass,
+    meta int32 [3][B][CONFORM_META], src_off / dst_off int64 [3][B] (the data offsets are added by the caller), pass_dims int32 [3][3], scratch
+    (elements of intermediate storage), exact bool [B][3]."""
+    shapes = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
+    N = np.asarray(target_shape, dtype=np.int64)
+    B, off = len(shapes), np.concatenate([[0], np.cumsum(N)])
+    meta, src_off, dst_off = np.zeros((3, B, CONFORM_META), np.int32), np.zeros((3, B), np.int64), np.zeros((3, B), np.int64)
+    dims, exact, scratch, npass = np.zeros((3, 3), np.int64), np.zeros((B, 3), bool), 0, 1
+    for b in range(B):
+        n = shapes[b]
+        for a in range(3):
+            rows = slice(off[a], off[a + 1])
+            ins = inside[b, rows].astype(bool)
+            exact[b, a] = taps[b, a] == 1 and bool((weights[b, rows, 0][ins] == 1.0).all())
+        contract = sorted((a for a in range(3) if not exact[b, a]), key=lambda a: (N[a] / n[a], a))
+        passes = max(1, len(contract))
+        npass = max(npass, passes)
+        cur = n.copy()
+        for p in range(passes):
+            ca = contract[p] if contract else -1
+            mode = [CONFORM_CONTRACT if a == ca else
+                    (CONFORM_GATHER if p == 0 else CONFORM_DONE) if exact[b, a] else
+                    CONFORM_DONE if a in contract[:p] else CONFORM_KEEP for a in range(3)]
+            out = np.array([cur[a] if mode[a] == CONFORM_KEEP else N[a] for a in range(3)])
+            last = p == passes - 1
+            meta[p, b, :14] = [1, int(p > 0), int(last), *mode, *cur, *out, ca, taps[b, ca] if ca >= 0 else 1]
+            src_off[p, b] = dst_off[p - 1, b] if p else 0
+            dst_off[p, b] = b * int(N.prod()) if last else scratch
+            if not last:
+                scratch += int(out.prod())
+            dims[p] = np.maximum(dims[p], out)
+            cur = out
+        assert (cur == N).all()                                           # a sample's last pass leaves it on the output grid
+    return dict(npass=npass, meta=meta, src_off=src_off, dst_off=dst_off, pass_dims=dims.astype(np.int32), scratch=scratch, exact=exact)
+
+
+class ConformLaunch:
+    """One checked and uploaded `conform_volumes` call: `run()` launches its passes and returns `out`.  It keeps the device tables alive, so
+    the same conform can be launched again (tools/bench_conform.py times exactly the launches this way)."""
+
+    def __init__(self, desc, out, keep):
+        self.desc, self.out, self._keep = desc, out, keep
+
+    def run(self) -> torch.Tensor:
+        L.launch.gvk_conform_volumes(C.byref(self.desc))
+        return self.out
+
+
+def conform_volumes(*args, **kw) -> torch.Tensor:
+    """`conform_prepare(...).run()`: a packed buffer of unequal float32 volumes onto the uniform grid, returned as out [B][D][H][W]."""
+    return conform_prepare(*args, **kw).run()
+
+
+def conform_prepare(data, offsets, shapes, start, weights, inside, taps, target_shape, pad_value: float = 0.0, partials=None, out=None,
+                    scratch=None) -> ConformLaunch:
+    """A packed buffer of unequal float32 volumes onto the uniform grid out [B][D][H][W] through the per-axis banded tables of
+    `data.conform_tables` (start, inside [B][D + H + W], weights [B][D + H + W][T], taps [B][3] = each sample's own band per axis): up to three
+    streaming passes planned by `conform_plan`.  offsets, shapes and all four tables are HOST arrays: every index they imply is checked here,
+    then they are uploaded.  pad_value fills voxels outside a sample; with partials (ragged_minmax of the same buffer) the sample's own minimum
+    does, read on the device.  out and the scratch of the intermediate passes are allocated unless given; neither may overlap data."""
+    offsets, shapes, _ = _ragged(data, offsets, shapes, "conform_volumes")
+    B, N = len(shapes), tuple(int(v) for v in target_shape)
+    if len(N) != 3 or min(N) < 1:
+        raise L.GavikoHipError(f"conform_volumes: target_shape is three positive lengths, not {target_shape!r}")
+    S = sum(N)
+    start, inside = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(inside).astype(np.int32)
+    weights, taps = np.ascontiguousarray(weights, dtype=np.float32), np.ascontiguousarray(taps, dtype=np.int64)
+    if start.shape != (B, S) or inside.shape != (B, S) or weights.ndim != 3 or weights.shape[:2] != (B, S) or taps.shape != (B, 3):
+        raise L.GavikoHipError(f"conform_volumes: start, inside [B = {B}][{S}], weights [B][{S}][T] and taps [B][3] expected")
+    T = weights.shape[2]
+    if not 1 <= T <= CONFORM_MAX_TAPS or (taps < 1).any() or (taps > T).any():
+        raise L.GavikoHipError(f"conform_volumes: 1..{CONFORM_MAX_TAPS} taps per row and 1 <= taps <= T = {T}")
+    if not np.isfinite(weights).all():
+        raise L.GavikoHipError("conform_volumes: weights must be finite")
+    off = np.concatenate([[0], np.cumsum(N)])
+    for a in range(3):                                                  # every read an inside row implies lies inside its sample
+        rows = slice(off[a], off[a + 1])
+        ins = inside[:, rows] != 0
+        bad = ins & ((start[:, rows] < 0) | (start[:, rows] + taps[:, a:a + 1] > shapes[:, a:a + 1]))
+        if bad.any():
+            b, q = np.argwhere(bad)[0]
+            raise L.GavikoHipError(f"conform_volumes: sample {b}, axis {a}, row {q} reads [{start[b, off[a] + q]}, +{taps[b, a]}) of {shapes[b, a]} voxels")
+    plan = conform_plan(shapes, N, start, weights, inside, taps)
+    dims = plan["pass_dims"]
+    for p in range(plan["npass"]):
+        if (int(dims[p][0]) + 7) // 8 * B > 65535 or (int(dims[p][1]) + 3) // 4 > 65535:
+            raise L.GavikoHipError(f"conform_volumes: pass {p} of {tuple(dims[p])} voxels per sample x {B} samples exceeds the launch grid")
+    plan["src_off"][0] += offsets
+    dev = data.device
+    if out is None:
+        out = torch.empty((B,) + N, dtype=torch.float32, device=dev)
+    _chk(out, torch.float32, "conform_volumes out", B * N[0] * N[1] * N[2])
+    if plan["scratch"] and scratch is None:
+        scratch = torch.empty(plan["scratch"], dtype=torch.float32, device=dev)
+    if plan["scratch"]:
+        _chk(scratch, torch.float32, "conform_volumes scratch", plan["scratch"])
+    if partials is not None:
+        _chk(partials, torch.float32, "conform_volumes partials", B * L.load().gvk_minmax_partials())
+    tabs = [torch.from_numpy(t).to(dev) for t in (plan["src_off"], plan["dst_off"], plan["meta"], start, inside, weights)]
+    d = L.ConformDesc(data=L.ptr(data), scratch=L.ptr(scratch) if plan["scratch"] else None, out=L.ptr(out),
+                      src_off=L.ptr(tabs[0]), dst_off=L.ptr(tabs[1]), meta=L.ptr(tabs[2]), start=L.ptr(tabs[3]), inside=L.ptr(tabs[4]),
+                      weights=L.ptr(tabs[5]), partials=L.ptr(partials) if partials is not None else None,
+                      B=B, D=N[0], H=N[1], W=N[2], T=T, npass=plan["npass"], pad_min=int(partials is not None),
+                      pad_value=float(pad_value), **{f"p{p}d{a}": int(dims[p][a]) for p in range(3) for a in range(3)})
+    return ConformLaunch(d, out, tabs + [data, scratch, partials])
+
+
 def eval_rows(logits, target, proba, pred, confusion) -> None:
     _chk(logits, torch.float32, "eval_rows logits")
     N, K = logits.shape

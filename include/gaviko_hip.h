@@ -969,6 +969,39 @@ int gvk_knn_vote(const int32_t* idx, const float* score, const int32_t* labels, 
                  float temperature, void* stream);
 int gvk_class_means(const float* x, const int32_t* labels, float* mean, int32_t* count, int N, int C, int K, void* stream);
 
+/* ---- raw volumes of any shape and spacing onto the model grid (csrc/conform.hip; gaviko_amd.data.Conform) ----
+ * torchio's first stage (Resample to a spacing / Resize, then CropOrPad) for a RAGGED batch: `data` holds B float32 volumes of unequal
+ * shape n_b = (n0, n1, n2), each in [D][H][W] order, sample b starting at element offset off_b (any alignment); the output is the uniform
+ * out [B][D][H][W].  Per sample and per array axis a the whole geometry is ONE banded table built on the host in float64 and rounded to
+ * float32 once (data.conform_tables): output index q reads the inputs start[q] .. start[q] + K - 1 with weights[q][0..K), or -- inside[q] == 0
+ * -- lies in the padding.  The tables of the three axes are concatenated: start / inside int32 [B][D + H + W] (offsets 0, D, D + H),
+ * weights float32 [B][D + H + W][T], T <= GVK_CONFORM_MAX_TAPS the row length (a sample's own band K <= T is in its meta rows).
+ * gvk_ragged_minmax: partials [B][gvk_minmax_partials()] = the (min, max) slab pairs of the counts[b] elements at data + offsets[b], the
+ *   layout of gvk_volume_minmax (offsets, counts int64 [B], DEVICE tables); scalar loads, no alignment assumed.  Exact.
+ * gvk_conform_volumes: the contraction is separable, so it runs as npass <= 3 streaming passes, one contracted axis each, lanes along W in
+ *   every pass.  The caller plans them (ops.conform_volumes): per pass p and sample b a meta row of 16 int32
+ *     { live, src_sel (0 data, 1 scratch), dst_sel (0 scratch, 1 out), mode[3], in_dims[3], out_dims[3], contracted axis or -1, K, 0, 0 }
+ *   with mode 0 = untouched so far (identity), 1 = gathered in this pass (out[q] = in[start[q]]: a move of 32-bit words), 2 = contracted in
+ *   this pass, 3 = done in an earlier pass (already on the output grid), and src_off / dst_off int64 [3][B] the element offsets of the
+ *   sample inside the selected buffers.  An axis whose rows are all single taps of weight 1 is gathered, never multiplied: a batch that is
+ *   only cropped, padded or already conforming comes out bit for bit in one pass.  A contracted element is
+ *   v = w[0] x[0]; v = fmaf(w[t], x[t], v) for t = 1..K-1 (one rounding per tap), stored as float32 between passes.  An output voxel that is
+ *   outside on any axis touched so far is written as the pad value in every pass, so the padding is exact: pad_value, or with pad_min != 0
+ *   the sample's own minimum reduced on the device from partials (gvk_ragged_minmax).  The device tables are not read by the host: every
+ *   index they imply (start[q] + K <= n on inside rows, the offsets) must have been checked by the caller.  pass_dims[p] = the largest
+ *   out_dims over the live samples of pass p (the grid).  No atomics: the same bits on every run.  64-bit element offsets throughout.
+ *   Bytes: every pass reads its input once and writes its output once; with the axis of largest reduction first the intermediates are
+ *   the smallest possible. */
+enum { GVK_CONFORM_MAX_TAPS = 16, GVK_CONFORM_META = 16 };
+typedef struct gvk_conform_desc {
+  const float* data; float* scratch; float* out; const int64_t* src_off; const int64_t* dst_off; const int32_t* meta; const int32_t* start;
+  const int32_t* inside; const float* weights; const float* partials;
+  int32_t B, D, H, W, T, npass, pad_min, p0d0, p0d1, p0d2, p1d0, p1d1, p1d2, p2d0, p2d1, p2d2;
+  float pad_value;
+} gvk_conform_desc;
+int gvk_ragged_minmax(const float* data, const int64_t* offsets, const int64_t* counts, float* partials, int B, void* stream);
+int gvk_conform_volumes(const gvk_conform_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
