@@ -5,10 +5,11 @@ One `Engine` per model instance.  It owns
     the pre-transposed weight; frozen weights need no wgrad and their GEMM inputs are never saved),
   * the per-batch-size workspace (fp32 residual streams per layer, bf16 GEMM operands, saved statistics),
   * the ordered list of C-ABI launches that make up forward() and backward().
-The method-specific halves are mixins (engine_gaviko.py, engine_peft.py), and so are the analysis entry points of gaviko_amd.explain /
-uncertainty / features (engine_analysis.py); the sweeps here call their hooks.  What is STATIC about a method -- token geometry, feature
-flags, its own workspace slots, name patterns, which tensors its own gradient kernels cover -- is one spec per kind in engine_methods.py
-(`self.method`); `self.kind` is compared only where a sweep picks its next launch.
+GAViKO's side paths and the unfrozen-backbone gradients are mixins (engine_gaviko.py, engine_peft.py), and so are the analysis entry points
+of gaviko_amd.explain / uncertainty / features (engine_analysis.py).  Everything else that is a method's own -- token geometry, feature
+flags, workspace slots, name patterns AND its launches -- is one spec per kind in engine_methods.py (`self.method`): the sweeps here are the
+backbone plus GAViKO's stream choreography, call `self.method.<hook>(self, ...)` wherever another method launches something, and compare
+`self.kind` with "gaviko" only.
 Everything is enqueued on torch's current HIP stream; nothing synchronises, so a whole step can be captured in a HIP
 graph.  There is no CPU / eager fallback.
 
@@ -29,22 +30,21 @@ import torch
 from . import lib as L
 from . import ops
 from .engine_analysis import AnalysisPaths
-from .engine_common import (GRAPH_WARMUP, PLAN_TIMING, SEED_EMB, SEED_LAYER, SEED_PROMPT, USE_GRAPHS, _ABLATE, _EPI_NAMES, _SIDE_STREAMS, Names,
-                            _on, flat_views)
-from .engine_common import evp_highpass_operator  # noqa: F401  (re-exported: tests import it from here)
+from .engine_common import GRAPH_WARMUP, PLAN_TIMING, SEED_EMB, SEED_LAYER, USE_GRAPHS, _ABLATE, _EPI_NAMES, _SIDE_STREAMS, Names, _on, flat_views
+from .engine_common import SEED_PROMPT, evp_highpass_operator  # noqa: F401  (re-exported: tests read them from here)
 from .engine_gaviko import GavikoPaths
 from .engine_methods import METHOD_SPECS
-from .engine_peft import PeftPaths
+from .engine_peft import BackboneGrads
 
 # bench.py instrumentation: when set to a dict, plans recorded from then on bracket every GEMM launch (and the patch-embed
 # stage) with timestamped plan events, so the kernels are timed inside the real three-stream schedule of a replayed step.
 GEMM_MARKS = None
 
 
-class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
+class Engine(GavikoPaths, BackboneGrads, AnalysisPaths):
     def __init__(self, kind: str, cfg: dict, params: Dict[str, torch.nn.Parameter], depth, heads, dim, mlp_dim):
         self.kind, self.cfg, self.p = kind, cfg, params
-        self.method = METHOD_SPECS.get(kind)           # the kind's static facts: geometry, flags, its own buffers and names (engine_methods.py)
+        self.method = METHOD_SPECS.get(kind)           # everything that is the kind's own: geometry, flags, buffers, names, launches (engine_methods.py)
         if self.method is None:
             raise L.GavikoHipError(f"unknown engine kind {kind!r}: expected one of {tuple(METHOD_SPECS)}")
         self.depth, self.heads, self.C, self.mlp = depth, heads, dim, mlp_dim
@@ -69,7 +69,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
             raise L.GavikoHipError("patch embedding is built for single-channel volumes (channels = 1)")
         self.pool = cfg.get("pool", "cls")
         self.method.geometry(self, cfg)                # P, T, Ts, row_off and the method's own widths
-        self.names = Names(kind, self.lora_layers if self.method.wraps_qkv else None)
+        self.names = Names(self.method, self.lora_layers if self.method.wraps_qkv else None)
         self._w16: Dict[str, torch.Tensor] = {}
         self._w16_version = None
         self._shadowed = frozenset(self._backbone_weight_names())
@@ -163,8 +163,8 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
     def refresh_weights(self, need_dgrad: bool) -> None:
         """(Re)build the bf16 shadows when a source weight changed (load_state_dict, optimizer step on an unfrozen tensor).
         Shadows are rewritten IN PLACE so that captured HIP graphs keep pointing at valid operands."""
-        if self.kind == "ssf":
-            return                                  # every operand is re-folded from (W, scale) inside the recorded step (_ssf_fold)
+        if self.method.folds_in_step:
+            return                                  # SSF: every operand is re-folded from (W, scale) inside the recorded step
         names = self._backbone_weight_names()
         version = tuple(self.p[n]._version for n in names) + tuple(self.p[n].data_ptr() for n in names)
         stale = version != self._w16_version
@@ -470,11 +470,11 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
     def _forward_impl(self, ws, sv):
         B, C, T, N, train = sv["B"], self.C, self.T, self.N, sv["train"]
         M = B * T
-        nm, w, d = self.names, self._w16, self._d
+        nm, d = self.names, self._d
         self._mark("f:begin")
         ops.seed_advance(ws["seed"], 7919)                  # device-side dropout epoch (replay safe)
-        if self.kind == "ssf":
-            self._ssf_fold(train)
+        gaviko = self.kind == "gaviko"
+        self.method.fwd_begin(self, ws, train)
         # ---- embedding: patch GEMM (+bias +pos, scattered to rows row_off..) and the broadcast rows
         marking = GEMM_MARKS is not None and self._recording  # bench.py: time the whole patch-embed stage (im2col + GEMM + scatter)
         cur = torch.cuda.current_stream()
@@ -483,39 +483,18 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         G0 = ws["G"][0]
         # im2col -> bf16, then the MFMA GEMM scatters the token rows (a fused gather-GEMM was built in round 2 and measured slower: DESIGN.md 7b.5)
         ops.patchify(ws["img"], ws["cols"], self.patch)
-        if self.kind == "evp":
-            # the raw patch embedding is needed on its own (embedding_generator reads it, evp.py:347-348): conv -> xc, tokens = xc + pos
-            ops.gemm_nt(ws["cols"], w["conv"], B * N, ws["xc"], epilogue=ops.EPI_STORE_F32, bias=d(nm.conv() + ".bias"))
-            ops.rows_patch(G0, ws["xc"], pos[1:], B, T, N, C, 1, False)
-            self._evp_latents(ws, B)
-        else:
-            ops.gemm_nt(ws["cols"], w["conv"], B * N, G0, epilogue=ops.EPI_PATCH_F32, out1=ws["Lc"][0] if self.kind == "gaviko" else None,
-                        bias=d(nm.conv() + ".bias"), pos=pos[1:], rows_in=N, rows_out=T, row_off=self.row_off)
+        self.method.patch_embed(self, ws, B, G0, pos, out1=ws["Lc"][0] if gaviko else None)     # (EVP: + its latents)
         if marking:
-            nout = 2 if self.kind == "gaviko" else 1
+            nout = 2 if gaviko else 1
             self._gemm_marks.append(("__patch_embed__", 2.0 * B * N * self.Kp * C, [B * N, C, self.Kp],
                                      B * (self.Kp * N * 4 + nout * N * C * 4), pe0, self._ev_record(cur)))
-        cls = d(nm.root + "cls_token")[0]
-        if self.kind in ("gaviko", "dvpt"):                   # [P prompts | cls | patches] (gaviko.py:536-548, dvpt.py:196-199)
-            ops.rows_broadcast(G0, d("prompt_embeddings")[0], d("prompt_positional_embedding")[0], B, T, 0, self.P, C)
-            ops.rows_broadcast(G0, cls, pos[0:1], B, T, self.P, 1, C)
-        else:
-            ops.rows_broadcast(G0, cls, pos[0:1], B, T, 0, 1, C)
+        self.method.embed_rows(self, G0, d(nm.root + "cls_token")[0], pos, B)           # cls, behind the prompts where they lead
         if sv["edrop"] > 0:                                   # x = dropout(x + pos) over [cls | patches] (vision_transformer.py:157)
             ops.dropout_rows(G0, sv["edrop"], SEED_EMB, ws["seed"], out32=G0, M=B * T, N=C)
-            if self.kind == "gaviko":                         # ... and, with its own draw, over the local tokens (gaviko.py:544,548)
+            if gaviko:                                        # ... and, with its own draw, over the local tokens (gaviko.py:544,548)
                 ops.dropout_rows(ws["Lc"][0], sv["edrop"], SEED_EMB + 1, ws["seed"], out32=ws["Lc"][0], M=B * N, N=C)
-        if self.kind == "vpt":                                # prompt_proj on every layer's prompts at once (vpt.py:56,127-153)
-            emb = d("deep_prompt_embeddings" if self.deep else "prompt_embeddings").reshape(-1, self.pd)
-            ops.small_linear_fwd(emb, d("prompt_proj.weight"), d("prompt_proj.bias"), ws["vproj"], emb.shape[0], self.pd, C)
-            ops.rows_broadcast(G0, ws["vproj"][: self.P], None, B, T, 1, self.P, C)
-            self._prompt_dropout(ws, sv, 0, G0, self.Ts[0])
-        if self.kind == "melo":
-            self._melo_merge(ws, train)
-        if self.kind == "adaptformer":
-            self._adapter_shadows(train)
+        self.method.fwd_embedded(self, ws, sv, G0, train)     # VPT's projected prompts, the MeLO merge, AdaptFormer's operand shadows
         # ---- layers.  main stream: attention block -> MLP block;  side stream: MWSA -> GPA latents / gates / cross-attention
-        gaviko = self.kind == "gaviko"
         if gaviko:
             loc, gpa = self._stream("loc"), self._stream("gpa")
             self._wait("loc", None)                                  # Lc[0] written by the patch GEMM
@@ -534,8 +513,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
             si = i if sv["keep"] else 0
             gi, go = (i, i + 1) if train else (i & 1, (i + 1) & 1)
             Mi = B * self.Ts[i]
-            repack = self.kind == "vpt" and self.deep
-            gout = ws["Go"] if repack else ws["G"][go]
+            gout = self.method.layer_out(self, ws, go)               # (deep VPT: the layer output before its re-pack)
             if sv["feat"]:
                 self._feat_pool(ws, sv, i, ws["G"][gi], self.Ts[i])       # before anything of layer i touches its input (EVP adds its prompt in place)
             if gaviko:
@@ -548,8 +526,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                     if self._fuse_proj and not fuse_local:
                         self._gpa_down_local(ws, i, si, ws["Lc"][go], B)
             self._mark(f"f{i}:start")
-            if self.kind == "evp":
-                self._evp_add_prompt(ws, i, si, ws["G"][gi], B)               # x[:, 1:] += prompt_i (evp.py:235-238)
+            self.method.fwd_layer_begin(self, ws, i, si, ws["G"][gi], B)      # EVP: x[:, 1:] += prompt_i
             self._attn_block_fwd(ws, i, si, ws["G"][gi], ws["G1"][si], Mi, sv["bdrop"], folded=folded_in)
             self._mark(f"f{i}:attn")
             fused = gaviko and self._fuse_proj
@@ -559,10 +536,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                 with torch.cuda.stream(gpa):
                     self._gpa_fwd_latents(ws, i, si, ws["G1"][si], ws["Lc"][go], M, B, True)
                 side_weights(i)
-            if self.kind == "adaptformer":
-                self._adapter_fwd_down(ws, i, si, ws["G1"][si], Mi)
-            if self.kind == "dvpt":
-                self._dvpt_fwd_latents(ws, i, si, ws["G1"][si], Mi, B)
+            self.method.fwd_after_attn(self, ws, i, si, ws["G1"][si], Mi, B)  # AdaptFormer's down-projection, DVPT's latents
             self._mlp_ln_fwd(ws, i, si, ws["G1"][si], Mi, fused)     # fused: also zx / xl = GPA proj_down(G1), same pass
             if fused:
                 self._wait("gpa", None)                              # xl ready
@@ -581,10 +555,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                              and self.depth not in sv["feat"]) else None)
             self._mlp_block_fwd(ws, i, si, ws["G1"][si], gout, Mi, train, sv["bdrop"],
                                 up_in_fc2=up_in_fc2, stats_out=fold_next, panels=last_rows)
-            if self.kind == "adaptformer":
-                self._adapter_fwd_up(ws, i, si, gout, Mi)
-            if self.kind == "dvpt":
-                self._dvpt_fwd_up(ws, i, si, gout, Mi)
+            self.method.fwd_after_mlp(self, ws, i, si, gout, Mi)     # ... and their up-projections into gout
             self._mark(f"f{i}:mlp")
             if gaviko and up_in_fc2:
                 # the P prompt rows still lack (enh - xl) . Wup^T; when the next layer's first LayerNorm is folded into its qkv GEMM, the
@@ -603,10 +574,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                 self._wait(None, "gpa")                              # enh ready
                 self._gpa_fwd_up(ws, i, si, ws["G"][go], M)
             self._mark(f"f{i}:end")
-            if repack and i + 1 < self.depth:
-                ops.vpt_repack_fwd(gout, ws["vproj"][(i + 1) * self.P: (i + 2) * self.P], ws["G"][go], B, self.Ts[i], self.Ts[i + 1],
-                                   self.P, self.pd, C)
-                self._prompt_dropout(ws, sv, i + 1, ws["G"][go], self.Ts[i + 1])
+            self.method.fwd_layer_end(self, ws, sv, i, gout, go, B)  # deep VPT: re-pack into G[go], prompt dropout
         if gaviko:
             self._wait(None, "loc")                                  # join the local chain (capture needs every fork joined)
         gfin = self._final_stream(ws, train)
@@ -632,12 +600,6 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         out32 = ws["dyd"] if need32 else None
         ops.dropout_rows(dy, p, seed, ws["seed"], out32=out32, out16=ws["dG16"], M=M, N=self.C)
         return out32
-
-    def _prompt_dropout(self, ws, sv, i, g, T):
-        """prompt_dropout on the projected prompts of layer i, rows 1..P of every sample (vpt.py:129,148,152: applied after .expand(B),
-        so every sample draws its own mask)."""
-        if sv["pdrop"] > 0:
-            ops.dropout_rows(g, sv["pdrop"], SEED_PROMPT + i, ws["seed"], out32=g, M=sv["B"] * self.P, N=self.C, rows_in=self.P, rows_out=T, row_off=1)
 
     def _attn_block_fwd(self, ws, i, si, gin, g1, M, pdrop=0.0, folded=False):
         nm, w, d, C = self.names, self._w16, self._d, self.C
@@ -838,7 +800,7 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
 
     def _backward_head(self, ws, sv, gv, backbone_bwd):
         nm, d = self.names, self._d
-        B, C, T = sv["B"], self.C, self.T
+        B, C = sv["B"], self.C
         r0, R = self._pool_rows()
         dG = ws["dG"][0] if backbone_bwd else None
         if backbone_bwd:
@@ -854,17 +816,8 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
             ops.layernorm_fwd(g, d(nw), d(nb), B * Tl, C, y16=ws["xn"], mean=bw["stat"][0], rstd=bw["stat"][1])
             ops.ssf_head_grad(g, bw["stat"][0], bw["stat"][1], d(nm.head() + ".weight"), ws["dlogits"], bw["ones"][:C], bw["zeros"][:C],
                               gv[nw] if nw in bb else bw["junk"][:C], gv[nb] if nb in bb else bw["junk"][C: 2 * C], B, Tl, C, self.K, r0, R)
-        if self.kind == "ssf" and backbone_bwd:
-            # final norm + ssf (ssf.py:138): statistics of the final stream, then the pooled rows' scale / shift gradients
-            g = self._final_stream(ws, True)
-            st = ws["ssf_stat"]
-            ops.layernorm_fwd(g, self.p["transformer.norm.weight"].detach(), self.p["transformer.norm.bias"].detach(), B * T, C, y16=ws["xn"],
-                              mean=st[0], rstd=st[1])
-            ops.ssf_head_grad(g, st[0], st[1], d(nm.head() + ".weight"), ws["dlogits"], self.p["transformer.norm.weight"].detach(),
-                              self.p["transformer.norm.bias"].detach(), gv["transformer.ssf_scale_1"], gv["transformer.ssf_shift_1"],
-                              B, T, C, self.K, r0, R)
-            self._ssf_unfold(gv, bb, self._ssf_sites()[-1:])                           # the final norm's affine
         if backbone_bwd:
+            self.method.bwd_head(self, ws, sv, gv, bb, B)            # SSF: the final norm's scale / shift
             ops.to_operand(dG, ws["dG16"], self.adt)
             if self.kind == "gaviko":
                 ops.memset_zero(ws["dL"][0])
@@ -875,18 +828,14 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         the local-stream gradient ping-pongs with the layer parity."""
         if first:
             self._mwsa_pending = None
-        d = self._d
-        B, C, T = sv["B"], self.C, self.T
+        B, C = sv["B"], self.C
         gaviko = self.kind == "gaviko"
         if first:
             self._mark("b:begin")
             self._backward_head(ws, sv, gv, True)
-        dGout, dGin = ws["dG"][0], ws["dG"][1]
+        dGout, dGin = self.method.bwd_first_boundary(self, ws, hi), ws["dG"][1]      # (dG[0]; deep VPT's un-repack alternates two buffers)
         if gaviko and ((self.depth - 1 - hi) & 1):
             dGout = ws["dGb"]                                  # the boundary gradient ping-pongs with the layer parity (see below)
-        vpt_deep = self.kind == "vpt" and self.deep
-        if vpt_deep and ((self.depth - 1 - hi) & 1):           # the un-repack alternates two buffers with the layer parity
-            dGout = ws["dGv"]
         if gaviko:
             loc, gpa = self._stream("loc"), self._stream("gpa")
             self._wait("gpa", None)
@@ -906,7 +855,6 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         prev_scl = None
         for i in range(hi, lo - 1, -1):
             M = B * self.Ts[i]
-            T = self.Ts[i]
             par = (self.depth - 1 - i) & 1
             # GPA stream: the critical kernels (-> dzx, dzl) first, then the parameter gradients; the other streams wait only
             # for the event between the two
@@ -942,23 +890,11 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
                     self._ev_wait(gpa, prev_scl)
                 prev_scl = self._scl_done
                 self._wait("gpa", None)                                      # the next layer's GPA backward needs this dG[i]
-            if self.kind == "evp":
-                self._evp_bwd_layer(ws, gv, i, dGout, B)
-            if self.kind == "ssf" and bb:
-                self._ssf_unfold(gv, bb, self._ssf_sites()[1 + 6 * i: 7 + 6 * i])     # this layer's six sites, before its bucket is final
+            self.method.bwd_layer(self, ws, gv, bb, i, dGout, B)              # EVP's layer step, the SSF unfold: before the layer's bucket is final
             self._mark(f"b{i}:end")
             if not gaviko:
                 self._bucket_mark("main", i)                                 # transformer.layers.{i}.* gradients (adapters, LoRA, ...) are final
-            if self.kind == "vpt" and (i == 0 or self.deep):
-                # prompt rows 1..P of this layer's input are this layer's projected prompts (vpt.py:127-131,147-153)
-                if sv.get("pdrop", 0.0) > 0:                                 # through prompt_dropout: same mask, in place (these rows end here)
-                    ops.dropout_rows(dGout, sv["pdrop"], SEED_PROMPT + i, ws["seed"], out32=dGout, M=B * self.P, N=C, rows_in=self.P, rows_out=T, row_off=1)
-                ops.rows_batch_sum(dGout, ws["dvproj"][i * self.P: (i + 1) * self.P], None, B, T, 1, self.P, C)
-            if vpt_deep and i > 0:
-                other = ws["dGv"] if dGout is ws["dG"][0] else ws["dG"][0]
-                ops.vpt_repack_bwd(dGout, other, B, self.Ts[i - 1], T, self.P, self.pd, C)
-                dGout = other
-                ops.to_operand(dGout, ws["dG16"], self.adt)
+            dGout = self.method.bwd_layer_boundary(self, ws, sv, i, dGout, B)   # VPT: its prompt rows end here; deep VPT un-repacks into the other buffer
         if gaviko:
             if last:                                                         # (the deferred step crosses segment boundaries like layer boundaries)
                 # frozen embedding: the local stream's INPUT gradient (layer 0's deferred last step) has no reader -- conv / pos_embedding carry none
@@ -968,32 +904,14 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         if last and sv.get("bb"):
             if sv.get("edrop", 0.0) > 0:                                     # through emb_dropout
                 ops.dropout_rows(dGout, sv["edrop"], SEED_EMB, ws["seed"], out32=dGout, M=B * self.T, N=C)
-            dlocal = ws["dL"][(self.depth - 1 - lo + 1) & 1] if gaviko else None      # what _mwsa_final of the lowest layer wrote
+            # a second gradient of the raw patch embedding: what _mwsa_final of GAViKO's lowest layer wrote; EVP's embedding_generator share
+            dlocal = ws["dL"][(self.depth - 1 - lo + 1) & 1] if gaviko else self.method.bwd_embed_dlocal(self, ws, dGout, B)
             if gaviko and sv.get("edrop", 0.0) > 0:
                 ops.dropout_rows(dlocal, sv["edrop"], SEED_EMB + 1, ws["seed"], out32=dlocal, M=B * self.N, N=C)
-            if self.kind == "evp":
-                # the raw conv output also feeds embedding_generator (evp.py:347-348): d xc += d s . W_e  (d s is complete once layer 0 is through)
-                dlocal = ws["ev"]["tmp"]
-                ops.skinny_up(lat=ws["evb"]["ds"], w=self._evp_state(dGout.device)["We"], out=dlocal, M=B * self.N, C=C, L=self.Lp, w_layout=1,
-                              accumulate=0)
             self._bb_embed_grads(ws, gv, sv["bb"], dGout, B, dlocal=dlocal, dlocal_to_pos=gaviko)
-        if last and self.kind == "evp":
-            self._evp_bwd_finish(ws, gv, B)
-        if last and self.kind == "ssf":
-            # patch embedding + ssf (ssf.py:229-232): dy = the patch rows of the input gradient, y = G[0] patch rows - pos[1:]
-            pos = self.p["pos_embedding"].detach()[0]
-            ops.ssf_colgrad(dGout, ws["G"][0], self.p["ssf_scale_1"].detach(), self.p["ssf_shift_1"].detach(), gv["ssf_scale_1"], gv["ssf_shift_1"],
-                            ws["ssf_scratch"], B * self.N, C, pos=pos[1:], rows_in=self.N, rows_out=T, row_off=1,
-                            y_mul=1.0 - sv.get("edrop", 0.0))              # (dGout is already masked by emb_dropout when that is live)
-            self._ssf_unfold(gv, sv.get("bb") or (), self._ssf_sites()[:1])            # the patch embedding's conv tensors
-        if last and self.kind == "vpt":
-            emb_name = "deep_prompt_embeddings" if self.deep else "prompt_embeddings"
-            emb = d(emb_name).reshape(-1, self.pd)
-            ops.small_linear_bwd(emb, d("prompt_proj.weight"), ws["dvproj"], gv["prompt_proj.weight"], gv["prompt_proj.bias"],
-                                 gv[emb_name].view(-1, self.pd), emb.shape[0], self.pd, C)
-        if last and (gaviko or self.kind == "dvpt"):
-            ops.rows_batch_sum(dGout, gv["prompt_embeddings"].view(self.P, C), gv["prompt_positional_embedding"].view(self.P, C), B, T, 0,
-                               self.P, C)
+        if last:
+            # what the method's own tensors still lack: EVP's generators, SSF's patch-embedding site, VPT's prompt_proj, the leading prompt rows
+            self.method.bwd_tail(self, ws, sv, gv, dGout, B)
         if last and self._igrad:
             self._input_grad_tail(ws, sv, dGout, B, lo)
         if last:
@@ -1007,22 +925,19 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         B, T = sv["B"], self.Ts[i]
         M, m, st = B * T, self.names.mlp(i), ws["stat"][i]
         bb, pd_ = sv.get("bb") or (), sv.get("bdrop", 0.0)
-        dvpt, ssf = self.kind == "dvpt", self.kind == "ssf"
+        site, ln_site = self.method.bwd_linear_site, self.method.bwd_ln_site      # SSF's scale / shift gradients; no-ops elsewhere
         dy_ff = dGout
         if pd_ > 0:                                                          # gradient of dropout(fc2(.)): the forward's mask on dGout
-            dy_ff = self._masked_grad(ws, dGout, pd_, SEED_LAYER + 8 * i + 3, bool(bb) or ssf, M)
+            dy_ff = self._masked_grad(ws, dGout, pd_, SEED_LAYER + 8 * i + 3, bool(bb) or self.method.reads_masked_grad, M)
         if bb:                                                               # fc2: db = colsum(dGout), dW = dGout^T . act
             self._bb_linear_grads(ws, gv, bb, m + ".net.4", dy_ff, ws["dG16"], ws["sav"]["act"][i] if sv["wgrad"] else None, M, C, self.mlp,
                                   ldx=self.ldx if self.ldx != self.mlp else None)
-        if dvpt:
-            self._dvpt_bwd_latents(ws, gv, i, dGout, M, B)
-        if ssf:                                                              # fc2 + ssf_2: dy = dGout, y = G[i+1] - G1[i]
-            # (behind a live dropout the stored difference is kept / (1 - p): masked gradient, y_mul = 1 - p)
-            self._ssf_linear_grad(ws, gv, m, 2, dy_ff, ws["G"][i + 1], M, C, y1=ws["G1"][i], y_mul=1.0 - pd_)
+        self.method.bwd_mlp_begin(self, ws, gv, i, dGout, M, B)              # DVPT: its latents' backward
+        # fc2: dy = dGout, y = G[i+1] - G1[i] (behind a live dropout the stored difference is kept / (1 - p): masked gradient, y_mul = 1 - p)
+        site(self, ws, gv, m, 2, dy_ff, ws["G"][i + 1], M, C, y1=ws["G1"][i], y_mul=1.0 - pd_)
         self._gemm(ws["dG16"], w[f"fc2{i}_t"], M, ws["dpre"], epilogue=ops.EPI_GELU_BWD_BF16, aux=ws["pre"][i], ldaux=self.ldx,
                    drop_p=pd_, seed=SEED_LAYER + 8 * i + 2, seed_ptr=ws["seed"], aux_is_grad=int(sv.get("pre_is_grad", False)), **top)
-        if ssf:                                                              # fc1 + ssf_1: dy = d(pre-activation), y = saved pre-activation
-            self._ssf_linear_grad(ws, gv, m, 1, ws["dpre"], ws["pre"][i], M, self.mlp)
+        site(self, ws, gv, m, 1, ws["dpre"], ws["pre"][i], M, self.mlp)      # fc1: dy = d(pre-activation), y = saved pre-activation
         if bb:                                                               # fc1: db = colsum(dpre), dW = dpre^T . LN2(G1)
             self._bb_linear_grads(ws, gv, bb, m + ".net.1", ws["dpre"], ws["dpre"], ws["sav"]["xn2"][i] if sv["wgrad"] else None, M, self.mlp, C)
         self._gemm(ws["dpre"], w[f"fc1{i}_t"], M, ws["dx16b"] if dy16 else ws["dx32"], epilogue=ops.EPI_STORE_BF16 if dy16 else ops.EPI_STORE_F32,
@@ -1030,17 +945,13 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         self._mark(f"b{i}:fc1d")
         if bb:
             self._bb_ln_grads(ws, gv, bb, m + ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
-        if ssf:                                                              # LN2 + ssf_0
-            self._ssf_ln_grad(ws, gv, m, ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
+        ln_site(self, ws, gv, m, ".net.0", ws["dx32"], ws["G1"][i], st[2], st[3], M)
         if top:                                                              # the other rows of dG1 are dGout: zero, in one memset
             ops.memset_zero(dGin)
         ops.layernorm_bwd(ws["dx16b"] if dy16 else ws["dx32"], ws["G1"][i], st[2], st[3], d(m + ".net.0.weight"), M, C, dx=dGin, dres=dGout,
-                          dx16=None if self.kind in ("gaviko", "adaptformer", "dvpt") else ws["dG16"],
+                          dx16=ws["dG16"] if self.method.ln2_leaves_operand else None,
                           rows=(B, sum(self._pool_rows()), T) if top else None)
-        if dvpt:
-            self._dvpt_bwd_scatter(ws, i, dGin, M)                           # dG1 += (dz . Wd) * QuickGELU'(G1)  (+ operand copy)
-        if self.kind == "adaptformer":
-            self._adapter_bwd(ws, gv, i, dGout, dGin, M, refresh_operand=pd_ > 0)   # adds LN_a'(...) into dG1 and refreshes dG16
+        self.method.bwd_mlp_end(self, ws, gv, i, dGout, dGin, M, pd_)        # DVPT's scatter, AdaptFormer's backward: += dG1, refresh dG16
 
     def _attn_block_bwd(self, ws, sv, gv, i, dGin, dx, dy16, bot):
         """Main stream, attention block of layer i: dx = dGin + LN1'(qkv^T(attn'(out^T(dGin)))), with the method's own gradients of the block
@@ -1049,12 +960,11 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         B, T = sv["B"], self.Ts[i]
         M, a, st = B * T, self.names.attn(i), ws["stat"][i]
         bb, pd_ = sv.get("bb") or (), sv.get("bdrop", 0.0)
-        ssf = self.kind == "ssf"
+        site, ln_site = self.method.bwd_linear_site, self.method.bwd_ln_site
         dy_at = dGin
         if pd_ > 0:                                                          # gradient of dropout(to_out(.))
-            dy_at = self._masked_grad(ws, dGin, pd_, SEED_LAYER + 8 * i + 1, bool(bb) or ssf, M)
-        if ssf:                                                              # to_out + ssf_2: dy = dG1, y = G1[i] - G[i]
-            self._ssf_linear_grad(ws, gv, a, 2, dy_at, ws["G1"][i], M, C, y1=ws["G"][i], y_mul=1.0 - pd_)
+            dy_at = self._masked_grad(ws, dGin, pd_, SEED_LAYER + 8 * i + 1, bool(bb) or self.method.reads_masked_grad, M)
+        site(self, ws, gv, a, 2, dy_at, ws["G1"][i], M, C, y1=ws["G"][i], y_mul=1.0 - pd_)      # to_out: dy = dG1, y = G1[i] - G[i]
         if bb:                                                               # to_out: db = colsum(dG1), dW = dG1^T . ctx
             self._bb_linear_grads(ws, gv, bb, a + ".to_out.0", dy_at, ws["dG16"], ws["ctx"][i], M, C, C)
         self._gemm(ws["dG16"], w[f"out{i}_t"], M, ws["dctx"], epilogue=ops.EPI_STORE_BF16)
@@ -1065,19 +975,16 @@ class Engine(GavikoPaths, PeftPaths, AnalysisPaths):
         ops.attention_bwd(ws["qkv"][i], ws["ctx"][i], ws["dctx"], ws["lse"][i], ws["delta"], ws["dqkv"], B, T, self.heads, 64 ** -0.5,
                           drop_p=pd_, seed=SEED_LAYER + 8 * i, seed_ptr=ws["seed"], q_prescaled=True, need_rows=self.P if bot else None)
         self._mark(f"b{i}:attnb")
-        if self.kind == "melo" and i in self.lora_layers:
-            self._melo_bwd(ws, gv, i, M)
-        if ssf:                                                              # to_qkv + ssf_1: dy = dqkv, y = saved qkv
-            uq = {} if self.fp32 else dict(y0_cols=self.heads * 64, y0_mul=1.0 / self.q_scale)     # the saved q block is pre-scaled
-            self._ssf_linear_grad(ws, gv, a, 1, ws["dqkv"], ws["qkv"][i], M, 3 * C, **uq)
+        self.method.bwd_after_attention(self, ws, gv, i, M)                  # MeLO: the LoRA factors of a wrapped layer
+        uq = {} if self.fp32 else dict(y0_cols=self.heads * 64, y0_mul=1.0 / self.q_scale)         # the saved q block is pre-scaled
+        site(self, ws, gv, a, 1, ws["dqkv"], ws["qkv"][i], M, 3 * C, **uq)   # to_qkv: dy = dqkv, y = saved qkv
         if bb:                                                               # to_qkv (bias-free): dW = dqkv^T . LN1(G)
             self._bb_linear_grads(ws, gv, bb, a + ".to_qkv", None, ws["dqkv"], ws["sav"]["xn1"][i] if sv["wgrad"] else None, M, 3 * C, C)
         self._gemm(ws["dqkv"], w[f"qkv{i}_t"], M, ws["dx16b"] if dy16 else ws["dx32"], epilogue=ops.EPI_STORE_BF16 if dy16 else ops.EPI_STORE_F32,
                    **bot)
         if bb:
             self._bb_ln_grads(ws, gv, bb, a + ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
-        if ssf:                                                              # LN1 + ssf_0
-            self._ssf_ln_grad(ws, gv, a, ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
+        ln_site(self, ws, gv, a, ".norm", ws["dx32"], ws["G"][i], st[0], st[1], M)
         self._mark(f"b{i}:qkvd")
         proj = None
         if self._fuse_proj and i > 0:                                        # + dcomb = dx . W_up for the GPA core of layer i - 1

@@ -71,7 +71,7 @@ class AnalysisPaths:
         """feature_forward: the CLS row and the patch-row mean of the stream g [B][T][C] entering layer l (l = depth: the last output)."""
         if l in sv["feat"]:
             j = sv["feat"].index(l)
-            r_cls = 0 if self.kind == "vpt" else self.row_off - 1
+            r_cls = self.method.cls_row(self)
             ops.token_pool(g, sv["B"], T, self.C, r_cls, 1, out=ws["feat_cls"][j])
             ops.token_pool(g, sv["B"], T, self.C, self.row_off, T - self.row_off, out=ws["feat_patch"][j])
 
@@ -273,7 +273,7 @@ class AnalysisPaths:
         if "conv_t" not in w:
             w["conv_t"] = torch.zeros((Kp, C), dtype=self.adt, device=device)
         if self.kind == "evp":
-            st = self._evp_state(device)
+            st = self.method.state(self, device)
             if "hpT" not in st:
                 st["hpT"] = st["hp"].t().contiguous()                   # the adjoint operator of the high-pass's linear part
                 st["WpT"] = torch.zeros((Kp, 64), device=device)
@@ -306,13 +306,13 @@ class AnalysisPaths:
                 ops.dropout_rows(dlocal, edrop, SEED_EMB + 1, ws["seed"], out32=dlocal, M=BN, N=C)
             ops.add2d(ig["dxc"], C, dlocal, C, ig["dxc"], C, BN, C)
         if self.kind == "evp":                             # embedding_generator reads the raw conv output (evp.py:347-348)
-            ops.skinny_up(lat=ws["evb"]["ds"], w=self._evp_state(dG0.device)["We"], out=ig["dxc"], M=BN, C=C, L=self.Lp, w_layout=1, accumulate=1)
+            ops.skinny_up(lat=ws["evb"]["ds"], w=self.method.state(self, dG0.device)["We"], out=ig["dxc"], M=BN, C=C, L=self.Lp, w_layout=1, accumulate=1)
         if self.kind == "ssf":                             # y = s o conv(img) + t (ssf.py:229-232): the operand is s o W, as the forward's
             ops.ssf_fold_weight(self.p[self.names.conv() + ".weight"].detach().reshape(C, Kp), self.p["ssf_scale_1"].detach(), w["conv"], w["conv_t"])
         a = ig["dxc"] if self.fp32 else ops.to_operand(ig["dxc"], ig["dxc16"], self.adt)
         ops.gemm_nt(a, w["conv_t"], BN, ig["dcols"], epilogue=ops.EPI_STORE_F32)
         if self.kind == "evp":
-            st = self._evp_state(dG0.device)
+            st = self.method.state(self, dG0.device)
             # hc = hcols . Wp^T + bp, s = hc[:, :Lp] + e  ->  d hcols = ds . Wp (rows >= r of Wp are zero); fp32 as the forward's GEMM
             ops.pad2d(ws["evb"]["ds"], BN, self.Lp, ig["dhc"], BN, 64)
             ops.transpose_any(st["Wp"], st["WpT"], 64, Kp)

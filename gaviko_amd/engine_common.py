@@ -1,7 +1,7 @@
-"""Constants, switches and small helpers shared by the launch-plan engine (engine.py) and its halves (engine_gaviko.py: the MWSA / GPA
-side paths; engine_peft.py: AdaptFormer, LoRA, unfrozen-backbone gradients, EVP, DVPT, SSF; engine_analysis.py: the entry points of
-gaviko_amd.explain / uncertainty / features).  The per-kind static facts -- geometry, flags, buffers, name patterns -- live in
-engine_methods.py; `Names` here turns its patterns into state_dict names."""
+"""Constants, switches and small helpers shared by the launch-plan engine (engine.py), its halves (engine_gaviko.py: the MWSA / GPA
+side paths; engine_peft.py: unfrozen-backbone gradients; engine_analysis.py: the entry points of gaviko_amd.explain / uncertainty /
+features) and the per-method specs (engine_methods.py: geometry, flags, buffers, name patterns and every launch of a method's own).
+`Names` here turns a spec's patterns into state_dict names.  Imports nothing of the engine, so every engine module may import it."""
 from __future__ import annotations
 
 import os
@@ -9,7 +9,6 @@ import os
 import torch
 
 from . import lib as L
-from .engine_methods import METHOD_SPECS
 
 # How a step is issued after the GRAPH_WARMUP eager passes (env GAVIKO_HIP_GRAPHS):
 #   "plan"  (default, also "1") -- the library's launch plan: recorded once, replayed from one C loop on the real streams
@@ -82,9 +81,8 @@ class Names:
     """Maps logical backbone tensors to the state_dict names of each reference class, from the name patterns of the
     kind's spec (engine_methods.py)."""
 
-    def __init__(self, kind: str, lora_layers=None):
-        spec = METHOD_SPECS[kind]
-        self.kind, self.root, self.wraps_qkv = kind, spec.root, spec.wraps_qkv
+    def __init__(self, spec, lora_layers=None):
+        self.root, self.wraps_qkv = spec.root, spec.wraps_qkv
         self.lora_layers = None if lora_layers is None else frozenset(lora_layers)     # MeLO: layers whose to_qkv is wrapped (melo.py:53-68)
         self._attn, self._mlp = self.root + spec.attn_name, self.root + spec.mlp_name  # "%d" = the layer
         self._conv, self._head = self.root + spec.conv_name, self.root + spec.head_name

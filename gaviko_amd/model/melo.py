@@ -3,7 +3,7 @@
 `MeLO(vit=VisionTransformer(**cfg), **cfg)` as in train.py:148-150.  Parameter names follow the reference's wrapping
 (`lora_vit.transformer.layers.{i}.0.to_qkv.{qkv,linear_a_q,linear_b_q,linear_a_v,linear_b_v}.weight`, melo.py:66-87) and the
 head is re-created (90-91).  On the MI355X path the rank-r update is folded into the bf16 QKV operand every step
-(engine._melo_merge), so the forward is the plain MFMA GEMM; the integer scale alpha // r of melo.py:45-46 is kept.
+(engine_methods.MeloSpec.fwd_embedded), so the forward is the plain MFMA GEMM; the integer scale alpha // r of melo.py:45-46 is kept.
 """
 from __future__ import annotations
 

@@ -175,14 +175,14 @@ def _dict_literal_keys(node):
 
 
 def _is_gemm_call(node, names):
-    """a call of ops.gemm_nt, or of self._gemm (the engine's wrapper around it)"""
+    """a call of ops.gemm_nt, or of the engine's wrapper around it: self._gemm in the engine, eng._gemm in a method spec's hook"""
     if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name)):
         return False
     return (node.func.value.id, node.func.attr) in names
 
 
 def engine_gemm_parameters():
-    """gemm_nt parameter names the engine modules pass: keywords of self._gemm / ops.gemm_nt calls, and the keys of the dict(...) literals
+    """gemm_nt parameter names the engine modules pass: keywords of self._gemm / eng._gemm / ops.gemm_nt calls, and the keys of the dict(...) literals
     behind every **name of those calls (looked up in the enclosing function; a spliced name with no literal must be a panel carrier)."""
     params = _gemm_nt_parameters()
     passed, unresolved = set(), set()
@@ -207,7 +207,7 @@ def engine_gemm_parameters():
                         if isinstance(t, ast.Name):
                             assigned.setdefault(t.id, set()).update(_dict_literal_keys(sub.value))
             for sub in ast.walk(fn):
-                if not _is_gemm_call(sub, {("self", "_gemm"), ("ops", "gemm_nt")}):
+                if not _is_gemm_call(sub, {("self", "_gemm"), ("eng", "_gemm"), ("ops", "gemm_nt")}):
                     continue
                 for k in sub.keywords:
                     if k.arg is not None:
