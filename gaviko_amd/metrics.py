@@ -396,6 +396,176 @@ def risk_coverage(score: torch.Tensor, labels: torch.Tensor, pred: torch.Tensor,
                         stratified=bool(stratified), level=float(level))
 
 
+class PredictionSets(NamedTuple):
+    mask: np.ndarray                       # bool [N, K]: class k is in the set of row n
+    size: np.ndarray                       # int64 [N]
+
+
+class ConformalPredictor(NamedTuple):
+    qhat: np.ndarray                       # float32 [K]: class k is in a row's set when its score <= qhat[k] (one value repeated when not mondrian); may be +inf
+    alpha: float                           # the miscoverage asked for
+    level: float                           # 1 - alpha, the coverage the sets are built for
+    n: int                                 # calibration rows
+    score: str                             # 'lac', 'aps' or 'raps'
+    params: Dict[str, object]              # randomized, seed, k_reg, lam: what conformal_scores was called with
+    mondrian: bool
+
+    def sets(self, proba: torch.Tensor) -> PredictionSets:
+        """The prediction sets of new rows: proba f32 [N, K] on the device -> mask[n, k] = score[n, k] <= qhat[k], the rule
+        gvk_conformal_splits counts the test rows by.  An infinite qhat[k] (too few calibration rows for this alpha) puts k in every set."""
+        s = conformal_scores(proba, score=self.score, **self.params)
+        if s.shape[1] != self.qhat.size:
+            raise GavikoHipError(f"ConformalPredictor.sets: {s.shape[1]} classes, calibrated on {self.qhat.size}")
+        mask = (s <= torch.from_numpy(self.qhat).to(s.device)[None, :]).cpu().numpy()
+        return PredictionSets(mask=mask, size=mask.sum(1).astype(np.int64))
+
+
+class ConformalEvaluation(NamedTuple):
+    alphas: Tuple[float, ...]              # the Q miscoverage levels
+    coverage: np.ndarray                   # float64 [R, Q]: covered test rows / test rows of every split
+    mean_size: np.ndarray                  # float64 [R, Q]: mean set size over the test rows of every split
+    coverage_mean: np.ndarray              # float64 [Q]: mean over the splits
+    coverage_ci: List[Tuple[float, float]]     # per level, the percentile interval of coverage over the splits
+    mean_size_mean: np.ndarray             # float64 [Q]
+    mean_size_ci: List[Tuple[float, float]]
+    singleton: np.ndarray                  # float64 [Q]: share of test rows (all splits pooled) whose set has exactly one class
+    empty: np.ndarray                      # float64 [Q]: ... whose set is empty
+    size_hist: np.ndarray                  # int64 [Q, K + 1]: test rows by set size, all splits pooled
+    coverage_by_size: np.ndarray           # float64 [Q, K + 1]: size-stratified coverage, all splits pooled; NaN where no test row had the size
+    class_coverage: np.ndarray             # float64 [R, Q, K]: coverage among the test rows of every label; NaN where a split has none
+    class_undefined: np.ndarray            # int64 [K]: splits whose test half has no row of the label
+    infinite: np.ndarray                   # float64 [Q]: share of the (split, segment) thresholds that are +inf
+    qhat: np.ndarray                       # float32 [R, Q, G]: the thresholds as scores (+inf where a segment has too few calibration rows)
+    seed: int
+    n_cal: int
+    n_test: int
+    mondrian: bool
+    score: str
+    level: float
+    counts: Dict[str, np.ndarray]          # the device's integers: qpos [R, Q, G], n_seg [R, G], size_hist / covered_by_size [R, Q, K + 1],
+                                           # class_test [R, K], class_covered [R, Q, K]
+
+
+def _conformal_shape(what: str, proba, labels) -> Tuple[int, int]:
+    if not isinstance(proba, torch.Tensor) or proba.dim() != 2 or proba.shape[0] < 1:
+        raise GavikoHipError(f"{what}: expected proba [N, K], got {tuple(proba.shape) if isinstance(proba, torch.Tensor) else type(proba).__name__}")
+    N, K = proba.shape
+    if N > ops.BOOTSTRAP_MAX_ROWS or not 2 <= K <= ops.CONFORMAL_MAX_CLASSES:
+        raise GavikoHipError(f"{what}: N = {N}, K = {K} outside N <= {ops.BOOTSTRAP_MAX_ROWS}, 2 <= K <= {ops.CONFORMAL_MAX_CLASSES}")
+    if torch.as_tensor(labels).numel() != N:
+        raise GavikoHipError(f"{what}: {torch.as_tensor(labels).numel()} labels for {N} rows of probabilities")
+    return N, K
+
+
+def _conformal_labels(what: str, proba, labels) -> torch.Tensor:
+    if not proba.is_cuda:
+        raise GavikoHipError(f"{what}: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    labels = torch.as_tensor(labels).to(proba.device).to(torch.int64).contiguous().reshape(proba.shape[0])
+    if int(labels.min()) < 0 or int(labels.max()) >= proba.shape[1]:
+        raise GavikoHipError(f"{what}: labels outside [0, {proba.shape[1]})")
+    return labels
+
+
+def _conformal_alphas(what: str, alphas) -> List[float]:
+    try:
+        a = [float(x) for x in alphas]
+    except TypeError:
+        raise GavikoHipError(f"{what}: alphas = {alphas!r} (a sequence of numbers within (0, 1))") from None
+    if not a or any(not 0.0 < x < 1.0 for x in a):
+        raise GavikoHipError(f"{what}: alphas = {alphas!r} (at least one, each within (0, 1))")
+    return a
+
+
+def conformal_scores(proba: torch.Tensor, *, score: str = "lac", randomized: bool = False, seed: int = 0, k_reg: int = 1,
+                     lam: float = 0.01) -> torch.Tensor:
+    """Nonconformity scores for split conformal prediction, f32 [N, K] on the device (a row-major VIEW of the class-major [K, N] buffer
+    gvk_conformal_scores writes): low = the class conforms.  proba f32 [N, K] on the device, 2 <= K <= 64, no NaN.  With the classes of a
+    row ranked by descending probability (ties: the lower class index first):
+      'lac'  (Sadinle et al., 2019)       1 - p_k: the smallest sets on average
+      'aps'  (Romano et al., 2020)        the probability mass of the classes ranked at or above k, added in rank order: adaptive sets.
+                                          randomized=True counts the class's own mass only u_n times, u_n in [0, 1) from (seed, row)
+      'raps' (Angelopoulos et al., 2021)  aps + lam * max(0, rank_k + 1 - k_reg), rank_k 0-based: a penalty that keeps the tail out
+    Every operation is one float32 rounding (tests/conformal_ref.py restates the bits in numpy)."""
+    if not isinstance(proba, torch.Tensor):
+        raise GavikoHipError(f"conformal_scores: expected proba [N, K], got {type(proba).__name__}")
+    if proba.is_cuda:
+        proba = proba.detach().float().contiguous()
+    return ops.conformal_scores(proba, score, bool(randomized), seed, k_reg, lam).t()
+
+
+def conformal_calibrate(proba: torch.Tensor, labels: torch.Tensor, *, alpha: float = 0.1, mondrian: bool = False, score: str = "lac",
+                        randomized: bool = False, seed: int = 0, k_reg: int = 1, lam: float = 0.01) -> ConformalPredictor:
+    """Split conformal calibration (Angelopoulos & Bates, 2021) on held-out rows: proba f32 [N, K] on the device, labels [N] within [0, K).
+    The threshold is the m-th smallest true-class score of the n calibration rows, m = ceil((n + 1)(1 - alpha)) in float64; the sets
+    {k : score_k <= qhat} of exchangeable new rows then contain the label with probability >= 1 - alpha.  m > n (too few rows for this alpha)
+    gives qhat = +inf: every class in every set.  mondrian=True calibrates every class on its own rows (class-conditional coverage; a class with
+    fewer than ceil(1 / alpha) - 1 calibration rows gets +inf).  gvk_conformal_splits computes the thresholds (n_cal = N, one replicate)."""
+    N, K = _conformal_shape("conformal_calibrate", proba, labels)
+    a = _conformal_alphas("conformal_calibrate", [alpha])
+    labels = _conformal_labels("conformal_calibrate", proba, labels)
+    params = {"randomized": bool(randomized), "seed": int(seed), "k_reg": k_reg, "lam": float(lam)}
+    s = conformal_scores(proba, score=score, **params).t()
+    tables = ops.conformal_tables(s, labels, bool(mondrian))
+    qpos = ops.conformal_splits(s, labels, tables, a, N, 1, 0)["qpos"].cpu().numpy()[0, 0]
+    sorted_score = tables["sorted_score"].cpu().numpy()
+    qhat = np.where(qpos >= 0, sorted_score[np.maximum(qpos, 0)], np.float32(np.inf)).astype(np.float32)
+    return ConformalPredictor(qhat=np.broadcast_to(qhat, (K,)).copy(), alpha=a[0], level=1.0 - a[0], n=N, score=score, params=params,
+                              mondrian=bool(mondrian))
+
+
+def conformal_evaluate(proba: torch.Tensor, labels: torch.Tensor, *, alphas=(0.1,), n_cal: Optional[int] = None, calibration_fraction: float = 0.5,
+                       replicates: int = 1000, seed: int = 0, mondrian: bool = False, score: str = "lac", randomized: bool = False,
+                       k_reg: int = 1, lam: float = 0.01, level: float = 0.95) -> ConformalEvaluation:
+    """How a conformal method behaves on this evaluation set, over `replicates` random calibration/test splits (Angelopoulos & Bates, 2021,
+    section 3): every split calibrates on n_cal rows (default floor(calibration_fraction N), within [1, N - 1]) and builds the sets of the
+    other N - n_cal.  proba f32 [N, K] on the device, labels [N] within [0, K); any number of `alphas` (8 per launch, the same seed and so
+    the same splits in every launch).  Split b: the n_cal rows with the smallest keys (hash_u32(seed, b N + i) & ~0x1FFF) | i.
+    Reported per level: coverage and mean set size of every split, their means and percentile intervals at `level`, singleton / empty rates,
+    the set-size histogram, coverage by set size and per class, and how often a threshold was +inf (a segment with too few calibration rows:
+    under mondrian=True a class needs at least ceil(1 / alpha) - 1 of them).  Marginal coverage of a split has expectation
+    ceil((n_cal + 1)(1 - alpha)) / (n_cal + 1) when scores do not tie.  gvk_conformal_splits counts everything in exact integers on the device.
+    N <= 8192, 2 <= K <= 64."""
+    N, K = _conformal_shape("conformal_evaluate", proba, labels)
+    a = _conformal_alphas("conformal_evaluate", alphas)
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1:
+        raise GavikoHipError(f"conformal_evaluate: replicates = {replicates!r} (an integer >= 1)")
+    if not 0.0 < float(level) < 1.0:
+        raise GavikoHipError(f"conformal_evaluate: level = {level!r} outside (0, 1)")
+    if N < 2:
+        raise GavikoHipError("conformal_evaluate: a split needs at least 2 rows")
+    if n_cal is None:
+        if not 0.0 < float(calibration_fraction) < 1.0:
+            raise GavikoHipError(f"conformal_evaluate: calibration_fraction = {calibration_fraction!r} outside (0, 1)")
+        n_cal = min(N - 1, max(1, int(float(calibration_fraction) * N)))
+    if isinstance(n_cal, bool) or not isinstance(n_cal, int) or not 1 <= n_cal <= N - 1:
+        raise GavikoHipError(f"conformal_evaluate: n_cal = {n_cal!r} (an integer within [1, {N - 1}]: every split needs test rows)")
+    labels = _conformal_labels("conformal_evaluate", proba, labels)
+    R, Q, n_test = replicates, len(a), N - n_cal
+    s = conformal_scores(proba, score=score, randomized=randomized, seed=seed, k_reg=k_reg, lam=lam).t()
+    tables = ops.conformal_tables(s, labels, bool(mondrian))
+    parts = [ops.conformal_splits(s, labels, tables, a[i:i + ops.CONFORMAL_MAX_LEVELS], n_cal, R, seed) for i in range(0, Q, ops.CONFORMAL_MAX_LEVELS)]
+    counts = {k: np.concatenate([p[k].cpu().numpy() for p in parts], 1) if parts[0][k].dim() == 3 else parts[0][k].cpu().numpy() for k in parts[0]}
+    sorted_score = tables["sorted_score"].cpu().numpy()
+    qpos = counts["qpos"]
+    qhat = np.where(qpos >= 0, sorted_score[np.maximum(qpos, 0)], np.float32(np.inf)).astype(np.float32)
+    hist, cov_hist = counts["size_hist"].astype(np.int64), counts["covered_by_size"].astype(np.int64)
+    sizes = np.arange(K + 1, dtype=np.float64)
+    coverage = cov_hist.sum(2) / float(n_test)
+    mean_size = (hist * sizes).sum(2) / float(n_test)
+    pooled, pooled_cov = hist.sum(0), cov_hist.sum(0)
+    cls_test = counts["class_test"].astype(np.float64)[:, None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        by_size = np.where(pooled > 0, pooled_cov / pooled.astype(np.float64), np.nan)
+        by_class = np.where(cls_test > 0, counts["class_covered"] / cls_test, np.nan)
+    return ConformalEvaluation(alphas=tuple(a), coverage=coverage, mean_size=mean_size, coverage_mean=coverage.mean(0),
+                               coverage_ci=[_interval(coverage[:, q], float(level)) for q in range(Q)], mean_size_mean=mean_size.mean(0),
+                               mean_size_ci=[_interval(mean_size[:, q], float(level)) for q in range(Q)],
+                               singleton=pooled[:, 1] / float(R * n_test), empty=pooled[:, 0] / float(R * n_test), size_hist=pooled,
+                               coverage_by_size=by_size, class_coverage=by_class, class_undefined=(counts["class_test"] == 0).sum(0).astype(np.int64),
+                               infinite=(qpos < 0).mean((0, 2)), qhat=qhat, seed=int(seed), n_cal=int(n_cal), n_test=int(n_test),
+                               mondrian=bool(mondrian), score=score, level=float(level), counts=counts)
+
+
 _bootstrap = bootstrap                                     # Evaluator.compute has a parameter of that name
 
 
@@ -410,12 +580,14 @@ class Evaluator:
         self._labels.append(labels.detach().to(torch.int64))
 
     def compute(self, bootstrap: Optional[int] = None, seed: int = 0, stratified: bool = False, *, selective: bool = False,
-                temperature: Optional[float] = None) -> Dict[str, object]:
+                temperature: Optional[float] = None, conformal=None) -> Dict[str, object]:
         """bootstrap = R adds "bootstrap" (the BootstrapResult of R replicates with this seed and rule, on the probabilities and predictions
         computed here) and "report" (classification_report of the confusion matrix); None returns the keys eval.py needs and "calibration".
         selective = True adds "selective": the RiskCoverage of the max-probability confidence, with R replicates of the same seed and rule
         when bootstrap = R.  temperature = T > 0 (fit_temperature on validation rows) takes the probabilities, and with them "auc",
-        "calibration", "bootstrap" and "selective", from logits / T; the predictions and the confusion matrix stay those of the logits."""
+        "calibration", "bootstrap" and "selective", from logits / T; the predictions and the confusion matrix stay those of the logits.
+        conformal = alpha (or a sequence of them) adds "conformal": the ConformalEvaluation of the lac score over random halves of these rows
+        (conformal_evaluate with this seed; `bootstrap` replicates when given, else 1000), on the probabilities computed here."""
         logits = torch.cat(self._logits).contiguous()
         labels = torch.cat(self._labels).contiguous().to(self.device)
         N, K = logits.shape
@@ -447,6 +619,9 @@ class Evaluator:
             out["report"] = classification_report(conf)
         if selective:
             out["selective"] = risk_coverage(proba.max(1).values, labels, pred, replicates=bootstrap, seed=seed, stratified=stratified)
+        if conformal is not None:
+            out["conformal"] = conformal_evaluate(proba, labels, alphas=conformal if isinstance(conformal, (list, tuple)) else (conformal,),
+                                                  replicates=1000 if bootstrap is None else bootstrap, seed=seed)
         return out
 
 

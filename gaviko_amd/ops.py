@@ -1796,6 +1796,112 @@ def temperature_fit(logits: torch.Tensor, target: torch.Tensor, t_min: float = 0
     return state
 
 
+# ---- split-conformal prediction sets (csrc/conformal.hip) ----
+CONFORMAL_MAX_CLASSES = 64      # gvk_conformal_scores: one class per lane of a wave
+CONFORMAL_MAX_LEVELS = 8        # gvk_conformal_splits: miscoverage levels answered per launch
+CONFORMAL_KINDS = {"lac": 0, "aps": 1, "raps": 2}
+
+
+def conformal_scores(proba: torch.Tensor, kind: str = "lac", randomized: bool = False, seed: int = 0, k_reg: int = 1, lam: float = 0.01,
+                     scores: torch.Tensor = None) -> torch.Tensor:
+    """proba f32 [N, K] -> scores f32 [K, N] (class-major), the nonconformity scores of include/gaviko_hip.h: kind 'lac' (1 - p), 'aps' (the
+    probability mass down to and including the class, in rank order; randomized=True: u_n of the class's own mass, u_n from (seed, row)) or
+    'raps' (aps + lam * max(0, rank + 1 - k_reg)).  2 <= K <= 64; NaN probabilities are the caller's contract."""
+    if not isinstance(proba, torch.Tensor):
+        raise L.GavikoHipError(f"conformal_scores proba: expected a tensor, got {type(proba).__name__}")
+    if proba.dim() != 2 or proba.shape[0] < 1:
+        raise L.GavikoHipError(f"conformal_scores proba: expected [N, K], got {tuple(proba.shape)}")
+    N, K = proba.shape
+    if not 2 <= K <= CONFORMAL_MAX_CLASSES:
+        raise L.GavikoHipError(f"conformal_scores: K = {K} classes outside [2, {CONFORMAL_MAX_CLASSES}] (one class per lane)")
+    if N * K >= 1 << 31:
+        raise L.GavikoHipError(f"conformal_scores: N = {N} rows exceed the kernel's 32-bit row index")
+    if kind not in CONFORMAL_KINDS:
+        raise L.GavikoHipError(f"conformal_scores: kind = {kind!r} (one of {sorted(CONFORMAL_KINDS)})")
+    if randomized and kind == "lac":
+        raise L.GavikoHipError("conformal_scores: lac has no randomised form")
+    if isinstance(k_reg, bool) or not isinstance(k_reg, int) or k_reg < 0:
+        raise L.GavikoHipError(f"conformal_scores: k_reg = {k_reg!r} (an integer >= 0)")
+    lam = float(lam)
+    if not 0.0 <= lam < float("inf"):
+        raise L.GavikoHipError(f"conformal_scores: lam = {lam!r} (a finite number >= 0)")
+    _chk(proba, torch.float32, "conformal_scores proba")
+    if scores is None:
+        scores = torch.empty((K, N), dtype=torch.float32, device=proba.device)
+    _chk(scores, torch.float32, "conformal_scores scores")
+    if tuple(scores.shape) != (K, N):
+        raise L.GavikoHipError(f"conformal_scores scores: expected [{K}, {N}] (class-major), got {tuple(scores.shape)}")
+    L.launch.gvk_conformal_scores(proba, scores, N, K, CONFORMAL_KINDS[kind], 1 if randomized else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, min(k_reg, K + 1),
+                                  lam)
+    return scores
+
+
+def conformal_tables(scores: torch.Tensor, labels: torch.Tensor, mondrian: bool = False) -> dict:
+    """The per-call tables of gvk_conformal_splits, built with torch (plumbing: once per call, not per replicate).  scores f32 [K, N]
+    (class-major, no NaN), labels i64 [N] within [0, K) -> order i32 [N] (the rows grouped by segment -- one segment, or with mondrian=True one
+    per label -- and inside a segment ascending by true-class score, stable), seg_off i32 [G + 1], and sorted_score f32 [N] (the true-class
+    score of the row at every sorted position: what a qpos of the kernel stands for)."""
+    K, N = scores.shape
+    true = scores[labels, torch.arange(N, device=scores.device)]
+    order = torch.sort(true, stable=True).indices
+    if mondrian:
+        order = order[torch.sort(labels[order], stable=True).indices]
+        off = torch.zeros(K + 1, dtype=torch.int64, device=scores.device)
+        off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
+    else:
+        off = torch.tensor([0, N], dtype=torch.int64, device=scores.device)
+    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
+    return {"order": i32(order), "seg_off": i32(off), "sorted_score": true[order].contiguous()}
+
+
+def conformal_splits(scores: torch.Tensor, labels: torch.Tensor, tables: dict, alphas, n_cal: int, replicates: int = 1, seed: int = 0) -> dict:
+    """`replicates` random splits of the N rows into n_cal calibration rows and N - n_cal test rows (n_cal = N: no test rows), the conformal
+    thresholds of every segment at up to 8 miscoverage levels `alphas` (host floats within (0, 1)) and the test rows' set-size and coverage
+    counts; include/gaviko_hip.h has the definitions.  scores f32 [K, N] = conformal_scores(...), labels i64 [N], tables =
+    conformal_tables(scores, labels, mondrian).  -> dict of int32 device tensors: qpos [R, Q, G], n_seg [R, G], size_hist / covered_by_size
+    [R, Q, K + 1], class_test [R, K], class_covered [R, Q, K].  N <= 8192, 2 <= K <= 64."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise L.GavikoHipError(f"conformal_splits scores: expected a class-major [K, N] tensor, got "
+                               f"{tuple(scores.shape) if isinstance(scores, torch.Tensor) else type(scores).__name__}")
+    K, N = scores.shape
+    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
+        raise L.GavikoHipError(f"conformal_splits: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+    if not 2 <= K <= CONFORMAL_MAX_CLASSES:
+        raise L.GavikoHipError(f"conformal_splits: K = {K} classes outside [2, {CONFORMAL_MAX_CLASSES}]")
+    R = replicates
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise L.GavikoHipError(f"conformal_splits: replicates = {R!r} (an integer >= 1)")
+    if isinstance(n_cal, bool) or not isinstance(n_cal, int) or not 1 <= n_cal <= N:
+        raise L.GavikoHipError(f"conformal_splits: n_cal = {n_cal!r} (an integer within [1, {N}])")
+    try:
+        alphas = [float(a) for a in alphas]
+    except TypeError:
+        raise L.GavikoHipError(f"conformal_splits: alphas = {alphas!r} (a sequence of numbers)") from None
+    Q = len(alphas)
+    if not 1 <= Q <= CONFORMAL_MAX_LEVELS:
+        raise L.GavikoHipError(f"conformal_splits: Q = {Q} levels outside [1, {CONFORMAL_MAX_LEVELS}] per launch")
+    if any(not 0.0 < a < 1.0 for a in alphas):
+        raise L.GavikoHipError(f"conformal_splits: alphas = {alphas!r} (each within (0, 1))")
+    seg_off = tables.get("seg_off")
+    if seg_off is None or seg_off.numel() not in (2, K + 1):
+        raise L.GavikoHipError(f"conformal_splits seg_off: expected an int32 [2] (marginal) or [{K + 1}] (one segment per class) table")
+    G = seg_off.numel() - 1
+    _chk(scores, torch.float32, "conformal_splits scores")
+    _chk(labels, torch.int64, "conformal_splits labels")
+    if labels.numel() != N:
+        raise L.GavikoHipError(f"conformal_splits labels: expected {N} labels, got {tuple(labels.shape)}")
+    _tab(tables.get("order"), "conformal_splits order", N)
+    _tab(seg_off, "conformal_splits seg_off", G + 1)
+    dev = scores.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)   # noqa: E731
+    out = {"qpos": i32(R, Q, G), "n_seg": i32(R, G), "size_hist": i32(R, Q, K + 1), "covered_by_size": i32(R, Q, K + 1), "class_test": i32(R, K),
+           "class_covered": i32(R, Q, K)}
+    alphas_d = torch.tensor(alphas, dtype=torch.float64, device=dev)
+    L.launch.gvk_conformal_splits(scores, labels, tables["order"], seg_off, alphas_d, out["qpos"], out["n_seg"], out["size_hist"], out["covered_by_size"],
+                                  out["class_test"], out["class_covered"], N, K, Q, G, n_cal, R, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return out
+
+
 # ---- feature embeddings and kNN probes (csrc/features.hip) ----
 FEATURE_MAX_DIM = 1024          # gvk_token_pool / gvk_feature_topk: C % 4 == 0, C <= 1024
 TOPK_MAX_K = 32                 # gvk_feature_topk / gvk_knn_vote: sorted lists of at most 32 entries

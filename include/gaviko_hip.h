@@ -932,6 +932,51 @@ int gvk_risk_coverage(const void* labels, const int32_t* pred, const int32_t* or
                       int32_t* errors, int N, int K, int Q, int R, uint64_t seed, int stratified, int resample, void* stream);
 int gvk_temperature_fit(const float* logits, const void* target, double* state, int N, int K, double t_min, double t_max, void* stream);
 
+/* ---- split-conformal prediction sets (csrc/conformal.hip; gaviko_amd.metrics.conformal_scores / conformal_calibrate / conformal_evaluate) ----
+ * gvk_conformal_scores: proba f32 [N][K] -> scores f32 [K][N] (CLASS-MAJOR: gvk_conformal_splits reads a class column over consecutive rows).
+ *   Rank of class k in its row, 0-based:  r_k = #{j : p_j > p_k or (p_j == p_k and j < k)}  (ties go to the lower class index); pi(r) = the
+ *   class of rank r.  Every operation below is ONE fp32 rounding, never contracted into an FMA (a numpy float32 restatement gives the bits):
+ *     kind GVK_CONFORMAL_LAC  (Sadinle et al., 2019):       s_k = 1 - p_k
+ *     kind GVK_CONFORMAL_APS  (Romano et al., 2020):        c_0 = 0, c_{r+1} = c_r + p_pi(r), added sequentially in rank order;
+ *                                                           randomized = 0: s_pi(r) = c_{r+1};  randomized = 1: s_pi(r) = c_r + (u_n * p_pi(r))
+ *                                                           with one u_n = float(hash_u32(seed, n) >> 8) * 2^-24 per row (hash_u32 of
+ *                                                           csrc/dropout.hpp; u_n in [0, 1), exact)
+ *     kind GVK_CONFORMAL_RAPS (Angelopoulos et al., 2021):  s = aps + (lam * float(max(0, r + 1 - k_reg))),  lam >= 0, k_reg >= 0
+ *   One wave per row, one class per lane, no atomics.  N >= 1, 2 <= K <= GVK_CONFORMAL_MAX_CLASSES; randomized = 1 needs aps or raps; seed,
+ *   k_reg and lam are read by the kinds that name them.  NaN probabilities are the caller's contract.
+ * gvk_conformal_splits: R random calibration/test splits of the N rows of an evaluation set, one 256-thread workgroup per replicate b.
+ *   scores f32 [K][N] (as written above), labels int64 [N] within [0, K) (clamped), alphas f64 [Q] miscoverage levels within (0, 1), all on
+ *   the DEVICE, and two DEVICE tables computed once per call by the caller (int32):
+ *     order [N]                     the rows grouped by segment, inside a segment ascending by TRUE-class score scores[labels[i]][i] (a stable
+ *                                   sort: equal scores in row order).  G = 1: one segment (marginal); G = K: segment = label (class-conditional,
+ *                                   "Mondrian")
+ *     seg_off [G+1]                 where each segment starts in `order`
+ *   Split rule:  key_i = (hash_u32(seed, b*N + i) & ~0x1FFF) | i  -- distinct, the row index fits the low 13 bits -- and the calibration rows of
+ *   replicate b are the n_cal rows with the smallest keys (numpy: argsort(keys)[:n_cal]); the rest are test rows.  n_cal = N: every row
+ *   calibrates, no test rows (how a predictor is calibrated on a whole set).  A replicate depends on (seed, b, N, n_cal) only.
+ *   Threshold of segment g with n_g calibration rows at level q, in float64 with exactly this expression:
+ *     m = (int)ceil((double)(n_g + 1) * (1.0 - alphas[q]))   (at least 1);   m > n_g: qhat = +inf, qpos = -1;   else qhat = the true-class score of
+ *     the m-th calibration row of the segment in sorted order, qpos = its position in `order`
+ *   Every test row i and level q:  size = #{k : scores[k][i] <= qhat[q][g(k)]},  covered = scores[y_i][i] <= qhat[q][g(y_i)],  g(k) = 0 (G = 1) or
+ *   k (G = K).  Written per replicate, never accumulated, int32:
+ *     qpos [R][Q][G]                see above
+ *     n_seg [R][G]                  n_g
+ *     size_hist [R][Q][K+1]         test rows by set size
+ *     covered_by_size [R][Q][K+1]   covered test rows by set size
+ *     class_test [R][K]             test rows by label
+ *     class_covered [R][Q][K]       covered test rows by label
+ *   The selection is a 4-pass radix select of the n_cal-th smallest key, the order statistic one inclusive scan of the membership flags over
+ *   `order` in tiles of 1024, the histograms LDS integer atomics; no atomics on global memory: exact integers, the same on every run.
+ *   1 <= N <= GVK_BOOTSTRAP_MAX_ROWS, 2 <= K <= GVK_CONFORMAL_MAX_CLASSES, 1 <= Q <= GVK_CONFORMAL_MAX_LEVELS, G in {1, K}, 1 <= n_cal <= N,
+ *   R >= 1 (the grid's x dimension).  LDS: 8 * ceil(N / 1024) * 1024 + 14176 bytes. */
+enum { GVK_CONFORMAL_MAX_CLASSES = 64, GVK_CONFORMAL_MAX_LEVELS = 8 };
+enum { GVK_CONFORMAL_LAC = 0, GVK_CONFORMAL_APS = 1, GVK_CONFORMAL_RAPS = 2 };
+int gvk_conformal_scores(const float* proba, float* scores, int N, int K, int kind, int randomized, uint64_t seed, int k_reg, float lam,
+                         void* stream);
+int gvk_conformal_splits(const float* scores, const void* labels, const int32_t* order, const int32_t* seg_off, const double* alphas,
+                         int32_t* qpos, int32_t* n_seg, int32_t* size_hist, int32_t* covered_by_size, int32_t* class_test, int32_t* class_covered,
+                         int N, int K, int Q, int G, int n_cal, int R, uint64_t seed, void* stream);
+
 /* ---- feature embeddings and kNN probes (csrc/features.hip; gaviko_amd/features.py) ----
  * All fp32, no atomics, every sum in a fixed order: two runs are bit-identical.
  * gvk_token_pool: out f32 [B][C], out[b][c] = (1/R) sum_{r in [r0, r0+R)} g[b][r][c] of a token stream g f32 [B][T][C] (row pitch C).
