@@ -7,15 +7,13 @@
 // replicate is a prefix sum: P = inclusive scan of the negatives' weights in sorted order, and a positive at sorted position s adds
 //   w (2 P[gstart - 1] + (P[gend - 1] - P[gstart - 1])) = w (P[gstart - 1] + P[gend - 1]),     P[-1] = 0
 // -- O(N) per class and replicate, against O(N^2) for counting pairs.  Everything is an integer: the order of the atomics changes nothing.
-#include "common.hpp"
-#include "dropout.hpp"
+#include "replicate.hpp"
 #include "../../include/gaviko_hip.h"
 
 namespace gvk {
 
 constexpr int kBootMaxN = GVK_BOOTSTRAP_MAX_ROWS;               // multiplicities stay below 2^24 (the label shares their LDS word), two N-entry LDS arrays
 constexpr int kBootMaxK = GVK_BOOTSTRAP_MAX_CLASSES;            // the label takes the 8 bits above them; K x K counters in LDS
-constexpr int kBootTile = 1024;                                  // scan tile: 256 threads x 4 consecutive entries (one 16-byte LDS access each)
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
@@ -26,10 +24,10 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 // One 256-thread workgroup per replicate.  LDS (dynamic): wl[Npad] | P[Npad] | conf[K * K], Npad = N rounded up to the scan tile.
 //   wl[row] = label << 24 | multiplicity: the label is laid down first, the N draws of the replicate add 1 each (32-bit LDS atomics; a
 //   multiplicity is at most N <= 8192, so it never reaches the label), and every later pass gets both from one LDS read.
-// Per class c: P[s] = weight of the row at sorted position s if it is a negative, else 0; inclusive scan of P in tiles of 1024 (4 entries per
-// thread, wave64 shuffle scan of the thread totals, the 4 wave totals and the running carry through LDS); the positives' sums; a block
-// reduction; plain stores.  Every index read from a table is clamped or tested before it addresses LDS: the tables are the caller's contract
-// (ops.bootstrap_counts builds them), a broken one gives wrong counts, never an access outside the arrays.
+// Per class c: P[s] = weight of the row at sorted position s if it is a negative, else 0; inclusive scan of P (block_scan_tiles_u32 of
+// replicate.hpp); the positives' sums; a block reduction; plain stores.  Every index read from a table is clamped or tested before it
+// addresses LDS: the tables are the caller's contract (ops.bootstrap_counts builds them), a broken one gives wrong counts, never an access
+// outside the arrays.
 __global__ __launch_bounds__(256) void bootstrap_counts_kernel(const long long* __restrict__ labels, const int* __restrict__ pred,
                                                                const int* __restrict__ order, const int* __restrict__ gstart,
                                                                const int* __restrict__ gend, const int* __restrict__ class_rows,
@@ -51,22 +49,7 @@ __global__ __launch_bounds__(256) void bootstrap_counts_kernel(const long long* 
   }
   for (int i = t; i < K * K; i += 256) conf[i] = 0u;
   __syncthreads();
-  for (int n = t; n < N; n += 256) {
-    const unsigned long long h = hash_u32(seed, b * (unsigned long long)N + (unsigned long long)n);
-    int j;
-    if (stratified) {
-      const long long y = labels[n];
-      const int c = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);
-      const int o0 = class_off[c], nc = class_off[c + 1] - o0;
-      int q = o0 + (int)((h * (unsigned long long)(nc > 0 ? nc : 0)) >> 32);
-      q = q < 0 ? 0 : (q >= N ? N - 1 : q);
-      j = class_rows[q];
-      j = j < 0 ? 0 : (j >= N ? N - 1 : j);
-    } else {
-      j = (int)((h * (unsigned long long)N) >> 32);                       // < N: h < 2^32
-    }
-    atomicAdd(&wl[j], 1u);
-  }
+  for (int n = t; n < N; n += 256) atomicAdd(&wl[draw_row(seed, b, n, N, K, labels, class_rows, class_off, stratified)], 1u);
   __syncthreads();
   for (int i = t; i < N; i += 256) {
     const unsigned int v = wl[i], y = v >> 24, w = v & 0xFFFFFFu;
@@ -81,39 +64,16 @@ __global__ __launch_bounds__(256) void bootstrap_counts_kernel(const long long* 
     for (int s = t; s < Npad; s += 256) {
       unsigned int w = 0u;
       if (s < N) {
-        int row = oc[s];
-        row = row < 0 ? 0 : (row >= N ? N - 1 : row);
-        const unsigned int v = wl[row];
+        const unsigned int v = wl[clamp_row(oc[s], N)];
         w = (v >> 24) != (unsigned int)c ? (v & 0xFFFFFFu) : 0u;
       }
       P[s] = w;
     }
     __syncthreads();
-    unsigned int carry = 0u;                                              // sum of the tiles before this one: the same in every thread
-    for (int s0 = 0; s0 < Npad; s0 += kBootTile) {
-      u32x4 v = *(const u32x4*)(P + s0 + 4 * t);
-      v.y += v.x; v.z += v.y; v.w += v.z;
-      const unsigned int tot = v.w;
-      unsigned int inc = tot;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-      }
-      if (lane == 63) s_wave[wave] = inc;
-      __syncthreads();
-      const unsigned int w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-      const unsigned int base = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + (inc - tot);
-      v.x += base; v.y += base; v.z += base; v.w += base;
-      *(u32x4*)(P + s0 + 4 * t) = v;
-      carry += w0 + w1 + w2 + w3;
-      __syncthreads();                                                    // P is complete for the reads below; s_wave is free for the next tile
-    }
+    const unsigned int carry = block_scan_tiles_u32(P, Npad, s_wave);
     unsigned long long acc = 0ull, npos = 0ull;
     for (int s = t; s < N; s += 256) {
-      int row = oc[s];
-      row = row < 0 ? 0 : (row >= N ? N - 1 : row);
-      const unsigned int v = wl[row], w = v & 0xFFFFFFu;
+      const unsigned int v = wl[clamp_row(oc[s], N)], w = v & 0xFFFFFFu;
       if ((v >> 24) == (unsigned int)c && w) {
         int gs = gstart[(size_t)c * N + s], ge = gend[(size_t)c * N + s];
         gs = gs < 0 ? 0 : (gs > N ? N : gs);
@@ -151,14 +111,10 @@ extern "C" int gvk_bootstrap_counts(const void* labels, const int32_t* pred, con
   GVK_REQUIRE(R >= 1, "gvk_bootstrap_counts: R = %d replicates (at least 1)", R);
   GVK_REQUIRE(stratified == 0 || stratified == 1, "gvk_bootstrap_counts: stratified = %d (0 or 1)", stratified);
   GVK_REQUIRE(!stratified || (class_rows && class_off), "gvk_bootstrap_counts: the stratified rule needs class_rows and class_off");
-  const int Npad = (N + kBootTile - 1) / kBootTile * kBootTile;
+  const int Npad = scan_pad(N);
   const size_t lds = sizeof(unsigned int) * ((size_t)2 * Npad + (size_t)K * K);
   static size_t granted = 64 * 1024 - 256;                                // what a launch may ask for without the attribute (the static arrays take a little)
-  if (lds > granted) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bootstrap_counts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(bootstrap_counts): %s", hipGetErrorString(e));
-    granted = lds;
-  }
+  if (int rc = ensure_lds(&bootstrap_counts_kernel, lds, granted, "bootstrap_counts")) return rc;
   GVK_LAUNCH(bootstrap_counts_kernel, dim3((unsigned)R), dim3(256), (unsigned)lds, (hipStream_t)stream, (const long long*)labels, (const int*)pred,
              (const int*)order, (const int*)gstart, (const int*)gend, (const int*)class_rows, (const int*)class_off, (long long*)confusion,
              (long long*)auc_counts, N, K, Npad, (unsigned long long)seed, stratified);

@@ -156,6 +156,17 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds
 #define GVK_LAUNCH(kernel, grid, block, lds, stream, ...) ::gvk::launch(kernel, grid, block, lds, stream, __VA_ARGS__)
 
 int check_launch(const char* what);
+
+// Raise a kernel's dynamic-LDS limit to `bytes` once a launch asks for more than `granted` (the call site's static: what the kernel may use
+// without the attribute at first, then the largest grant so far).
+template <typename K>
+inline int ensure_lds(K kernel, size_t bytes, size_t& granted, const char* who) {
+  if (bytes <= granted) return 0;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(%s): %s", who, hipGetErrorString(e));
+  granted = bytes;
+  return 0;
+}
 }  // namespace gvk
 
 #define GVK_REQUIRE(cond, ...)                                  \

@@ -12,8 +12,7 @@
 // count, less the count before its segment, is m.  Everything it leaves is an exact integer.
 #include <math.h>
 
-#include "common.hpp"
-#include "dropout.hpp"
+#include "replicate.hpp"
 #include "../../include/gaviko_hip.h"
 
 #pragma clang fp contract(off)
@@ -23,7 +22,6 @@ namespace gvk {
 constexpr int kConfMaxN = GVK_BOOTSTRAP_MAX_ROWS;                // the row index takes the low 13 bits of a split key
 constexpr int kConfMaxK = GVK_CONFORMAL_MAX_CLASSES;             // one class per lane of a wave
 constexpr int kConfMaxQ = GVK_CONFORMAL_MAX_LEVELS;
-constexpr int kConfTile = 1024;                                  // scan tile: 256 threads x 4 consecutive entries (one 16-byte LDS access each)
 constexpr unsigned int kConfRowMask = (unsigned int)kConfMaxN - 1u;
 static_assert((kConfMaxN & (kConfMaxN - 1)) == 0, "the split key keeps the row index in its low bits");
 
@@ -94,8 +92,7 @@ static_assert(kConfSmallWords % 4 == 0, "the LDS carve keeps 16-byte alignment")
 // One 256-thread workgroup per replicate.  LDS (dynamic): keys[Npad] | P[Npad] | the small tables above, Npad = N rounded up to the scan tile.
 //   keys[i] = (hash_u32(seed, b N + i) & ~0x1FFF) | i: distinct, so "the n_cal rows with the smallest keys" is  keys[i] <= T  with T the
 //             n_cal-th smallest key, found by a 4-pass radix select (8 bits per pass, 256 bins = one per thread, LDS atomics)
-//   P[s]    = 1 if the row at sorted position s is a calibration row, then its inclusive scan (tiles of 1024: 4 entries per thread, wave64
-//             shuffle scan of the thread totals, the 4 wave totals and the running carry through LDS -- the scan of risk_coverage_kernel)
+//   P[s]    = 1 if the row at sorted position s is a calibration row, then its inclusive scan (block_scan_tiles_u32 of replicate.hpp)
 // Every index read from a table is clamped before it addresses LDS or global memory: the tables are the caller's contract
 // (ops.conformal_tables builds them), a broken one gives wrong counts, never an access outside the arrays.  The histograms are LDS integer
 // atomics; nothing is accumulated in global memory.
@@ -141,13 +138,7 @@ __global__ __launch_bounds__(256) void conformal_splits_kernel(const float* __re
       if ((key & mask) == prefix) atomicAdd(&s_bins[(key >> shift) & 0xFFu], 1u);
     }
     __syncthreads();
-    const unsigned int c = s_bins[t];
-    unsigned int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned int u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
+    const unsigned int c = s_bins[t], inc = wave_scan_u32(c);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     const unsigned int incl = inc + (wave > 0 ? s_wave[0] : 0u) + (wave > 1 ? s_wave[1] : 0u) + (wave > 2 ? s_wave[2] : 0u);
@@ -159,36 +150,9 @@ __global__ __launch_bounds__(256) void conformal_splits_kernel(const float* __re
   }
   const unsigned int T = prefix;                                            // keys[i] <= T: a calibration row (n_cal == N: every row)
 
-  for (int s = t; s < Npad; s += 256) {
-    unsigned int v = 0u;
-    if (s < N) {
-      int row = order[s];
-      row = row < 0 ? 0 : (row >= N ? N - 1 : row);
-      v = keys[row] <= T ? 1u : 0u;
-    }
-    P[s] = v;
-  }
+  for (int s = t; s < Npad; s += 256) P[s] = (s < N && keys[clamp_row(order[s], N)] <= T) ? 1u : 0u;
   __syncthreads();
-  unsigned int carry = 0u;                                                  // sum of the tiles before this one: the same in every thread
-  for (int s0 = 0; s0 < Npad; s0 += kConfTile) {
-    u32x4 v = *(const u32x4*)(P + s0 + 4 * t);
-    v.y += v.x; v.z += v.y; v.w += v.z;
-    const unsigned int tot = v.w;
-    unsigned int inc = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned int u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    const unsigned int w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-    const unsigned int base = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + (inc - tot);
-    v.x += base; v.y += base; v.z += base; v.w += base;
-    *(u32x4*)(P + s0 + 4 * t) = v;
-    carry += w0 + w1 + w2 + w3;
-    __syncthreads();                                                        // P is complete for the reads below; s_wave is free for the next tile
-  }
+  block_scan_tiles_u32(P, Npad, s_wave);
 
   // per segment: the calibration rows before it and inside it; per level the order statistic asked for (0: none, the threshold stays +inf)
   for (int g = t; g < G; g += 256) {
@@ -208,11 +172,9 @@ __global__ __launch_bounds__(256) void conformal_splits_kernel(const float* __re
   }
   __syncthreads();
   for (int s = t; s < N; s += 256) {
-    int row = order[s];
-    row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+    const int row = clamp_row(order[s], N);
     if (keys[row] > T) continue;
-    const long long y = labels[row];
-    const int yc = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);                   // labels outside [0, K) are the caller's contract
+    const int yc = clamp_label(labels[row], K);                             // labels outside [0, K) are the caller's contract
     const int g = G == 1 ? 0 : yc;
     const int r = (int)P[s] - s_base[g];                                    // this row is the r-th calibration row of its segment, 1-based
     for (int q = 0; q < Q; ++q)
@@ -223,8 +185,7 @@ __global__ __launch_bounds__(256) void conformal_splits_kernel(const float* __re
   // the test rows: set sizes and coverage at every level
   for (int i = t; i < N; i += 256) {
     if (keys[i] <= T) continue;
-    const long long y = labels[i];
-    const int yc = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);
+    const int yc = clamp_label(labels[i], K);
     int size[kConfMaxQ];
 #pragma unroll
     for (int q = 0; q < kConfMaxQ; ++q) size[q] = 0;
@@ -293,14 +254,10 @@ extern "C" int gvk_conformal_splits(const float* scores, const void* labels, con
   GVK_REQUIRE(G == 1 || G == K, "gvk_conformal_splits: G = %d segments (1: marginal, K = %d: one per class)", G, K);
   GVK_REQUIRE(n_cal >= 1 && n_cal <= N, "gvk_conformal_splits: n_cal = %d calibration rows outside [1, %d]", n_cal, N);
   GVK_REQUIRE(R >= 1, "gvk_conformal_splits: R = %d replicates (at least 1)", R);
-  const int Npad = (N + kConfTile - 1) / kConfTile * kConfTile;
+  const int Npad = scan_pad(N);
   const size_t lds = sizeof(unsigned int) * ((size_t)2 * Npad + (size_t)kConfSmallWords);
   static size_t granted = 64 * 1024;                                        // what a launch may ask for without the attribute
-  if (lds > granted) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conformal_splits_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(conformal_splits): %s", hipGetErrorString(e));
-    granted = lds;
-  }
+  if (int rc = ensure_lds(&conformal_splits_kernel, lds, granted, "conformal_splits")) return rc;
   GVK_LAUNCH(conformal_splits_kernel, dim3((unsigned)R), dim3(256), (unsigned)lds, (hipStream_t)stream, scores, (const long long*)labels,
              (const int*)order, (const int*)seg_off, alphas, (int*)qpos, (int*)n_seg, (int*)size_hist, (int*)covered_by_size, (int*)class_test,
              (int*)class_covered, N, K, Q, G, Npad, n_cal, (unsigned long long)seed);

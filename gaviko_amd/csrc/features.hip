@@ -349,15 +349,6 @@ static int topk_slabs(int Nq, int Ng, int want) {
   return (ntiles + tps - 1) / tps;                              // no empty slab
 }
 
-template <typename K>
-static int feat_ensure_lds(K kernel, size_t bytes, size_t& granted, const char* who) {
-  if (bytes <= granted) return 0;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(%s): %s", who, hipGetErrorString(e));
-  granted = bytes;
-  return 0;
-}
-
 }  // namespace gvk
 
 extern "C" int gvk_token_pool(const float* g, float* out, int B, int T, int C, int r0, int R, void* stream) {
@@ -407,11 +398,11 @@ extern "C" int gvk_feature_topk(const gvk_feature_topk_desc* d, void* stream) {
   const dim3 grid((unsigned)((Nq + 15) / 16), (unsigned)nslabs), block(64 * kTopkWaves);
   static size_t granted_ip = 64 * 1024, granted_l2 = 64 * 1024;
   if (d->metric == 1) {
-    if (int rc = feat_ensure_lds(&topk_slab_kernel<true>, lds, granted_l2, "topk_slab<l2>")) return rc;
+    if (int rc = ensure_lds(&topk_slab_kernel<true>, lds, granted_l2, "topk_slab<l2>")) return rc;
     GVK_LAUNCH(topk_slab_kernel<true>, grid, block, (unsigned)lds, (hipStream_t)stream, (const float*)d->q, (const float*)d->g, (const int*)d->exclude,
                pkey, pidx, Nq, Ng, C, k, nslabs, tps);
   } else {
-    if (int rc = feat_ensure_lds(&topk_slab_kernel<false>, lds, granted_ip, "topk_slab<ip>")) return rc;
+    if (int rc = ensure_lds(&topk_slab_kernel<false>, lds, granted_ip, "topk_slab<ip>")) return rc;
     GVK_LAUNCH(topk_slab_kernel<false>, grid, block, (unsigned)lds, (hipStream_t)stream, (const float*)d->q, (const float*)d->g, (const int*)d->exclude,
                pkey, pidx, Nq, Ng, C, k, nslabs, tps);
   }

@@ -500,15 +500,6 @@ static int row_grid(int M) {
   return want < cus ? want : cus;
 }
 
-template <typename K>
-static int ensure_lds(K kernel, size_t bytes, size_t& granted, const char* who) {
-  if (bytes <= granted) return 0;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(%s): %s", who, hipGetErrorString(e));
-  granted = bytes;
-  return 0;
-}
-
 template <int L>
 static int launch_down_t(const DownArgs& a, hipStream_t s) {
   static size_t granted = 0;

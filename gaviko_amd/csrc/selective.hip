@@ -12,8 +12,7 @@
 // gvk_temperature_fit: one workgroup minimises the mean NLL of softmax(beta z) over beta = 1 / T by safeguarded Newton, float64 throughout,
 // without a host read: every thread holds the same sums (the partials go through LDS and every thread adds them in the same order), so the
 // whole iteration is uniform control flow.
-#include "common.hpp"
-#include "dropout.hpp"
+#include "replicate.hpp"
 #include "../../include/gaviko_hip.h"
 
 namespace gvk {
@@ -21,12 +20,10 @@ namespace gvk {
 constexpr int kSelMaxN = GVK_BOOTSTRAP_MAX_ROWS;                 // multiplicities and their sums stay below 2^16: two of them share a word
 constexpr int kSelMaxK = GVK_BOOTSTRAP_MAX_CLASSES;
 constexpr int kSelMaxQ = GVK_RISK_COVERAGE_MAX_NEEDS;
-constexpr int kSelTile = 1024;                                   // scan tile: 256 threads x 4 consecutive entries (one 16-byte LDS access each)
 
 // One 256-thread workgroup per replicate.  LDS (dynamic): w[Npad] | P[Npad], Npad = N rounded up to the scan tile.
 //   w[row] = multiplicity of the row (the N draws add 1 each by 32-bit LDS atomics; all 1 when resample = 0)
-//   P[s]   = the packed pair of the row at sorted position s, then its inclusive scan (tiles of 1024: 4 entries per thread, wave64 shuffle
-//            scan of the thread totals, the 4 wave totals and the running carry through LDS -- the scan of bootstrap_counts_kernel)
+//   P[s]   = the packed pair of the row at sorted position s, then its inclusive scan (block_scan_tiles_u32 of replicate.hpp)
 // Every index read from a table is clamped before it addresses LDS or global memory: the tables are the caller's contract
 // (ops.selective_tables builds them), a broken one gives wrong counts, never an access outside the arrays.  No atomics on global memory; the
 // aurc partials are added in a fixed order (per thread by ascending position, the xor butterfly of a wave, the 4 waves in order).
@@ -52,55 +49,20 @@ __global__ __launch_bounds__(256) void risk_coverage_kernel(const long long* __r
   }
   __syncthreads();
   if (resample) {
-    for (int n = t; n < N; n += 256) {
-      const unsigned long long h = hash_u32(seed, b * (unsigned long long)N + (unsigned long long)n);
-      int j;
-      if (stratified) {
-        const long long y = labels[n];
-        const int c = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);
-        const int o0 = class_off[c], nc = class_off[c + 1] - o0;
-        int q = o0 + (int)((h * (unsigned long long)(nc > 0 ? nc : 0)) >> 32);
-        q = q < 0 ? 0 : (q >= N ? N - 1 : q);
-        j = class_rows[q];
-        j = j < 0 ? 0 : (j >= N ? N - 1 : j);
-      } else {
-        j = (int)((h * (unsigned long long)N) >> 32);                       // < N: h < 2^32
-      }
-      atomicAdd(&w[j], 1u);
-    }
+    for (int n = t; n < N; n += 256) atomicAdd(&w[draw_row(seed, b, n, N, K, labels, class_rows, class_off, stratified)], 1u);
     __syncthreads();
   }
   for (int s = t; s < Npad; s += 256) {
     unsigned int v = 0u;
     if (s < N) {
-      int row = order[s];
-      row = row < 0 ? 0 : (row >= N ? N - 1 : row);
+      const int row = clamp_row(order[s], N);
       const unsigned int m = w[row];
       v = m << 16 | ((long long)pred[row] != labels[row] ? m : 0u);
     }
     P[s] = v;
   }
   __syncthreads();
-  unsigned int carry = 0u;                                                  // sum of the tiles before this one: the same in every thread
-  for (int s0 = 0; s0 < Npad; s0 += kSelTile) {
-    u32x4 v = *(const u32x4*)(P + s0 + 4 * t);
-    v.y += v.x; v.z += v.y; v.w += v.z;
-    const unsigned int tot = v.w;
-    unsigned int inc = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned int u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    const unsigned int w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-    const unsigned int base = carry + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u) + (inc - tot);
-    v.x += base; v.y += base; v.z += base; v.w += base;
-    *(u32x4*)(P + s0 + 4 * t) = v;
-    carry += w0 + w1 + w2 + w3;
-    __syncthreads();                                                        // P is complete for the reads below; s_wave is free for the next tile
-  }
+  const unsigned int carry = block_scan_tiles_u32(P, Npad, s_wave);
   double acc = 0.0;
   for (int s = t; s < N; s += 256) {
     int ge = gend[s];
@@ -173,7 +135,7 @@ __device__ __forceinline__ void fit_eval(const float* __restrict__ logits, const
       S0 += e; S1 += e * d; S2 += e * d * d;
     }
     const long long y = target[n];
-    const int yc = y < 0 ? 0 : (y >= K ? K - 1 : (int)y);                   // labels outside [0, K) are the caller's contract
+    const int yc = clamp_label(y, K);                                       // labels outside [0, K) are the caller's contract
     const double dy = (double)z[yc] - m, mean = S1 / S0, var = S2 / S0 - mean * mean;
     sg += mean - dy;
     sh += var > 0.0 ? var : 0.0;
@@ -241,14 +203,10 @@ extern "C" int gvk_risk_coverage(const void* labels, const int32_t* pred, const 
               "gvk_risk_coverage: the stratified rule needs class_rows, class_off and 1 <= K <= %d (K = %d)", kSelMaxK, K);
   GVK_REQUIRE((accepted == nullptr) == (errors == nullptr), "gvk_risk_coverage: accepted and errors come together");
   GVK_REQUIRE(!resample || !accepted, "gvk_risk_coverage: the curve (accepted, errors) is written with resample = 0 only");
-  const int Npad = (N + kSelTile - 1) / kSelTile * kSelTile;
+  const int Npad = scan_pad(N);
   const size_t lds = sizeof(unsigned int) * (size_t)2 * Npad;
   static size_t granted = 64 * 1024 - 256;                                  // what a launch may ask for without the attribute (the static arrays take a little)
-  if (lds > granted) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&risk_coverage_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(risk_coverage): %s", hipGetErrorString(e));
-    granted = lds;
-  }
+  if (int rc = ensure_lds(&risk_coverage_kernel, lds, granted, "risk_coverage")) return rc;
   GVK_LAUNCH(risk_coverage_kernel, dim3((unsigned)R), dim3(256), (unsigned)lds, (hipStream_t)stream, (const long long*)labels, (const int*)pred,
              (const int*)order, (const int*)gend, (const int*)class_rows, (const int*)class_off, (const int*)need, aurc, (int*)at, (int*)total,
              (int*)accepted, (int*)errors, N, K, Q, Npad, (unsigned long long)seed, stratified, resample);

@@ -41,6 +41,23 @@ def macro_ovr_auc(counts: np.ndarray) -> float:
     return float((counts[:, 0] / (2.0 * counts[:, 1] * counts[:, 2])).mean())
 
 
+def _device_tensor(what: str, t, noun: str) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise GavikoHipError(f"{what}: the {noun} must be a tensor on the HIP device (there is no CPU path)")
+
+
+def _check_replicates(what: str, replicates, optional: bool = False) -> None:
+    if optional and replicates is None:
+        return
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1:
+        raise GavikoHipError(f"{what}: replicates = {replicates!r} ({'None or ' if optional else ''}an integer >= 1)")
+
+
+def _check_level(what: str, level) -> None:
+    if not 0.0 < float(level) < 1.0:
+        raise GavikoHipError(f"{what}: level = {level!r} outside (0, 1)")
+
+
 def calibration(proba: torch.Tensor, labels: torch.Tensor, bins: int = 15) -> Dict[str, object]:
     """Calibration of top-1 confidences (Guo et al., 2017) from the device probabilities gvk_eval_rows wrote: proba f32 [N, K], labels [N]
     within [0, K).  gvk_calibration_bins counts, per equal-width confidence bin (i / bins, (i + 1) / bins], the rows, the correct top-1
@@ -48,8 +65,7 @@ def calibration(proba: torch.Tensor, labels: torch.Tensor, bins: int = 15) -> Di
       ece  = sum_i (n_i / N) |acc_i - conf_i|        mce = max_i |acc_i - conf_i| over the non-empty bins
       brier = (1 / N) sum_n sum_k (p_nk - 1[y_n = k])^2        nll = (1 / N) sum_n -log max(p_n,y_n, FLT_MIN)
       bin_count int64 [bins], bin_accuracy / bin_confidence f64 [bins] (NaN for an empty bin): the reliability diagram."""
-    if not isinstance(proba, torch.Tensor) or not proba.is_cuda:
-        raise GavikoHipError("calibration: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    _device_tensor("calibration", proba, "probabilities")
     if proba.dim() != 2:
         raise GavikoHipError(f"calibration: expected proba [N, K], got {tuple(proba.shape)}")
     N, K = proba.shape
@@ -193,8 +209,7 @@ def bootstrap(proba: torch.Tensor, labels: torch.Tensor, *, replicates: int = 20
     A replicate that lost a class (no positive, or no negative row for it) has auc = NaN and counts in undefined["auc"]; the interval and the
     standard error skip NaN.  `pred` i32 [N] (optional): the predictions, where they are not the argmax of proba (lowest index on a tie).
     N <= 8192, 2 <= K <= 64."""
-    if not isinstance(proba, torch.Tensor) or not proba.is_cuda:
-        raise GavikoHipError("bootstrap: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    _device_tensor("bootstrap", proba, "probabilities")
     if proba.dim() != 2:
         raise GavikoHipError(f"bootstrap: expected proba [N, K], got {tuple(proba.shape)}")
     N, K = proba.shape
@@ -205,10 +220,8 @@ def bootstrap(proba: torch.Tensor, labels: torch.Tensor, *, replicates: int = 20
         raise GavikoHipError(f"bootstrap: N = {N}, K = {K} outside N <= {ops.BOOTSTRAP_MAX_ROWS}, 2 <= K <= {ops.BOOTSTRAP_MAX_CLASSES}")
     if int(labels.min()) < 0 or int(labels.max()) >= K:
         raise GavikoHipError(f"bootstrap: labels outside [0, {K})")
-    if isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1:
-        raise GavikoHipError(f"bootstrap: replicates = {replicates!r} (an integer >= 1)")
-    if not 0.0 < float(level) < 1.0:
-        raise GavikoHipError(f"bootstrap: level = {level!r} outside (0, 1)")
+    _check_replicates("bootstrap", replicates)
+    _check_level("bootstrap", level)
     proba = proba.detach().float().contiguous()
     if bool(torch.isnan(proba).any()):
         raise GavikoHipError("bootstrap: NaN probabilities have no rank")
@@ -310,8 +323,7 @@ def fit_temperature(logits: torch.Tensor, labels: torch.Tensor, *, t_min: float 
         raise GavikoHipError(f"fit_temperature: K = {K} classes outside [2, {ops.TEMPERATURE_MAX_CLASSES}]")
     if not 0.0 < float(t_min) < float(t_max) < float("inf"):
         raise GavikoHipError(f"fit_temperature: need 0 < t_min < t_max, finite (got {t_min!r}, {t_max!r})")
-    if not logits.is_cuda:
-        raise GavikoHipError("fit_temperature: the logits must be a tensor on the HIP device (there is no CPU path)")
+    _device_tensor("fit_temperature", logits, "logits")
     logits = logits.detach().float().contiguous()
     labels = torch.as_tensor(labels).to(logits.device).to(torch.int64).contiguous()
     if labels.numel() != N:
@@ -355,14 +367,11 @@ def risk_coverage(score: torch.Tensor, labels: torch.Tensor, pred: torch.Tensor,
         raise GavikoHipError(f"risk_coverage: {len(cov)} coverages (at most {ops.RISK_COVERAGE_MAX_NEEDS})")
     if any(not 0.0 < q <= 1.0 for q in cov) or any(a > b for a, b in zip(cov, cov[1:])):
         raise GavikoHipError(f"risk_coverage: coverages = {coverages!r} (ascending, each within (0, 1])")
-    if replicates is not None and (isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1):
-        raise GavikoHipError(f"risk_coverage: replicates = {replicates!r} (None or an integer >= 1)")
-    if not 0.0 < float(level) < 1.0:
-        raise GavikoHipError(f"risk_coverage: level = {level!r} outside (0, 1)")
+    _check_replicates("risk_coverage", replicates, optional=True)
+    _check_level("risk_coverage", level)
     if bool(torch.isnan(score).any()):
         raise GavikoHipError("risk_coverage: NaN scores have no rank")
-    if not score.is_cuda:
-        raise GavikoHipError("risk_coverage: the scores must be a tensor on the HIP device (there is no CPU path)")
+    _device_tensor("risk_coverage", score, "scores")
     score = score.detach().float().contiguous()
     labels = torch.as_tensor(labels).to(score.device).to(torch.int64).contiguous()
     pred = torch.as_tensor(pred).to(score.device).to(torch.int32).contiguous()
@@ -458,8 +467,7 @@ def _conformal_shape(what: str, proba, labels) -> Tuple[int, int]:
 
 
 def _conformal_labels(what: str, proba, labels) -> torch.Tensor:
-    if not proba.is_cuda:
-        raise GavikoHipError(f"{what}: the probabilities must be a tensor on the HIP device (there is no CPU path)")
+    _device_tensor(what, proba, "probabilities")
     labels = torch.as_tensor(labels).to(proba.device).to(torch.int64).contiguous().reshape(proba.shape[0])
     if int(labels.min()) < 0 or int(labels.max()) >= proba.shape[1]:
         raise GavikoHipError(f"{what}: labels outside [0, {proba.shape[1]})")
@@ -527,10 +535,8 @@ def conformal_evaluate(proba: torch.Tensor, labels: torch.Tensor, *, alphas=(0.1
     N <= 8192, 2 <= K <= 64."""
     N, K = _conformal_shape("conformal_evaluate", proba, labels)
     a = _conformal_alphas("conformal_evaluate", alphas)
-    if isinstance(replicates, bool) or not isinstance(replicates, int) or replicates < 1:
-        raise GavikoHipError(f"conformal_evaluate: replicates = {replicates!r} (an integer >= 1)")
-    if not 0.0 < float(level) < 1.0:
-        raise GavikoHipError(f"conformal_evaluate: level = {level!r} outside (0, 1)")
+    _check_replicates("conformal_evaluate", replicates)
+    _check_level("conformal_evaluate", level)
     if N < 2:
         raise GavikoHipError("conformal_evaluate: a split needs at least 2 rows")
     if n_cal is None:

@@ -1642,22 +1642,53 @@ BOOTSTRAP_MAX_ROWS = 8192       # gvk_bootstrap_counts: one workgroup keeps the 
 BOOTSTRAP_MAX_CLASSES = 64
 
 
+def _i32(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.int32).contiguous()
+
+
+def _class_groups(labels: torch.Tensor, K: int):
+    """labels i64 [N] -> (class_rows i32 [N]: the rows grouped by label, ascending inside a label; class_off i32 [K + 1]: where every label's rows
+    start).  The stratified draw of the replicate kernels reads them, and the Mondrian segments of conformal_tables are the same groups."""
+    off = torch.zeros(K + 1, dtype=torch.int64, device=labels.device)
+    off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
+    return _i32(torch.sort(labels, stable=True).indices), _i32(off)
+
+
+def _tie_groups(vals: torch.Tensor):
+    """vals [..., N] sorted along the last dimension -> (gstart, gend) i64 [..., N]: per position the bounds [gstart, gend) of its run of
+    equal values."""
+    N = vals.shape[-1]
+    pos = torch.arange(N, device=vals.device).expand(vals.shape)
+    step = vals[..., 1:] != vals[..., :-1]
+    edge = torch.ones(vals.shape[:-1] + (1,), dtype=torch.bool, device=vals.device)
+    gstart = torch.cummax(torch.where(torch.cat([edge, step], -1), pos, torch.zeros_like(pos)), -1).values
+    gend = torch.cummin(torch.where(torch.cat([step, edge], -1), pos + 1, torch.full_like(pos, N)).flip(-1), -1).values.flip(-1)
+    return gstart, gend
+
+
+def _replicate_rows(what: str, N: int) -> None:
+    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
+        raise L.GavikoHipError(f"{what}: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+
+
+def _replicates(what: str, R) -> int:
+    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+        raise L.GavikoHipError(f"{what}: replicates = {R!r} (an integer >= 1)")
+    return R
+
+
+def _seed64(seed) -> int:
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def bootstrap_tables(proba: torch.Tensor, labels: torch.Tensor) -> dict:
     """The per-call tables of gvk_bootstrap_counts, built with torch on the device (plumbing: once per call, not per replicate).
     proba f32 [N, K], labels i64 [N] within [0, K) -> order / gstart / gend i32 [K, N] (the rows in ascending order of every class column,
     stable; per sorted position the bounds of its group of equal scores), class_rows i32 [N], class_off i32 [K + 1] (rows grouped by label)."""
-    N, K = proba.shape
     vals, order = torch.sort(proba.t().contiguous(), dim=1, stable=True)
-    pos = torch.arange(N, device=proba.device).expand(K, N)
-    step = vals[:, 1:] != vals[:, :-1]
-    edge = torch.ones((K, 1), dtype=torch.bool, device=proba.device)
-    gstart = torch.cummax(torch.where(torch.cat([edge, step], 1), pos, torch.zeros_like(pos)), 1).values
-    gend = torch.cummin(torch.where(torch.cat([step, edge], 1), pos + 1, torch.full_like(pos, N)).flip(1), 1).values.flip(1)
-    off = torch.zeros(K + 1, dtype=torch.int64, device=proba.device)
-    off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
-    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
-    return {"order": i32(order), "gstart": i32(gstart), "gend": i32(gend),
-            "class_rows": i32(torch.sort(labels, stable=True).indices), "class_off": i32(off)}
+    gstart, gend = _tie_groups(vals)
+    class_rows, class_off = _class_groups(labels, proba.shape[1])
+    return {"order": _i32(order), "gstart": _i32(gstart), "gend": _i32(gend), "class_rows": class_rows, "class_off": class_off}
 
 
 def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, replicates: int, seed: int, stratified: bool,
@@ -1672,13 +1703,10 @@ def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, rep
         raise L.GavikoHipError(f"bootstrap_counts order: expected an int32 [K, {N}] table, got {None if order is None else tuple(order.shape)}")
     K = order.shape[0]
     _tab(order, "bootstrap_counts order", K * N)
-    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
-        raise L.GavikoHipError(f"bootstrap_counts: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+    _replicate_rows("bootstrap_counts", N)
     if not 2 <= K <= BOOTSTRAP_MAX_CLASSES:
         raise L.GavikoHipError(f"bootstrap_counts: K = {K} classes outside [2, {BOOTSTRAP_MAX_CLASSES}]")
-    R = replicates
-    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
-        raise L.GavikoHipError(f"bootstrap_counts: replicates = {R!r} (an integer >= 1)")
+    R = _replicates("bootstrap_counts", replicates)
     _tab(pred, "bootstrap_counts pred", N)
     _tab(tables.get("gstart"), "bootstrap_counts gstart", K * N)
     _tab(tables.get("gend"), "bootstrap_counts gend", K * N)
@@ -1695,7 +1723,7 @@ def bootstrap_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict, rep
         raise L.GavikoHipError(f"bootstrap_counts: expected confusion [{R}, {K}, {K}] and auc_counts [{R}, {K}, 3], got {tuple(confusion.shape)} and "
                                f"{tuple(auc_counts.shape)}")
     L.launch.gvk_bootstrap_counts(labels, pred, tables["order"], tables["gstart"], tables["gend"], tables["class_rows"], tables["class_off"], confusion,
-                                  auc_counts, N, K, R, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0)
+                                  auc_counts, N, K, R, _seed64(seed), 1 if stratified else 0)
     return confusion, auc_counts
 
 
@@ -1711,15 +1739,8 @@ def selective_tables(score: torch.Tensor, labels: torch.Tensor) -> dict:
     label, as ops.bootstrap_tables has them; K = the largest label + 1) and sorted_score f32 [N] (score[order], for the thresholds)."""
     N = score.numel()
     vals, order = torch.sort(score.reshape(N), descending=True, stable=True)
-    pos = torch.arange(N, device=score.device)
-    edge = torch.ones(1, dtype=torch.bool, device=score.device)
-    last = torch.cat([vals[1:] != vals[:-1], edge])
-    gend = torch.cummin(torch.where(last, pos + 1, torch.full_like(pos, N)).flip(0), 0).values.flip(0)
-    K = int(labels.max()) + 1 if N else 1
-    off = torch.zeros(K + 1, dtype=torch.int64, device=score.device)
-    off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
-    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
-    return {"order": i32(order), "gend": i32(gend), "class_rows": i32(torch.sort(labels, stable=True).indices), "class_off": i32(off),
+    class_rows, class_off = _class_groups(labels, int(labels.max()) + 1 if N else 1)
+    return {"order": _i32(order), "gend": _i32(_tie_groups(vals)[1]), "class_rows": class_rows, "class_off": class_off,
             "sorted_score": vals.contiguous()}
 
 
@@ -1731,11 +1752,8 @@ def risk_coverage_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict,
     (accepted-row counts).  -> dict of device tensors: aurc f64 [R], at i32 [R, Q, 2], total i32 [R, 2] and, with resample=False, accepted /
     errors i32 [N] (per sorted position the running (accepted, wrong) counts at the end of its tie group).  N <= 8192."""
     N = labels.numel()
-    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
-        raise L.GavikoHipError(f"risk_coverage_counts: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
-    R = replicates
-    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
-        raise L.GavikoHipError(f"risk_coverage_counts: replicates = {R!r} (an integer >= 1)")
+    _replicate_rows("risk_coverage_counts", N)
+    R = _replicates("risk_coverage_counts", replicates)
     if not resample and R != 1:
         raise L.GavikoHipError(f"risk_coverage_counts: resample=False is the full sample, replicates = {R} must be 1")
     need = [n for n in need]
@@ -1764,7 +1782,7 @@ def risk_coverage_counts(labels: torch.Tensor, pred: torch.Tensor, tables: dict,
         out["errors"] = torch.empty(N, dtype=torch.int32, device=dev)
     need_d = torch.tensor(need, dtype=torch.int32, device=dev) if Q else None
     L.launch.gvk_risk_coverage(labels, pred, tables["order"], tables["gend"], tables["class_rows"], class_off, need_d, out["aurc"], out["at"] if Q else None,
-                               out["total"], out.get("accepted"), out.get("errors"), N, K, Q, R, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if stratified else 0,
+                               out["total"], out.get("accepted"), out.get("errors"), N, K, Q, R, _seed64(seed), 1 if stratified else 0,
                                1 if resample else 0)
     return out
 
@@ -1831,7 +1849,7 @@ def conformal_scores(proba: torch.Tensor, kind: str = "lac", randomized: bool = 
     _chk(scores, torch.float32, "conformal_scores scores")
     if tuple(scores.shape) != (K, N):
         raise L.GavikoHipError(f"conformal_scores scores: expected [{K}, {N}] (class-major), got {tuple(scores.shape)}")
-    L.launch.gvk_conformal_scores(proba, scores, N, K, CONFORMAL_KINDS[kind], 1 if randomized else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, min(k_reg, K + 1),
+    L.launch.gvk_conformal_scores(proba, scores, N, K, CONFORMAL_KINDS[kind], 1 if randomized else 0, _seed64(seed), min(k_reg, K + 1),
                                   lam)
     return scores
 
@@ -1846,12 +1864,10 @@ def conformal_tables(scores: torch.Tensor, labels: torch.Tensor, mondrian: bool 
     order = torch.sort(true, stable=True).indices
     if mondrian:
         order = order[torch.sort(labels[order], stable=True).indices]
-        off = torch.zeros(K + 1, dtype=torch.int64, device=scores.device)
-        off[1:] = torch.cumsum(torch.bincount(labels, minlength=K)[:K], 0)
+        seg_off = _class_groups(labels, K)[1]
     else:
-        off = torch.tensor([0, N], dtype=torch.int64, device=scores.device)
-    i32 = lambda t: t.to(torch.int32).contiguous()                       # noqa: E731
-    return {"order": i32(order), "seg_off": i32(off), "sorted_score": true[order].contiguous()}
+        seg_off = torch.tensor([0, N], dtype=torch.int32, device=scores.device)
+    return {"order": _i32(order), "seg_off": seg_off, "sorted_score": true[order].contiguous()}
 
 
 def conformal_splits(scores: torch.Tensor, labels: torch.Tensor, tables: dict, alphas, n_cal: int, replicates: int = 1, seed: int = 0) -> dict:
@@ -1864,13 +1880,10 @@ def conformal_splits(scores: torch.Tensor, labels: torch.Tensor, tables: dict, a
         raise L.GavikoHipError(f"conformal_splits scores: expected a class-major [K, N] tensor, got "
                                f"{tuple(scores.shape) if isinstance(scores, torch.Tensor) else type(scores).__name__}")
     K, N = scores.shape
-    if not 1 <= N <= BOOTSTRAP_MAX_ROWS:
-        raise L.GavikoHipError(f"conformal_splits: N = {N} rows outside [1, {BOOTSTRAP_MAX_ROWS}] (one workgroup keeps a replicate in LDS)")
+    _replicate_rows("conformal_splits", N)
     if not 2 <= K <= CONFORMAL_MAX_CLASSES:
         raise L.GavikoHipError(f"conformal_splits: K = {K} classes outside [2, {CONFORMAL_MAX_CLASSES}]")
-    R = replicates
-    if isinstance(R, bool) or not isinstance(R, int) or R < 1:
-        raise L.GavikoHipError(f"conformal_splits: replicates = {R!r} (an integer >= 1)")
+    R = _replicates("conformal_splits", replicates)
     if isinstance(n_cal, bool) or not isinstance(n_cal, int) or not 1 <= n_cal <= N:
         raise L.GavikoHipError(f"conformal_splits: n_cal = {n_cal!r} (an integer within [1, {N}])")
     try:
@@ -1898,7 +1911,7 @@ def conformal_splits(scores: torch.Tensor, labels: torch.Tensor, tables: dict, a
            "class_covered": i32(R, Q, K)}
     alphas_d = torch.tensor(alphas, dtype=torch.float64, device=dev)
     L.launch.gvk_conformal_splits(scores, labels, tables["order"], seg_off, alphas_d, out["qpos"], out["n_seg"], out["size_hist"], out["covered_by_size"],
-                                  out["class_test"], out["class_covered"], N, K, Q, G, n_cal, R, int(seed) & 0xFFFFFFFFFFFFFFFF)
+                                  out["class_test"], out["class_covered"], N, K, Q, G, n_cal, R, _seed64(seed))
     return out
 
 

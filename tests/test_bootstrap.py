@@ -101,6 +101,29 @@ def test_sorted_prefix_form_and_device_tables_equal_pair_counting():
     assert (want[:, 2, 0] == want[:, 2, 1] * want[:, 2, 2]).all()  # all ties: 2 * greater + ties = n_pos n_neg, AUC exactly 0.5
 
 
+def test_the_three_table_builders_group_the_rows_by_label_alike():
+    """class_rows / class_off of bootstrap_tables and selective_tables, and the Mondrian seg_off of conformal_tables, for labels with an
+    empty class: the stratified draw and the Mondrian segments read the same groups."""
+    y = torch.tensor([2, 0, 2, 2, 0, 2, 0, 2])                     # class sizes [3, 0, 5]
+    p = torch.softmax(torch.from_numpy(np.random.default_rng(5).standard_normal((8, 3)).astype(np.float32)), 1)
+    boot, sel = ops.bootstrap_tables(p, y), ops.selective_tables(p.max(1).values, y)
+    conf = ops.conformal_tables((1.0 - p).t().contiguous(), y, mondrian=True)
+    assert boot["class_rows"].tolist() == [1, 4, 6, 0, 2, 3, 5, 7] and boot["class_off"].tolist() == [0, 3, 3, 8]
+    for t in (boot["class_rows"], boot["class_off"], conf["seg_off"]):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert torch.equal(sel["class_rows"], boot["class_rows"]) and torch.equal(sel["class_off"], boot["class_off"])
+    assert torch.equal(conf["seg_off"], boot["class_off"])
+
+
+def test_tie_groups_of_an_all_tied_row_and_of_a_row_without_ties():
+    vals = torch.tensor([[0.5] * 7, [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6]])
+    gstart, gend = ops._tie_groups(vals)
+    assert gstart.tolist() == [[0] * 7, [0, 1, 2, 3, 4, 5, 6]]
+    assert gend.tolist() == [[7] * 7, [1, 2, 3, 4, 5, 6, 7]]
+    gs1, ge1 = ops._tie_groups(torch.tensor([3.0, 3.0, 2.0, 1.0, 1.0, 1.0, 0.0]))      # one dimension, descending, as selective_tables sorts
+    assert gs1.tolist() == [0, 0, 2, 3, 3, 3, 6] and ge1.tolist() == [2, 2, 3, 6, 6, 6, 7]
+
+
 def test_kappa_batch_restates_kappa_quadratic():
     g = np.random.default_rng(0)
     conf = g.integers(0, 6, (40, 5, 5))
