@@ -1,4 +1,4 @@
-// What the resampling evaluation kernels share (bootstrap.hip, selective.hip, conformal.hip): one 256-thread workgroup per replicate b,
+// What the resampling evaluation kernels share (bootstrap.hip, selective.hip, conformal.hip, roc.hip): one 256-thread workgroup per replicate b,
 // the replicate drawn from hash_u32(seed, b N + n), and an inclusive scan over the sorted positions held in LDS.
 #pragma once
 #include "common.hpp"

@@ -223,6 +223,7 @@ SIGNATURES = {
     "gvk_bootstrap_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_uint64, _I, _P],
     "gvk_risk_coverage": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_uint64, _I, _I, _P],
     "gvk_temperature_fit": [_P, _P, _P, _I, _I, C.c_double, C.c_double, _P],
+    "gvk_roc_replicates": [_P] * 18 + [_I, _I, _I, _I, _I, _I, C.c_uint64, _I, _I, _P],
     "gvk_conformal_scores": [_P, _P, _I, _I, _I, _I, C.c_uint64, _I, _F, _P],
     "gvk_conformal_splits": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P],
     "gvk_token_pool": [_P, _P, _I, _I, _I, _I, _I, _P],

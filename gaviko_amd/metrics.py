@@ -572,6 +572,256 @@ def conformal_evaluate(proba: torch.Tensor, labels: torch.Tensor, *, alphas=(0.1
                                mondrian=bool(mondrian), score=score, level=float(level), counts=counts)
 
 
+class RocAnalysis(NamedTuple):
+    thresholds: np.ndarray                 # float32 [G + 1]: +inf (point 0: call nothing positive), then the distinct scores, descending
+    tp: np.ndarray                         # int64 [G + 1]: positives with score >= threshold
+    fp: np.ndarray                         # int64 [G + 1]: negatives with score >= threshold
+    tpr: np.ndarray                        # float64 [G + 1]: tp / positives (NaN without a positive row)
+    fpr: np.ndarray                        # float64 [G + 1]: fp / negatives (NaN without a negative row)
+    positives: int
+    negatives: int
+    auc: float                             # (2 #{positive above negative} + #{tied pairs}) / (2 positives negatives); NaN when undefined
+    auc_se: float                          # DeLong's standard error of auc (NaN with fewer than 2 positives or 2 negatives)
+    average_precision: float               # sum_g (tp_g / positives) * precision_g: sklearn's step definition
+    sensitivity_at: Dict[float, float]     # specificity level -> the largest sensitivity of a point with specificity >= level
+    specificity_at: Dict[float, float]     # sensitivity level -> the largest specificity of a point with sensitivity >= level
+    at_threshold: Dict[float, Dict[str, float]]   # fixed threshold -> sensitivity, specificity, ppv, npv of "score >= threshold" (NaN: empty denominator)
+    youden: Tuple[float, float, float, float]     # (threshold, sensitivity, specificity, J) of the point with the largest J = sens + spec - 1
+    replicates: Optional[Dict[str, np.ndarray]]   # float64 [R] per scalar, see roc_analysis (None without replicates, as the five below are)
+    ci: Optional[Dict[str, Tuple[float, float]]]
+    stderr: Optional[Dict[str, float]]
+    undefined: Optional[Dict[str, int]]    # NaN replicates per scalar
+    counts: Optional[Dict[str, np.ndarray]]       # the device's integers per replicate: total, auc2, at_spec, at_sens, at_cut, youden
+    placements: np.ndarray                 # int64 [N], row order: DeLong's integer placement of every row (delong_placements)
+    seed: int
+    stratified: bool
+    level: float
+
+
+class RocComparison(NamedTuple):
+    delta_point: Dict[str, float]          # a - b on the full sample, per scalar of RocAnalysis.replicates
+    delta: Dict[str, np.ndarray]           # float64 [R], a - b per replicate (the same multiplicities on both sides)
+    ci: Dict[str, Tuple[float, float]]     # percentile interval of delta
+    p_value: Dict[str, float]              # two-sided, paired_p_value(delta)
+    delong_z: float                        # (auc_a - auc_b) / sqrt(DeLong's variance of the difference of two correlated curves)
+    delong_p: float                        # two-sided normal p-value of delong_z
+    a: RocAnalysis
+    b: RocAnalysis
+    seed: int
+    stratified: bool
+    level: float
+
+
+def binary_cut(proba: torch.Tensor, labels: torch.Tensor, cut: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The binary reading "grade >= cut" of K ordered classes (radiographic OA is KL >= 2): proba [N, K], labels [N] ->
+    (score = proba[:, cut:].sum(1), positive = labels >= cut).  1 <= cut < K."""
+    if not isinstance(proba, torch.Tensor) or proba.dim() != 2:
+        raise GavikoHipError(f"binary_cut: expected proba [N, K], got {tuple(proba.shape) if isinstance(proba, torch.Tensor) else type(proba).__name__}")
+    K = proba.shape[1]
+    if isinstance(cut, bool) or not isinstance(cut, int) or not 1 <= cut < K:
+        raise GavikoHipError(f"binary_cut: cut = {cut!r} outside [1, {K})")
+    return proba[:, cut:].sum(1), torch.as_tensor(labels).to(proba.device) >= cut
+
+
+def delong_placements(tp, fp, gend, order, positive) -> np.ndarray:
+    """DeLong's placements as integers, host only.  tp, fp [N]: per sorted position (descending score) the positives / negatives at or above
+    its score (the curve gvk_roc_replicates writes); gend [N]: one past the end of its tie group; order [N]: the row at every sorted position;
+    positive bool [N] in row order.  -> psi int64 [N] in row order:
+      positive row:  2 #{negatives scoring lower} + #{negatives tied}  in [0, 2 Nn]
+      negative row:  2 #{positives scoring higher} + #{positives tied}  in [0, 2 Pn]
+    so that AUC = sum(psi over the positives) / (2 Pn Nn) = sum(psi over the negatives) / (2 Pn Nn)."""
+    tp, fp, gend = np.asarray(tp, dtype=np.int64), np.asarray(fp, dtype=np.int64), np.asarray(gend, dtype=np.int64)
+    order, positive = np.asarray(order, dtype=np.int64), np.asarray(positive, dtype=bool)
+    N = tp.size
+    last = gend == np.arange(1, N + 1)
+    group = np.concatenate([[0], np.cumsum(last)[:-1]])                    # the tie group of every sorted position
+    TP, FP = np.concatenate([[0], tp[last]]), np.concatenate([[0], fp[last]])
+    tp_g, fp_g = np.diff(TP)[group], np.diff(FP)[group]
+    pos_s = positive[order]
+    psi_s = np.where(pos_s, 2 * (FP[-1] - FP[group + 1]) + fp_g, 2 * TP[group] + tp_g)
+    psi = np.empty(N, dtype=np.int64)
+    psi[order] = psi_s
+    return psi
+
+
+def delong_covariance(psi_a, psi_b, positive) -> float:
+    """DeLong, DeLong & Clarke-Pearson (1988): the covariance S10 / Pn + S01 / Nn of the AUCs of two scores on the same rows, from their
+    integer placements (delong_placements; psi_a is psi_b: the variance of one AUC).  The sums sum psi, sum psi_a psi_b are exact integers
+    (psi <= 2^14, N <= 2^13); each part is (n sum ab - sum a sum b) / (4 m^2 n^2 (n - 1)), n the rows of the part's own class and m those of
+    the other, formed in float64 from the exact numerator and denominator.  NaN with fewer than 2 positive or 2 negative rows."""
+    a, b, positive = np.asarray(psi_a, dtype=np.int64), np.asarray(psi_b, dtype=np.int64), np.asarray(positive, dtype=bool)
+    Pn, Nn = int(positive.sum()), int((~positive).sum())
+    if Pn < 2 or Nn < 2:
+        return float("nan")
+
+    def part(x, y, n, m):
+        num = n * int((x * y).sum()) - int(x.sum()) * int(y.sum())
+        return float(num) / float(4 * m * m * n * n * (n - 1))
+
+    return part(a[positive], b[positive], Pn, Nn) + part(a[~positive], b[~positive], Nn, Pn)
+
+
+def _roc_bp(what: str, levels) -> List[int]:
+    try:
+        lv = [float(q) for q in levels]
+    except TypeError:
+        raise GavikoHipError(f"roc_analysis: {what} = {levels!r} (a sequence of numbers within [0, 1])") from None
+    if len(lv) > ops.ROC_MAX_LEVELS:
+        raise GavikoHipError(f"roc_analysis: {len(lv)} {what} (at most {ops.ROC_MAX_LEVELS})")
+    if any(not 0.0 <= q <= 1.0 for q in lv):
+        raise GavikoHipError(f"roc_analysis: {what} = {levels!r} (each within [0, 1])")
+    return [int(round(q * ops.ROC_BASIS_POINTS)) for q in lv]
+
+
+def _div(num, den) -> np.ndarray:
+    """num / den in float64, NaN where den == 0"""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.divide(num, den, out=np.full(np.broadcast(num, den).shape, np.nan), where=den != 0)
+
+
+def roc_scalars(counts: Dict[str, np.ndarray], spec_bp, sens_bp, thresholds, sorted_score: np.ndarray) -> Dict[str, np.ndarray]:
+    """The scalars of R replicates, float64 [R] each, from the integers of gvk_roc_replicates (host arrays).  With (Pn, Nn) = total:
+      auc = auc2 / (2 Pn Nn);  average_precision = ap;  youden_*: of the kernel's point, J = sensitivity + specificity - 1
+      sens@spec=<q>: TP / Pn of at_spec;  spec@sens=<q>: (Nn - FP) / Nn of at_sens  (q = level in basis points / 10000)
+      sens@thr=<t>, spec@thr=<t>, ppv@thr=<t> = TP / (TP + FP), npv@thr=<t> = TN / (TN + FN) of at_cut
+    A replicate with Pn = 0 or Nn = 0 has no curve: every scalar but the predictive values is NaN there; a predictive value is NaN where its
+    own denominator is 0."""
+    total = np.asarray(counts["total"], dtype=np.int64)
+    Pn, Nn = total[:, 0], total[:, 1]
+    both = (Pn > 0) & (Nn > 0)
+    nan = lambda v: np.where(both, v, np.nan)                              # noqa: E731
+    out = {"auc": nan(_div(counts["auc2"], 2.0 * Pn * Nn)), "average_precision": nan(np.asarray(counts["ap"], dtype=np.float64))}
+    for i, a in enumerate(spec_bp):
+        out[f"sens@spec={a / ops.ROC_BASIS_POINTS}"] = nan(_div(counts["at_spec"][:, i, 0], Pn))
+    for i, a in enumerate(sens_bp):
+        out[f"spec@sens={a / ops.ROC_BASIS_POINTS}"] = nan(_div(Nn - counts["at_sens"][:, i, 1], Nn))
+    for i, t in enumerate(thresholds):
+        TP, FP = counts["at_cut"][:, i, 0].astype(np.int64), counts["at_cut"][:, i, 1].astype(np.int64)
+        out[f"sens@thr={t}"], out[f"spec@thr={t}"] = nan(_div(TP, Pn)), nan(_div(Nn - FP, Nn))
+        out[f"ppv@thr={t}"], out[f"npv@thr={t}"] = _div(TP, TP + FP), _div(Nn - FP, (Nn - FP) + (Pn - TP))
+    y = np.asarray(counts["youden"], dtype=np.int64)
+    sens, spec = nan(_div(y[:, 0], Pn)), nan(_div(Nn - y[:, 1], Nn))
+    out.update(youden_threshold=nan(np.asarray(sorted_score, dtype=np.float64)[y[:, 2]]), youden_sensitivity=sens, youden_specificity=spec,
+               youden_j=sens + spec - 1.0)
+    return out
+
+
+def roc_analysis(score: torch.Tensor, positive: torch.Tensor, *, specificities=(0.9, 0.95), sensitivities=(0.9,), thresholds=(),
+                 replicates: Optional[int] = None, seed: int = 0, stratified: bool = False, strata: Optional[torch.Tensor] = None,
+                 level: float = 0.95) -> RocAnalysis:
+    """The ROC analysis of a binary reading (binary_cut gives the one of ordered grades): score f32 [N] on the device, HIGHER = MORE
+    POSITIVE, no NaN; positive [N] (bool, or integers with nonzero = positive).  Rows with EQUAL scores are one point of the curve (nothing
+    depends on the order inside a tie).  Point g calls a row positive when score >= thresholds[g]; point 0 calls nothing positive.
+      specificities: sensitivity_at[q] = the sensitivity of the last point whose specificity is still >= q
+      sensitivities: specificity_at[q] = the specificity of the first point whose sensitivity is already >= q
+      thresholds:    at_threshold[t] = sensitivity, specificity, ppv, npv of the rule score >= t (t compared with the float32 scores in float64)
+    Levels are rounded to BASIS POINTS (0.0001) and compared in exact integers, each within [0, 1], at most 8 per list.
+    auc_se is DeLong's (delong_covariance of the rows' placements).  replicates = R adds bootstrap replicates of every scalar -- roc_scalars
+    names them -- drawn by the rule of `bootstrap` (same seed and rule = the same resamples, replicate for replicate), with percentile
+    intervals, standard errors and the number of undefined (NaN) replicates: a replicate without a positive or without a negative row is
+    counted there, not raised.  stratified = True keeps the size of every stratum in every replicate; `strata` [N] are the strata's integer
+    labels, by default the binary label itself (pass the K grades to repeat the resamples of bootstrap(..., stratified=True)).
+    gvk_roc_replicates computes all integers exactly on the device.  N <= 8192, strata < 64."""
+    if not isinstance(score, torch.Tensor) or score.dim() != 1 or score.numel() < 1:
+        raise GavikoHipError(f"roc_analysis: expected score [N], got {tuple(score.shape) if isinstance(score, torch.Tensor) else type(score).__name__}")
+    N = score.numel()
+    if N > ops.BOOTSTRAP_MAX_ROWS:
+        raise GavikoHipError(f"roc_analysis: N = {N} outside N <= {ops.BOOTSTRAP_MAX_ROWS}")
+    spec_bp, sens_bp = _roc_bp("specificities", specificities), _roc_bp("sensitivities", sensitivities)
+    try:
+        thr = [float(t) for t in thresholds]
+    except TypeError:
+        raise GavikoHipError(f"roc_analysis: thresholds = {thresholds!r} (a sequence of numbers)") from None
+    if len(thr) > ops.ROC_MAX_LEVELS or any(t != t for t in thr):
+        raise GavikoHipError(f"roc_analysis: thresholds = {thresholds!r} (at most {ops.ROC_MAX_LEVELS}, none NaN)")
+    _check_replicates("roc_analysis", replicates, optional=True)
+    _check_level("roc_analysis", level)
+    if bool(torch.isnan(score).any()):
+        raise GavikoHipError("roc_analysis: NaN scores have no rank")
+    _device_tensor("roc_analysis", score, "scores")
+    score = score.detach().float().contiguous()
+    positive = torch.as_tensor(positive).to(score.device).reshape(-1) != 0
+    if positive.numel() != N:
+        raise GavikoHipError(f"roc_analysis: {positive.numel()} labels for {N} scores")
+    strata = positive.to(torch.int64) if strata is None else torch.as_tensor(strata).to(score.device).to(torch.int64).contiguous().reshape(-1)
+    if strata.numel() != N:
+        raise GavikoHipError(f"roc_analysis: {strata.numel()} strata labels for {N} scores")
+    if int(strata.min()) < 0 or int(strata.max()) >= ops.BOOTSTRAP_MAX_CLASSES:
+        raise GavikoHipError(f"roc_analysis: strata outside [0, {ops.BOOTSTRAP_MAX_CLASSES})")
+    pos32 = positive.to(torch.int32)
+    tables = ops.roc_tables(score, pos32, strata)
+    sorted_score = tables["sorted_score"].cpu().numpy()
+    wide = sorted_score.astype(np.float64)
+    cut_rows = [int((wide >= t).sum()) for t in thr]
+    full_d = ops.roc_counts(pos32, strata, tables, spec_bp, sens_bp, cut_rows, resample=False, curve=True)
+    rep_d = ops.roc_counts(pos32, strata, tables, spec_bp, sens_bp, cut_rows, replicates, seed, bool(stratified)) if replicates is not None else None
+    full = {k: v.cpu().numpy() for k, v in full_d.items()}
+    gend, order = tables["gend"].cpu().numpy(), tables["order"].cpu().numpy()
+    last = gend == np.arange(1, N + 1)                                    # the last position of every tie group: one entry per distinct score
+    tp = np.concatenate([[0], full["tp"][last]]).astype(np.int64)
+    fp = np.concatenate([[0], full["fp"][last]]).astype(np.int64)
+    Pn, Nn = int(full["total"][0, 0]), int(full["total"][0, 1])
+    point = {k: float(v[0]) for k, v in roc_scalars(full, spec_bp, sens_bp, thr, sorted_score).items()}
+    psi = delong_placements(full["tp"], full["fp"], gend, order, positive.cpu().numpy())
+    var = delong_covariance(psi, psi, positive.cpu().numpy())
+    rep = ci = se = undefined = counts = None
+    if rep_d is not None:
+        counts = {k: v.cpu().numpy() for k, v in rep_d.items()}
+        rep = roc_scalars(counts, spec_bp, sens_bp, thr, sorted_score)
+        ci = {k: _interval(v, float(level)) for k, v in rep.items()}
+        se = {k: _stderr(v) for k, v in rep.items()}
+        undefined = {k: int(np.isnan(v).sum()) for k, v in rep.items()}
+    B = float(ops.ROC_BASIS_POINTS)
+    return RocAnalysis(thresholds=np.concatenate([[np.float32(np.inf)], sorted_score[last]]).astype(np.float32), tp=tp, fp=fp, tpr=_div(tp, Pn),
+                       fpr=_div(fp, Nn), positives=Pn, negatives=Nn, auc=point["auc"], auc_se=float(np.sqrt(var)),
+                       average_precision=point["average_precision"],
+                       sensitivity_at={a / B: point[f"sens@spec={a / B}"] for a in spec_bp},
+                       specificity_at={a / B: point[f"spec@sens={a / B}"] for a in sens_bp},
+                       at_threshold={t: {"sensitivity": point[f"sens@thr={t}"], "specificity": point[f"spec@thr={t}"], "ppv": point[f"ppv@thr={t}"],
+                                         "npv": point[f"npv@thr={t}"]} for t in thr},
+                       youden=(point["youden_threshold"], point["youden_sensitivity"], point["youden_specificity"], point["youden_j"]),
+                       replicates=rep, ci=ci, stderr=se, undefined=undefined, counts=counts, placements=psi, seed=int(seed),
+                       stratified=bool(stratified), level=float(level))
+
+
+def roc_compare(score_a: torch.Tensor, score_b: torch.Tensor, positive: torch.Tensor, *, specificities=(0.9, 0.95), sensitivities=(0.9,),
+                thresholds=(), replicates: int = 2000, seed: int = 0, stratified: bool = False, strata: Optional[torch.Tensor] = None,
+                level: float = 0.95) -> RocComparison:
+    """Paired comparison of two scores on the same rows: both are resampled with the same multiplicities (the rule depends on (seed,
+    replicate, draw, strata) alone), so delta = a - b per replicate is the paired difference.  Per scalar of roc_analysis: delta_point, delta
+    [R], its percentile interval, and paired_p_value(delta) over the replicates where both sides are defined.  For the AUC also DeLong's test
+    of two correlated curves: z = (auc_a - auc_b) / sqrt(var_a + var_b - 2 cov_ab) from delong_covariance, p two-sided normal; both NaN when
+    the variance of the difference is 0 or undefined."""
+    import math
+    if not isinstance(score_a, torch.Tensor) or not isinstance(score_b, torch.Tensor) or tuple(score_a.shape) != tuple(score_b.shape):
+        raise GavikoHipError("roc_compare: the two models' scores must be device tensors of one shape [N]")
+    _check_replicates("roc_compare", replicates)
+    kw = dict(specificities=specificities, sensitivities=sensitivities, thresholds=thresholds, replicates=replicates, seed=seed,
+              stratified=stratified, strata=strata, level=level)
+    a, b = roc_analysis(score_a, positive, **kw), roc_analysis(score_b, positive, **kw)
+    delta = {k: a.replicates[k] - b.replicates[k] for k in a.replicates}
+    point_a, point_b = _roc_point(a), _roc_point(b)
+    pos = (torch.as_tensor(positive).reshape(-1) != 0).cpu().numpy()
+    var = delong_covariance(a.placements, a.placements, pos) + delong_covariance(b.placements, b.placements, pos) \
+        - 2.0 * delong_covariance(a.placements, b.placements, pos)
+    z = (a.auc - b.auc) / math.sqrt(var) if var > 0.0 else float("nan")
+    return RocComparison(delta_point={k: point_a[k] - point_b[k] for k in delta}, delta=delta,
+                         ci={k: _interval(v, float(level)) for k, v in delta.items()}, p_value={k: paired_p_value(v) for k, v in delta.items()},
+                         delong_z=z, delong_p=math.erfc(abs(z) / math.sqrt(2.0)) if z == z else float("nan"), a=a, b=b, seed=int(seed),
+                         stratified=bool(stratified), level=float(level))
+
+
+def _roc_point(r: RocAnalysis) -> Dict[str, float]:
+    """the full-sample scalars of a RocAnalysis under the names of its replicates"""
+    out = {"auc": r.auc, "average_precision": r.average_precision, "youden_threshold": r.youden[0], "youden_sensitivity": r.youden[1],
+           "youden_specificity": r.youden[2], "youden_j": r.youden[3]}
+    out.update({f"sens@spec={q}": v for q, v in r.sensitivity_at.items()})
+    out.update({f"spec@sens={q}": v for q, v in r.specificity_at.items()})
+    for t, d in r.at_threshold.items():
+        out.update({f"sens@thr={t}": d["sensitivity"], f"spec@thr={t}": d["specificity"], f"ppv@thr={t}": d["ppv"], f"npv@thr={t}": d["npv"]})
+    return out
+
+
 _bootstrap = bootstrap                                     # Evaluator.compute has a parameter of that name
 
 
@@ -586,14 +836,16 @@ class Evaluator:
         self._labels.append(labels.detach().to(torch.int64))
 
     def compute(self, bootstrap: Optional[int] = None, seed: int = 0, stratified: bool = False, *, selective: bool = False,
-                temperature: Optional[float] = None, conformal=None) -> Dict[str, object]:
+                temperature: Optional[float] = None, conformal=None, roc: Optional[int] = None) -> Dict[str, object]:
         """bootstrap = R adds "bootstrap" (the BootstrapResult of R replicates with this seed and rule, on the probabilities and predictions
         computed here) and "report" (classification_report of the confusion matrix); None returns the keys eval.py needs and "calibration".
         selective = True adds "selective": the RiskCoverage of the max-probability confidence, with R replicates of the same seed and rule
         when bootstrap = R.  temperature = T > 0 (fit_temperature on validation rows) takes the probabilities, and with them "auc",
         "calibration", "bootstrap" and "selective", from logits / T; the predictions and the confusion matrix stay those of the logits.
         conformal = alpha (or a sequence of them) adds "conformal": the ConformalEvaluation of the lac score over random halves of these rows
-        (conformal_evaluate with this seed; `bootstrap` replicates when given, else 1000), on the probabilities computed here."""
+        (conformal_evaluate with this seed; `bootstrap` replicates when given, else 1000), on the probabilities computed here.
+        roc = cut adds "roc": the RocAnalysis of the binary reading "class >= cut" (binary_cut of the probabilities computed here), with R
+        replicates of the same seed and rule when bootstrap = R; the stratified draw keeps the sizes of the K classes, as "bootstrap" does."""
         logits = torch.cat(self._logits).contiguous()
         labels = torch.cat(self._labels).contiguous().to(self.device)
         N, K = logits.shape
@@ -628,6 +880,8 @@ class Evaluator:
         if conformal is not None:
             out["conformal"] = conformal_evaluate(proba, labels, alphas=conformal if isinstance(conformal, (list, tuple)) else (conformal,),
                                                   replicates=1000 if bootstrap is None else bootstrap, seed=seed)
+        if roc is not None:
+            out["roc"] = roc_analysis(*binary_cut(proba, labels, roc), replicates=bootstrap, seed=seed, stratified=stratified, strata=labels)
         return out
 
 

@@ -1814,6 +1814,87 @@ def temperature_fit(logits: torch.Tensor, target: torch.Tensor, t_min: float = 0
     return state
 
 
+# ---- ROC operating points of a binary reading (csrc/roc.hip) ----
+ROC_MAX_LEVELS = 8              # gvk_roc_replicates: entries of each of the three level lists answered per launch
+ROC_BASIS_POINTS = 10000
+
+
+def roc_tables(score: torch.Tensor, positive: torch.Tensor, strata: torch.Tensor = None) -> dict:
+    """The per-call tables of gvk_roc_replicates, built with torch on the device (plumbing: once per call, not per replicate).
+    score f32 [N] (higher = more positive, no NaN), positive [N] (bool or integers, nonzero = positive), strata i64 [N] >= 0 (the labels the
+    stratified draw keeps the sizes of; default: the binary label) -> order i32 [N] (the rows by descending score, stable), gend i32 [N]
+    (per sorted position, one past the end of its group of equal scores), class_rows i32 [N] / class_off i32 [K + 1] (the rows grouped by
+    stratum, as ops.bootstrap_tables has them; K = the largest stratum + 1) and sorted_score f32 [N] (score[order], for the thresholds)."""
+    N = score.numel()
+    vals, order = torch.sort(score.reshape(N), descending=True, stable=True)
+    if strata is None:
+        strata = (positive.reshape(N) != 0).to(torch.int64)
+    class_rows, class_off = _class_groups(strata, int(strata.max()) + 1 if N else 1)
+    return {"order": _i32(order), "gend": _i32(_tie_groups(vals)[1]), "class_rows": class_rows, "class_off": class_off,
+            "sorted_score": vals.contiguous()}
+
+
+def _roc_levels(what: str, levels, hi: int) -> list:
+    levels = [v for v in levels]
+    if len(levels) > ROC_MAX_LEVELS:
+        raise L.GavikoHipError(f"roc_counts: {len(levels)} {what} entries (at most {ROC_MAX_LEVELS} per launch)")
+    if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= hi for v in levels):
+        raise L.GavikoHipError(f"roc_counts: {what} = {levels!r} (integers within [0, {hi}])")
+    return levels
+
+
+def roc_counts(positive: torch.Tensor, strata: torch.Tensor, tables: dict, spec_bp=(), sens_bp=(), cut_rows=(), replicates: int = 1,
+               seed: int = 0, stratified: bool = False, resample: bool = True, curve: bool = False) -> dict:
+    """The ROC integers of `replicates` resamples (resample=True: the multiplicities of gvk_bootstrap_counts / gvk_risk_coverage for the same
+    seed and rule) or of the full sample (resample=False, replicates must be 1; curve=True then also writes the curve); include/gaviko_hip.h has
+    the definitions.  positive i32 [N] (nonzero = positive), strata i64 [N] (the labels of the stratified draw; None unless stratified),
+    tables = roc_tables(score, positive, strata); spec_bp / sens_bp: up to 8 host integers each, levels in basis points within [0, 10000];
+    cut_rows: up to 8 host integers within [0, N] (rows at or above a fixed threshold).  -> dict of device tensors: total i32 [R, 2] = (Pn, Nn),
+    auc2 i64 [R], ap f64 [R] (average precision, NaN without a positive row), at_spec / at_sens / at_cut i32 [R, Q, 2] = (TP, FP), youden i32
+    [R, 3] = (TP, FP, sorted position) and, with curve=True, tp / fp i32 [N] (per sorted position the counts at the end of its tie group).
+    N <= 8192."""
+    N = positive.numel()
+    _replicate_rows("roc_counts", N)
+    R = _replicates("roc_counts", replicates)
+    if not resample and R != 1:
+        raise L.GavikoHipError(f"roc_counts: resample=False is the full sample, replicates = {R} must be 1")
+    if curve and resample:
+        raise L.GavikoHipError("roc_counts: the curve is written with resample=False only")
+    spec_bp = _roc_levels("spec_bp", spec_bp, ROC_BASIS_POINTS)
+    sens_bp = _roc_levels("sens_bp", sens_bp, ROC_BASIS_POINTS)
+    cut_rows = _roc_levels("cut_rows", cut_rows, N)
+    class_off = tables.get("class_off")
+    if class_off is None or class_off.numel() < 2:
+        raise L.GavikoHipError("roc_counts class_off: expected an int32 [K + 1] table, K >= 1")
+    K = class_off.numel() - 1
+    if K > BOOTSTRAP_MAX_CLASSES:
+        raise L.GavikoHipError(f"roc_counts: K = {K} strata outside [1, {BOOTSTRAP_MAX_CLASSES}]")
+    if resample and stratified and strata is None:
+        raise L.GavikoHipError("roc_counts: the stratified draw needs the strata labels")
+    _tab(positive, "roc_counts positive", N)
+    _chk(strata, torch.int64, "roc_counts strata")
+    if strata is not None and strata.numel() != N:
+        raise L.GavikoHipError(f"roc_counts strata: expected {N} labels, got {tuple(strata.shape)}")
+    _tab(tables.get("order"), "roc_counts order", N)
+    _tab(tables.get("gend"), "roc_counts gend", N)
+    _tab(tables.get("class_rows"), "roc_counts class_rows", N)
+    _tab(class_off, "roc_counts class_off", K + 1)
+    dev = positive.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)   # noqa: E731
+    Qs, Qn, Qc = len(spec_bp), len(sens_bp), len(cut_rows)
+    out = {"total": i32(R, 2), "auc2": torch.empty(R, dtype=torch.int64, device=dev), "ap": torch.empty(R, dtype=torch.float64, device=dev),
+           "at_spec": i32(R, Qs, 2), "at_sens": i32(R, Qn, 2), "at_cut": i32(R, Qc, 2), "youden": i32(R, 3)}
+    if curve:
+        out["tp"], out["fp"] = i32(N), i32(N)
+    levels = torch.tensor(spec_bp + sens_bp + cut_rows, dtype=torch.int32, device=dev) if Qs + Qn + Qc else None      # one upload for the three lists
+    lv = lambda a, n: levels[a:a + n] if n else None                        # noqa: E731
+    L.launch.gvk_roc_replicates(strata, positive, tables["order"], tables["gend"], tables["class_rows"], class_off, lv(0, Qs), lv(Qs, Qn),
+                                lv(Qs + Qn, Qc), out["total"], out["auc2"], out["ap"], out["at_spec"] if Qs else None, out["at_sens"] if Qn else None,
+                                out["at_cut"] if Qc else None, out["youden"], out.get("tp"), out.get("fp"), N, K, Qs, Qn, Qc, R, _seed64(seed),
+                                1 if stratified else 0, 1 if resample else 0)
+    return out
+
+
 # ---- split-conformal prediction sets (csrc/conformal.hip) ----
 CONFORMAL_MAX_CLASSES = 64      # gvk_conformal_scores: one class per lane of a wave
 CONFORMAL_MAX_LEVELS = 8        # gvk_conformal_splits: miscoverage levels answered per launch

@@ -932,6 +932,48 @@ int gvk_risk_coverage(const void* labels, const int32_t* pred, const int32_t* or
                       int32_t* errors, int N, int K, int Q, int R, uint64_t seed, int stratified, int resample, void* stream);
 int gvk_temperature_fit(const float* logits, const void* target, double* state, int N, int K, double t_min, double t_max, void* stream);
 
+/* ---- ROC operating points of a binary reading (csrc/roc.hip; gaviko_amd.metrics.roc_analysis / roc_compare) ----
+ * gvk_roc_replicates: the ROC curve of a score against a binary label for R replicates of the N rows of an evaluation set.  positive int32 [N]:
+ *   a row is POSITIVE when its entry is not 0.  The scores enter through their order alone, computed once per call by the caller (DEVICE tables,
+ *   int32):
+ *     order [N]                     the rows by DESCENDING score (a stable sort: equal scores in row order)
+ *     gend [N]                      per sorted position, one past the last sorted position of its group of equal scores
+ *     strata int64 [N], class_rows [N], class_off [K+1]   the labels the stratified draw keeps the sizes of (any labelling of the rows: the
+ *                                   binary label, or the K grades behind it) and the tables of gvk_bootstrap_counts for them (read with
+ *                                   resample = 1 and stratified = 1 only; 1 <= K <= GVK_BOOTSTRAP_MAX_CLASSES there, strata clamped into [0, K))
+ *     spec_bp [Qspec], sens_bp [Qsens]   levels in BASIS POINTS (clamped into [0, 10000]); cut_rows [Qcut]: m_q = the number of full-sample
+ *                                   rows with score >= the q-th fixed threshold (clamped into [0, N]; the host finds it from the sorted
+ *                                   scores).  Each list has 0 .. GVK_ROC_MAX_LEVELS entries
+ *   Multiplicities w on the rows: resample = 1 draws replicate b exactly as gvk_bootstrap_counts / gvk_risk_coverage do (hash_u32(seed, b*N + n),
+ *   plain or stratified, see above), so replicate b here and there is the same resample; resample = 0 requires R = 1 and gives every row w = 1.
+ *   Let v_1 > v_2 > ... > v_G be the distinct scores of the full sample, tp_g / fp_g the summed w of the positive / negative rows with score
+ *   v_g, TP_g / FP_g their running sums.  Point g means "call positive when score >= v_g"; point 0 is (0, 0) (call nothing positive);
+ *   Pn = TP_G, Nn = FP_G.  A group of equal scores is taken together.  Written per replicate b, not accumulated:
+ *     total int32 [R][2]            (Pn, Nn)
+ *     auc2 int64 [R]                sum_g tp_g (2 (Nn - FP_g) + fp_g) = 2 (pairs where the positive scores higher) + (tied pairs), exact;
+ *                                   AUC = auc2 / (2 Pn Nn), formed by the host
+ *     ap f64 [R]                    average precision (the step definition of sklearn), DIVIDED BY Pn IN THE KERNEL:
+ *                                   (1 / Pn) sum over g with tp_g > 0 of tp_g TP_g / (TP_g + FP_g); NaN when Pn = 0.  Each product is an exact
+ *                                   integer below 2^26 and takes one rounding in the division; the terms are added in a fixed order (thread t
+ *                                   the groups starting at t, t + 256, ..; a wave's xor butterfly; the 4 waves), then one division
+ *     at_spec int32 [R][Qspec][2]   (TP_g, FP_g) of the LAST point g in 0..G with (Nn - FP_g) * 10000 >= spec_bp[q] * Nn: the sensitivity at
+ *                                   specificity >= spec_bp[q] / 10000.  Exact in 32-bit integers; point 0 always qualifies
+ *     at_sens int32 [R][Qsens][2]   (TP_g, FP_g) of the FIRST point g in 0..G with TP_g * 10000 >= sens_bp[q] * Pn: the specificity at
+ *                                   sensitivity >= sens_bp[q] / 10000.  Point G always qualifies
+ *     at_cut int32 [R][Qcut][2]     the running (TP, FP) over the first m_q sorted positions; m_q = 0 gives (0, 0)
+ *     youden int32 [R][3]           (TP_g, FP_g, s_g) of the point maximising TP_g * Nn - FP_g * Pn over the points 1..G that a draw reached
+ *                                   (tp_g + fp_g > 0); on a tie the smallest g.  s_g = the first sorted position of the group: the threshold
+ *                                   is score[order[s_g]]
+ *     tp, fp int32 [N]              resample = 0 only (else NULL; both or neither): per sorted position the (TP_g, FP_g) of its group
+ *   One 256-thread workgroup per replicate; multiplicities by 32-bit LDS atomics, no atomics on global memory; one packed inclusive scan
+ *   (positive ? w << 16 : w) in tiles of 1024.  The integers are exact, ap has the same bits on every run.  1 <= N <= GVK_BOOTSTRAP_MAX_ROWS,
+ *   R >= 1 (the grid's x dimension).  LDS: 8 * ceil(N / 1024) * 1024 bytes. */
+enum { GVK_ROC_MAX_LEVELS = 8 };
+int gvk_roc_replicates(const void* strata, const int32_t* positive, const int32_t* order, const int32_t* gend, const int32_t* class_rows,
+                       const int32_t* class_off, const int32_t* spec_bp, const int32_t* sens_bp, const int32_t* cut_rows, int32_t* total,
+                       int64_t* auc2, double* ap, int32_t* at_spec, int32_t* at_sens, int32_t* at_cut, int32_t* youden, int32_t* tp, int32_t* fp,
+                       int N, int K, int Qspec, int Qsens, int Qcut, int R, uint64_t seed, int stratified, int resample, void* stream);
+
 /* ---- split-conformal prediction sets (csrc/conformal.hip; gaviko_amd.metrics.conformal_scores / conformal_calibrate / conformal_evaluate) ----
  * gvk_conformal_scores: proba f32 [N][K] -> scores f32 [K][N] (CLASS-MAJOR: gvk_conformal_splits reads a class column over consecutive rows).
  *   Rank of class k in its row, 0-based:  r_k = #{j : p_j > p_k or (p_j == p_k and j < k)}  (ties go to the lower class index); pi(r) = the
