@@ -394,7 +394,8 @@ int gvk_reduce_batch(const gvk_reduce_job* jobs, int njobs, float* scratch, void
 /* Every parameter gradient of one rank-L side-path module of one layer in ONE launch (csrc/paramgrad.hip): up to 3 outer products
  *   out[l][c] (transposed=0) or out[c][l] (transposed=1) (+)= sum_m narrow'[m][l] * wide'[m][c],   colsum[c] (+)= sum_m wide'[m][c]
  * (narrow f32 [M][L], wide f32 [M][C]; narrow' = narrow with the rows t < P of every T-row sample taken from lat_override [.][P][L];
- * wide' = (wide - mean[m]) * rstd[m] when mean / rstd are given, times the dropout mask of element (m, c) when drop_p > 0; a second
+ * wide' = (wide * the dropout mask of element (m, c) when drop_p > 0, - mean[m]) * rstd[m] when mean / rstd are given -- the mask first,
+ * as in gvk_outer_reduce; a second
  * source (narrow2, wide2, M2 plain rows) extends the same sum -- one weight fed by two token streams, gaviko.py:155-156), and up to 8
  * small reductions (gvk_reduce_job) over the same rows.  With aff_w (f32 [L][C] = the projection weight behind a LayerNorm, wide' = xhat)
  * the product Q is not stored: out[l][c] (+)= gamma_c Q[l][c] + beta_c S[l], aff_dgamma[c] (+)= sum_l w[l][c] Q[l][c],
