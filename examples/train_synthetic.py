@@ -12,7 +12,10 @@
 With --ragged the volumes have shapes and spacings of their own (VolumeDataset + collate_ragged) and data.Conform brings each batch onto
 the (120,160,160) grid on the device (Resample to 1 mm, CropOrPad) before the transforms above.
 
-usage: python examples/train_synthetic.py [--ragged] [--method gaviko] [--backbone vit-t16] [--epochs 3] [--samples 8] [--out /tmp/gaviko_run]"""
+With --histogram the last step is torchio's MRI recipe: data.HistogramStandardization with landmarks trained here on the training volumes, then
+ZNormalization above the mean.
+
+usage: python examples/train_synthetic.py [--ragged] [--histogram] [--method gaviko] [--backbone vit-t16] [--epochs 3] [--samples 8] [--out /tmp/gaviko_run]"""
 import argparse
 import os
 import sys
@@ -50,7 +53,7 @@ def make_dataset(root, n, num_classes, seed=0, ragged=False):
 
 
 def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False,
-        motion_augment=False, batch_mix=False, ragged=False):
+        motion_augment=False, batch_mix=False, ragged=False, histogram=False):
     dev = torch.device("cuda:0")
     K = 5
     csv = make_dataset(os.path.join(out, "data"), samples, K, seed, ragged)
@@ -68,6 +71,13 @@ def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gavi
     torch.manual_seed(seed)
     pre = data.DataPreprocessor(config, seed=seed)
     train_loader, val_loader, _, train_ds, val_ds, _ = pre.preprocess(None)
+    if histogram:       # torchio's recipe: landmarks learned once from the training volumes, then HistogramStandardization + ZNormalization
+        on_grid = (lambda batch: pre.conform(batch.to(dev))) if pre.conform is not None else (lambda batch: batch.to(dev))
+        path = os.path.join(out, "landmarks.npy")
+        landmarks = data.HistogramStandardization.train((on_grid(inputs) for inputs, _ in train_loader), masking_method="mean", output_path=path)
+        log(f"histogram landmarks from {len(train_ds)} training volumes: {np.round(landmarks, 2).tolist()}")
+        config["data"]["normalization"] = {"histogram": {"landmarks": path, "masking_method": "mean"}, "then": "znorm"}
+        pre = data.DataPreprocessor(config, seed=seed)                   # the loaders stay; the transforms now standardise first
     model = build_model(config["model"]).to(dev)
     tuning_params = load_pretrained.tuning_param_names(model)            # train.py:160-169
     log(f"{method}/{backbone}: {len(tuning_params)} trainable tensors, {len(train_ds)} train / {len(val_ds)} val volumes")
@@ -117,8 +127,10 @@ if __name__ == "__main__":
     ap.add_argument("--motion-augment", action="store_true", help="with --intensity-augment: add k-space motion as the fourth member of that group")
     ap.add_argument("--batch-mix", action="store_true", help="Mixup / CutMix of each training batch (data.BatchMix, timm's defaults) with the mixed-target loss")
     ap.add_argument("--ragged", action="store_true", help="synthetic volumes of unequal shape and spacing, brought onto the grid by data.Conform")
+    ap.add_argument("--histogram", action="store_true", help="train histogram landmarks on the synthetic training volumes (on the device) and "
+                    "normalise with data.HistogramStandardization followed by ZNormalization instead of the min-max rescale")
     a = ap.parse_args()
     res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment,
-              batch_mix=a.batch_mix, ragged=a.ragged)
+              batch_mix=a.batch_mix, ragged=a.ragged, histogram=a.histogram)
     print("checkpoint:", res["checkpoint"])
     print("results   :", res["results_csv"])

@@ -4,6 +4,9 @@
 //   gvk_volume_stats        min / max / float64 mean of every voxel, then count, float64 mean and unbiased std of the masked voxels (x > t)
 //   gvk_volume_order_stats  exact order statistics of the masked voxels by a most-significant-first radix select, 11 / 11 / 10 bits
 //   gvk_normalize_intensity a tiny step that turns those tables into per-sample parameters and a status word, and one streaming apply pass
+// and tio.HistogramStandardization on the same machinery:
+//   gvk_volume_landmarks    the same order statistics at up to 16 percentiles in four sweeps of 8-bit digits, whatever the ranks fall under
+//   gvk_histogram_standardize  per-sample piecewise-linear map from the volume's landmarks onto trained ones, and its streaming apply pass
 //
 // Every streaming kernel walks a sample the same way (stream_slab): sample b starts at x + b V, which is 16-byte aligned only when b V is a
 // multiple of 4, so a sample is cut into a head of 0..3 voxels up to the next 16-byte boundary, a body of 16-byte loads shared out in equal
@@ -420,6 +423,256 @@ __global__ __launch_bounds__(256) void normalize_apply_kernel(const float* __res
 
 static int normalize_slabs(int64_t V) { return (int)std::min<int64_t>(kNmSlabs, std::max<int64_t>(1, (V / 4 + 1023) / 1024)); }
 
+// ---- landmarks: up to 16 order statistics in a fixed number of sweeps ----------------------------------------------------------------
+// tio.HistogramStandardization needs 13 percentiles of every volume to train and 11 to apply.  The select above counts 4 prefixes per sweep;
+// this one gives every one of the 2 Q <= 32 wanted ranks a slot of its own, so a pass is ONE sweep whatever the ranks fall under: four passes
+// of 8-bit digits, 32 slots x 256 bins = 32 KB of LDS.  Ranks, keys, the contention trick and the cutoff arithmetic are those of the select
+// above, so the results are its results bit for bit.
+constexpr int kLmRanks = 2 * GVK_LANDMARKS_MAX;                  // rank slots: (a, b) of every percentile
+constexpr int kLmBins = 256;                                     // bins of one 8-bit digit
+constexpr int kLmPasses = 4;
+constexpr int kLmSelWords = 128;                                 // per-sample select state, uint32: see landmark_init_kernel
+constexpr int kHsKnots = GVK_HISTSTD_KNOTS;                      // 11 knots, 10 segments
+constexpr int kHsParams = GVK_HISTSTD_PARAMS;                    // per-sample doubles: knots [0..10], slopes [11..20], intercepts [21..30]
+static_assert(kLmSelWords + kLmPasses * kLmRanks * kLmBins == GVK_LANDMARKS_WS_WORDS, "workspace size");
+
+struct LandmarkFractions { double q[GVK_LANDMARKS_MAX]; };       // a kernel argument: the fractions never touch device memory
+struct HistogramTargets { double m[kHsKnots]; };
+
+// Per-sample select state sel [B][128] uint32:
+//   [0] nslots = distinct key prefixes the wanted ranks fall under (0: empty mask), [1..32] the prefixes (the key bits decided so far, right
+//   aligned), [33..64] the slot of each of the 32 ranks, [65..96] each rank's position among the keys of its slot.
+// One workgroup per sample writes the first state and zeroes the sample's histograms hist [B][4 passes][32 slots][256].  Ranks beyond 2 Q
+// repeat rank 0, so they never add a prefix.
+__global__ __launch_bounds__(256) void landmark_init_kernel(const double* __restrict__ stats, unsigned* __restrict__ sel, unsigned* __restrict__ hist, int Q,
+                                                            LandmarkFractions f) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  unsigned* h = hist + (size_t)b * kLmPasses * kLmRanks * kLmBins;
+  for (int i = tid; i < kLmPasses * kLmRanks * kLmBins; i += 256) h[i] = 0u;
+  if (tid >= kLmSelWords) return;
+  unsigned* s = sel + (size_t)b * kLmSelWords;
+  const long long n = (long long)stats[(size_t)b * kStatWords + 4];
+  unsigned word = 0u;
+  if (n > 0) {
+    if (tid == 0) word = 1u;
+    if (tid >= 65 && tid < 65 + kLmRanks) {
+      const int r = tid - 65;
+      const bool mine = (r >> 1) < Q;
+      double qf = f.q[0];
+#pragma unroll
+      for (int j = 1; j < GVK_LANDMARKS_MAX; ++j) qf = (mine && (r >> 1) == j) ? f.q[j] : qf;
+      long long ia, ib;
+      double g;
+      order_ranks(n, qf, ia, ib, g);
+      word = (unsigned)((r & 1) && mine ? ib : ia);
+    }
+  }
+  s[tid] = word;
+}
+
+// NS = the slots this instantiation compares against (unused ones hold a prefix no key has)
+template <int NS>
+__device__ __forceinline__ void landmark_sweep(unsigned* h, const unsigned* __restrict__ s, int ns, const float* __restrict__ xb, long long V, int slab,
+                                               int nslabs, float t, int pass) {
+  unsigned pre[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) pre[j] = j < ns ? s[1 + j] : 0xffffffffu;   // prefixes have at most 24 bits
+  const int dshift = 24 - 8 * pass;
+  int cand = -2;
+  stream_slab(xb, V, slab, nslabs, [&](float v, bool ok) {
+    int idx = -1;
+    if (ok && v > t) {
+      const unsigned key = order_key(v);
+      const unsigned hp = pass == 0 ? 0u : key >> (dshift + 8);
+      const int d = (int)((key >> dshift) & 255u);
+#pragma unroll
+      for (int j = 0; j < NS; ++j)
+        if (hp == pre[j]) idx = j * kLmBins + d;
+    }
+    wave_count(h, idx, cand);
+  });
+}
+
+// Pass `pass`: every workgroup counts, for its slab, the current digit of the masked keys whose higher bits equal one of the sample's
+// prefixes, in ONE sweep, and merges its non-zero bins into the sample's histogram with integer atomics.
+__global__ __launch_bounds__(256) void landmark_hist_kernel(const float* __restrict__ x, const double* __restrict__ stats, const unsigned* __restrict__ sel,
+                                                            unsigned* __restrict__ hist, long long V, int nslabs, int pass) {
+  __shared__ unsigned h[kLmRanks * kLmBins];
+  const int b = blockIdx.y, slab = blockIdx.x, tid = threadIdx.x;
+  const unsigned* s = sel + (size_t)b * kLmSelWords;
+  const int ns = min((int)s[0], kLmRanks);
+  if (ns == 0) return;                                           // empty mask: nothing to count (uniform over the workgroup)
+  const float t = (float)stats[(size_t)b * kStatWords + 3];
+  const float* xb = x + (size_t)b * V;
+  unsigned* gh = hist + ((size_t)b * kLmPasses + pass) * kLmRanks * kLmBins;
+  for (int i = tid; i < ns * kLmBins; i += 256) h[i] = 0u;
+  __syncthreads();
+  if (ns <= 1) landmark_sweep<1>(h, s, ns, xb, V, slab, nslabs, t, pass);
+  else if (ns <= 8) landmark_sweep<8>(h, s, ns, xb, V, slab, nslabs, t, pass);
+  else if (ns <= 16) landmark_sweep<16>(h, s, ns, xb, V, slab, nslabs, t, pass);
+  else landmark_sweep<kLmRanks>(h, s, ns, xb, V, slab, nslabs, t, pass);
+  __syncthreads();
+  for (int i = tid; i < ns * kLmBins; i += 256) {
+    const unsigned c = h[i];
+    if (c != 0u) atomicAdd(&gh[i], c);
+  }
+}
+
+// Between passes, one workgroup per sample.  Each wave takes every fourth slot: a lane holds 4 bins, a shuffle scan gives their offsets, and
+// the lane whose bins hold a rank of that slot notes the bin and the rank's position in it.  Then lanes 0..31 build the new state: rank r's
+// new prefix, the first rank with the same prefix, and from the ballot of those firsts the compacted slot numbers.  After the last pass the
+// prefixes are whole keys: pairs and cutoffs as in order_select_kernel.
+__global__ __launch_bounds__(256) void landmark_select_kernel(const double* __restrict__ stats, unsigned* sel, const unsigned* __restrict__ hist,
+                                                              float* __restrict__ pairs, float* __restrict__ cutoffs, int Q, LandmarkFractions f, int pass) {
+  __shared__ unsigned rbin[kLmRanks], rpos[kLmRanks], skey[kLmRanks];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned* s = sel + (size_t)b * kLmSelWords;
+  const int nslots = min((int)s[0], kLmRanks);
+  if (tid < kLmRanks) { rbin[tid] = 0u; rpos[tid] = 0u; skey[tid] = 0u; }
+  __syncthreads();
+  for (int slot = wave; slot < nslots; slot += 4) {
+    const unsigned* gh = hist + (((size_t)b * kLmPasses + pass) * kLmRanks + slot) * kLmBins + lane * 4;
+    unsigned c[4], tot = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { c[j] = gh[j]; tot += c[j]; }
+    unsigned inc = tot;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned up = __shfl_up(inc, off, 64);
+      if (lane >= off) inc += up;
+    }
+    const unsigned excl = inc - tot;
+    for (int r = 0; r < kLmRanks; ++r) {
+      const unsigned rk = s[65 + r];
+      if ((int)s[33 + r] == slot && rk >= excl && rk - excl < tot) {
+        unsigned before = excl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (rk - before < c[j]) { rbin[r] = (unsigned)(lane * 4 + j); rpos[r] = rk - before; break; }
+          before += c[j];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const bool act = tid < kLmRanks && nslots > 0;
+  unsigned key = 0u;
+  if (act) {
+    const int old = min((int)s[33 + tid], kLmRanks - 1);
+    key = (s[1 + old] << 8) | rbin[tid];
+    skey[tid] = key;
+  }
+  __syncthreads();                                               // every read of the old state lies before this barrier
+  if (tid >= 64) return;
+  int first = tid;
+  if (act)
+    for (int j = tid - 1; j >= 0; --j)
+      if (skey[j] == key) first = j;
+  const unsigned long long firsts = __ballot(act && first == tid);
+  if (act) {
+    const int slot = __popcll(firsts & ((1ull << first) - 1ull));
+    s[33 + tid] = (unsigned)slot;
+    s[65 + tid] = rpos[tid];
+    if (first == tid) s[1 + slot] = key;
+    if (tid == 0) s[0] = (unsigned)__popcll(firsts);
+  }
+  if (pass != kLmPasses - 1 || tid >= Q) return;
+  const long long n = (long long)stats[(size_t)b * kStatWords + 4];
+  float fa = 0.f, fb = 0.f, fc = 0.f;                            // empty mask: zeros, and status 1 from gvk_histogram_standardize
+  if (nslots > 0 && n > 0) {
+    fa = order_value(skey[2 * tid]);
+    fb = order_value(skey[2 * tid + 1]);
+    double qf = f.q[0];
+#pragma unroll
+    for (int j = 1; j < GVK_LANDMARKS_MAX; ++j) qf = tid == j ? f.q[j] : qf;
+    long long ia, ib;
+    double g;
+    order_ranks(n, qf, ia, ib, g);
+    const double a = (double)fa, bb = (double)fb, diff = __dsub_rn(bb, a);
+    const double c = g < 0.5 ? __dadd_rn(a, __dmul_rn(diff, g)) : __dsub_rn(bb, __dmul_rn(diff, __dsub_rn(1.0, g)));
+    fc = (float)c;
+  }
+  pairs[((size_t)b * Q + tid) * 2] = fa;
+  pairs[((size_t)b * Q + tid) * 2 + 1] = fb;
+  cutoffs[(size_t)b * Q + tid] = fc;
+}
+
+// ---- histogram standardisation: parameters and apply -----------------------------------------------------------------------------------
+// torchio's _normalize on float64: d_j = k_{j+1} - k_j, taken as inf below epsilon (slope 0); slope_j = (m_{j+1} - m_j) / d_j;
+// icpt_j = m_j - slope_j k_j.  params [B][32] doubles = knots [0..10] (the float32 cutoffs), slopes [11..20], intercepts [21..30].
+// status [B]: 0 standardised, 1 empty mask -- such a sample is copied bit for bit.
+__global__ void histstd_params_kernel(const double* __restrict__ stats, const float* __restrict__ cutoffs, HistogramTargets tg, double epsilon,
+                                      double* __restrict__ params, int* __restrict__ status, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double* p = params + (size_t)b * kHsParams;
+  const float* c = cutoffs + (size_t)b * kHsKnots;
+  for (int i = 0; i < kHsParams; ++i) p[i] = 0.0;
+  for (int j = 0; j < kHsKnots; ++j) p[j] = (double)c[j];
+  for (int j = 0; j + 1 < kHsKnots; ++j) {
+    const double k0 = (double)c[j];
+    double d = __dsub_rn((double)c[j + 1], k0);
+    if (d < epsilon) d = (double)INFINITY;
+    const double slope = __ddiv_rn(__dsub_rn(tg.m[j + 1], tg.m[j]), d);
+    p[kHsKnots + j] = slope;
+    p[2 * kHsKnots - 1 + j] = __dsub_rn(tg.m[j], __dmul_rn(slope, k0));
+  }
+  status[b] = (long long)stats[(size_t)b * kStatWords + 4] <= 0 ? 1 : 0;
+}
+
+// The segment of x is the number of interior knots k_1..k_9 that are <= x (np.digitize, right=False); the knots ascend, so the last
+// knot that is <= x names it: nine float32 compares, each selecting that segment's (slope, intercept).  y = float32(slope (double)x + icpt),
+// the product and the sum rounded once each.
+__device__ __forceinline__ float histstd_one(float v, const float (&k)[kHsKnots - 2], const double (&sl)[kHsKnots - 1], const double (&ic)[kHsKnots - 1]) {
+  double s = sl[0], c = ic[0];
+#pragma unroll
+  for (int j = 0; j < kHsKnots - 2; ++j) {
+    const bool at = v >= k[j];
+    s = at ? sl[j + 1] : s;
+    c = at ? ic[j + 1] : c;
+  }
+  return (float)__dadd_rn(__dmul_rn(s, (double)v), c);
+}
+
+// head / body / tail as normalize_apply_kernel: a sample may start off the 16-byte grid
+__global__ __launch_bounds__(256) void histstd_apply_kernel(const float* __restrict__ x, float* __restrict__ y, const double* __restrict__ params,
+                                                            const int* __restrict__ status, long long V) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const double* p = params + (size_t)b * kHsParams;
+  const bool live = status[b] == 0;
+  float k[kHsKnots - 2];
+  double sl[kHsKnots - 1], ic[kHsKnots - 1];
+#pragma unroll
+  for (int j = 0; j < kHsKnots - 2; ++j) k[j] = (float)p[1 + j];
+#pragma unroll
+  for (int j = 0; j < kHsKnots - 1; ++j) { sl[j] = p[kHsKnots + j]; ic[j] = p[2 * kHsKnots - 1 + j]; }
+  const float* xb = x + (size_t)b * V;
+  float* yb = y + (size_t)b * V;
+  long long head = (long long)((4 - (int)(((uintptr_t)xb >> 2) & 3)) & 3);   // x and y are 16-byte aligned: yb has the same head
+  head = head < V ? head : V;
+  const long long n4 = (V - head) >> 2;
+  const f32x4* x4 = (const f32x4*)(xb + head);
+  f32x4* y4 = (f32x4*)(yb + head);
+  for (long long i = (long long)blockIdx.x * 256 + tid; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 v = x4[i];
+    if (live) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = histstd_one(v[e], k, sl, ic);
+    }
+    y4[i] = v;
+  }
+  if (blockIdx.x == 0) {
+    const long long t0 = head + (n4 << 2);
+    long long i = -1;
+    if (tid < head) i = tid;
+    else if (tid >= 64 && t0 + (tid - 64) < V) i = t0 + (tid - 64);
+    if (i >= 0) {
+      const float v = xb[i];
+      yb[i] = live ? histstd_one(v, k, sl, ic) : v;
+    }
+  }
+}
+
 }  // namespace gvk
 
 extern "C" int gvk_volume_stats(const float* x, double* partials, double* stats, int64_t* count, int mask_mode, float threshold, int want_std, int B,
@@ -483,4 +736,45 @@ extern "C" int gvk_normalize_intensity(const float* x, float* y, const double* s
   const int gx = (int)std::min<int64_t>((V / 4 + 255) / 256 + 1, 512);
   GVK_LAUNCH(normalize_apply_kernel, dim3(gx, B), dim3(256), 0, st, x, y, (const double*)params, (const int*)status, (long long)V, mode);
   return check_launch("normalize_intensity");
+}
+
+extern "C" int gvk_volume_landmarks(const float* x, const double* stats, void* workspace, float* pairs, float* cutoffs, int Q, const double* fractions_host,
+                                    int B, int64_t V, void* stream) {
+  using namespace gvk;
+  GVK_REQUIRE(x && stats && workspace && pairs && cutoffs && fractions_host, "gvk_volume_landmarks: null pointer");
+  GVK_REQUIRE(B > 0 && B <= 65535 && V > 0 && V < ((int64_t)1 << 31), "gvk_volume_landmarks: 1 <= B <= 65535 and 1 <= V < 2^31");
+  GVK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)workspace & 3) == 0, "gvk_volume_landmarks: x must be 16-byte aligned");
+  GVK_REQUIRE(Q >= 1 && Q <= GVK_LANDMARKS_MAX, "gvk_volume_landmarks: 1..%d percentiles per call", (int)GVK_LANDMARKS_MAX);
+  LandmarkFractions f;
+  for (int q = 0; q < GVK_LANDMARKS_MAX; ++q) f.q[q] = q < Q ? fractions_host[q] : 0.0;
+  for (int q = 0; q < Q; ++q) GVK_REQUIRE(f.q[q] >= 0.0 && f.q[q] <= 1.0, "gvk_volume_landmarks: percentile fractions lie in [0, 1]");
+  const int S = normalize_slabs(V);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* sel = (unsigned*)workspace;
+  unsigned* hist = sel + (size_t)B * kLmSelWords;
+  GVK_LAUNCH(landmark_init_kernel, dim3(B), dim3(256), 0, st, stats, sel, hist, Q, f);
+  for (int pass = 0; pass < kLmPasses; ++pass) {
+    GVK_LAUNCH(landmark_hist_kernel, dim3(S, B), dim3(256), 0, st, x, stats, (const unsigned*)sel, hist, (long long)V, S, pass);
+    GVK_LAUNCH(landmark_select_kernel, dim3(B), dim3(256), 0, st, stats, sel, (const unsigned*)hist, pairs, cutoffs, Q, f, pass);
+  }
+  return check_launch("volume_landmarks");
+}
+
+extern "C" int gvk_histogram_standardize(const float* x, float* y, const double* stats, const float* cutoffs, const double* targets_host, double epsilon,
+                                         double* params, int32_t* status, int B, int64_t V, void* stream) {
+  using namespace gvk;
+  GVK_REQUIRE(x && y && stats && cutoffs && targets_host && params && status, "gvk_histogram_standardize: null pointer");
+  GVK_REQUIRE(B > 0 && B <= 65535 && V > 0 && V < ((int64_t)1 << 31), "gvk_histogram_standardize: 1 <= B <= 65535 and 1 <= V < 2^31");
+  GVK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "gvk_histogram_standardize: x and y must be 16-byte aligned");
+  GVK_REQUIRE(epsilon >= 0.0, "gvk_histogram_standardize: epsilon is not negative");
+  HistogramTargets tg;
+  for (int j = 0; j < kHsKnots; ++j) {
+    tg.m[j] = targets_host[j];
+    GVK_REQUIRE(std::isfinite(tg.m[j]), "gvk_histogram_standardize: the targets are finite");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GVK_LAUNCH(histstd_params_kernel, dim3((B + 63) / 64), dim3(64), 0, st, stats, cutoffs, tg, epsilon, params, (int*)status, B);
+  const int gx = (int)std::min<int64_t>((V / 4 + 255) / 256 + 1, 512);
+  GVK_LAUNCH(histstd_apply_kernel, dim3(gx, B), dim3(256), 0, st, x, y, (const double*)params, (const int*)status, (long long)V);
+  return check_launch("histogram_standardize");
 }

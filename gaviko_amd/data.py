@@ -35,11 +35,14 @@ distributions, not the same voxels for the same seed.  Parity vs torchio / Simpl
 restatement (`tests/elastic_ref.py`) that is itself checked against scipy.ndimage.map_coordinates.
 
 The last step of every batch is a normaliser.  The reference's is the plain RescaleIntensity((0, 1)) (two kernels of `csrc/augment.hip`,
-kept bit for bit as the default); torchio's two MRI normalisers, RescaleIntensity with percentiles and a mask and ZNormalization
-(`normalization='percentile'` / `'znorm'`), run on exact per-volume order statistics and float64 moments computed on the device without a
+kept bit for bit as the default); torchio's three MRI normalisers -- RescaleIntensity with percentiles and a mask, ZNormalization
+(`normalization='percentile'` / `'znorm'`) and HistogramStandardization (an instance, alone or in a list before one of the strings) -- run on exact per-volume order statistics and float64 moments computed on the device without a
 sort or a host read (`csrc/normalize.hip`).  Empty masks and zero ranges become a per-sample status word (`DeviceCompose.last_norm_status`)
 where torchio warns or raises; cutoffs are rounded to float32 before the clip.  Parity vs torchio is UNPINNED; the kernels are pinned against
-np.sort / np.percentile / math.fsum (`tests/normalize_ref.py`).
+np.sort / np.percentile / math.fsum (`tests/normalize_ref.py`).  HistogramStandardization maps 11 landmarks (percentiles of the masked voxels, found
+in four sweeps whatever their number: `ops.volume_landmarks`) onto landmarks that `HistogramStandardization.train` learns on the device from the
+training batches; it keeps torchio's arithmetic (`tests/histstd_ref.py`), with float32 landmarks, the array-axis mask rules only, and the map
+evaluated in float64 and rounded once; an empty mask is a status word (`DeviceCompose.last_hist_status`).
 
 The rest of torchio's MRI augmentation family (`train_transforms(intensity=True, artifacts=True)`, `csrc/kspace.hip`) joins the intensity
 group: RandomGhosting reduces the way RandomMotion did, to a real circular convolution along the one axis its k-space mask depends on (any of
@@ -379,6 +382,113 @@ class ZNormalization:
         return y, ops.normalize_intensity(x, y, stats, ops.NORMALIZE_ZNORM)
 
 
+# ---- tio.HistogramStandardization (Nyul & Udupa): torchio's arithmetic on this package's order statistics -------------------------------
+DEFAULT_CUTOFF = (0.01, 0.99)
+LANDMARK_APPLY_INDEX = (0, 1, 2, 4, 5, 6, 7, 8, 10, 11, 12)      # of the 13 trained percentiles, the 11 the map uses (the quartiles 25 / 75 are left out)
+
+
+def landmark_percentiles(cutoff=DEFAULT_CUTOFF) -> np.ndarray:
+    """torchio's _standardize_cutoff and _get_percentiles: the sorted set of the two cutoffs (in percent, the low one clamped to [0, 9], the
+    high one to [91, 100]), the quartiles and the deciles -- always 13 distinct values, float64."""
+    if len(cutoff) != 2:
+        raise ValueError(f"HistogramStandardization: cutoff is (low, high) as fractions, not {cutoff!r}")
+    c = np.asarray([float(cutoff[0]), float(cutoff[1])], dtype=np.float64)
+    c[0] = max(0.0, c[0])
+    c[1] = min(1.0, c[1])
+    c[0] = min(c[0], 0.09)
+    c[1] = max(c[1], 0.91)
+    every = (100 * c).tolist() + np.arange(25, 100, 25).tolist() + np.arange(10, 100, 10).tolist()
+    return np.array(sorted(set(every)), dtype=np.float64)
+
+
+def average_mapping(database) -> np.ndarray:
+    """torchio's _get_average_mapping on a database [N][13] of per-volume landmarks, float64: every volume's (first, last) landmark is
+    taken to (0, 100), and the 13 trained landmarks are the mean of the volumes' landmarks on that scale."""
+    database = np.asarray(database, dtype=np.float64)
+    if database.ndim != 2 or database.shape[0] < 1:
+        raise ValueError(f"average_mapping: a database [N >= 1][landmarks], not shape {database.shape}")
+    pc1, pc2 = database[:, 0], database[:, -1]
+    s1, s2 = 0.0, 100.0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        slopes = np.nan_to_num((s2 - s1) / (pc2 - pc1))
+        intercepts = np.mean(s1 - slopes * pc1)
+        return slopes.dot(database) / len(database) + intercepts
+
+
+def landmark_database(batches, masking_method=None, cutoff=None):
+    """The training database of `HistogramStandardization.train`: (float64 [N][13], skipped).  Per batch one `ops.volume_stats` and one
+    `ops.volume_landmarks` launch at 13 percentiles; the rows stay on the device and come to the host in one copy at the end.  A volume whose
+    mask is empty has no landmarks: it is left out and counted in `skipped`."""
+    rule = _masking_method(masking_method, "HistogramStandardization.train")
+    q = landmark_percentiles(cutoff or DEFAULT_CUTOFF)
+    rows = []
+    for batch in batches:
+        x = batch[0] if isinstance(batch, (tuple, list)) else batch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("HistogramStandardization.train: the batches are device tensors [B, 1, D, H, W] or (tensor, labels) pairs "
+                               "(there is no CPU path)")
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        stats, count = ops.volume_stats(x, rule, want_std=False)
+        _, cutoffs = ops.volume_landmarks(x, stats, q)
+        rows.append(torch.cat([cutoffs.double(), count.double().unsqueeze(1)], dim=1))          # float32 and counts below 2^31: exact
+    if not rows:
+        raise ValueError("HistogramStandardization.train: no batches")
+    table = torch.cat(rows).cpu().numpy()                                                       # the one copy to the host
+    keep = table[:, -1] > 0
+    return np.ascontiguousarray(table[keep, :-1]), int((~keep).sum())
+
+
+class HistogramStandardization:
+    """tio.HistogramStandardization(landmarks, masking_method): a piecewise-linear map that takes the volume's own histogram landmarks (the
+    percentiles `landmark_percentiles(cutoff)` of its masked voxels, 11 of the 13) onto landmarks trained once on the training set
+    (`HistogramStandardization.train`).  `landmarks` is the 13 trained values or a path np.load reads.  The mask only selects the voxels the
+    percentiles come from; every voxel is mapped.  torchio's recipe follows it with ZNormalization(masking_method=ZNormalization.mean).
+    The landmarks are the float32 cutoffs of `ops.volume_order_stats`; the map is evaluated in float64 and rounded to float32 once."""
+
+    last_train_skipped = 0                                        # volumes the last `train` left out because their mask was empty
+
+    def __init__(self, landmarks, masking_method=None, cutoff=DEFAULT_CUTOFF, epsilon: float = 1e-5):
+        if isinstance(landmarks, (str, os.PathLike)):
+            landmarks = np.load(landmarks)
+        m = np.asarray(landmarks, dtype=np.float64)
+        self.percentiles = landmark_percentiles(cutoff or DEFAULT_CUTOFF)
+        if m.shape != (len(self.percentiles),) or not np.all(np.isfinite(m)) or np.any(np.diff(m) < 0):
+            raise ValueError(f"HistogramStandardization: landmarks are {len(self.percentiles)} finite values that do not decrease, got {landmarks!r}")
+        if not float(epsilon) >= 0.0:
+            raise ValueError(f"HistogramStandardization: epsilon is not negative, got {epsilon!r}")
+        self.landmarks = m
+        self.cutoff = tuple(self.percentiles[[0, -1]] / 100)
+        self.epsilon = float(epsilon)
+        self.masking_method = _masking_method(masking_method, "HistogramStandardization")
+
+    def apply(self, x: torch.Tensor, partials: torch.Tensor = None):
+        """(y, status) for the batch x, as `RescaleIntensity.apply`; `partials` is not used.  status int32 [B]: 0 standardised, 1 empty mask
+        (the sample comes back unchanged)."""
+        idx = list(LANDMARK_APPLY_INDEX)
+        stats, _ = ops.volume_stats(x, self.masking_method, want_std=False)
+        _, cutoffs = ops.volume_landmarks(x, stats, self.percentiles[idx])
+        y = torch.empty_like(x)
+        return y, ops.histogram_standardize(x, y, stats, cutoffs, self.landmarks[idx], self.epsilon)
+
+    @classmethod
+    def train(cls, batches, masking_method=None, cutoff=None, output_path=None) -> np.ndarray:
+        """torchio's HistogramStandardization.train on the device: `batches` is any iterable of device tensors [B, 1, D, H, W] or
+        (tensor, labels) pairs (a loader composed with `.to(device)` or `Conform`).  Returns the 13 trained landmarks, float64, and saves
+        them as .npy when output_path is given.  Volumes with an empty mask are left out; their number is `cls.last_train_skipped`."""
+        database, skipped = landmark_database(batches, masking_method, cutoff)
+        cls.last_train_skipped = skipped
+        if skipped:
+            import warnings
+            warnings.warn(f"HistogramStandardization.train: {skipped} volume(s) with an empty mask were left out of the landmark database")
+        if len(database) == 0:
+            raise ValueError("HistogramStandardization.train: every volume had an empty mask")
+        landmarks = average_mapping(database)
+        if output_path is not None:
+            np.save(output_path, landmarks)
+        return landmarks
+
+
 # ---- intensity transforms: train.py:43-48 --------------------------------------------------------------------------------------------
 # Each `sample(rng)` returns None (not applied) or (class name, params) and draws, in this order: one uniform for p, then the
 # parameters as listed in its docstring.  Parity with torchio itself is unpinned (module docstring).
@@ -564,7 +674,8 @@ INTENSITY_TRANSFORMS = (RandomNoise, RandomBiasField, RandomBlur, RandomMotion, 
 _BUILT = ("RandomAffine (at most one), RandomFlip, RandomNoise, RandomBiasField, RandomBlur, RandomMotion, OneOf of the last four, "
           "RescaleIntensity (at most one); RandomElasticDeformation (at most one), OneOf of RandomAffine and RandomElasticDeformation in place of "
           "the two; ZNormalization in place of RescaleIntensity (at most one normaliser, it runs last), RescaleIntensity percentiles and "
-          "masking_method None / 'mean' / a threshold; RandomGhosting, RandomSpike, RandomGamma, RandomAnisotropy, singly or in the intensity OneOf")
+          "masking_method None / 'mean' / a threshold; RandomGhosting, RandomSpike, RandomGamma, RandomAnisotropy, singly or in the intensity OneOf; "
+          "HistogramStandardization (at most one; it runs before the one RescaleIntensity / ZNormalization and may be listed with it)")
 
 
 class OneOf:
@@ -886,7 +997,8 @@ def apply_intensity(x: torch.Tensor, draws) -> torch.Tensor:
 class DeviceCompose:
     """The transforms of train.py:38-62 on a batch [B, 1, D, H, W] (or [B, D, H, W]) already on the GPU.  Affine and flips are merged
     into one resampling pass (affine first, flips on its output), the intensity transforms (singly or inside OneOf) follow in listed
-    order, the one normaliser (RescaleIntensity or ZNormalization) runs last, as in the reference's Compose.  RandomElasticDeformation is a resampling pass of its own BEFORE the
+    order, the one normaliser (RescaleIntensity or ZNormalization) runs last, as in the reference's Compose, and a HistogramStandardization
+    runs just before it wherever it is listed (it draws nothing; its status words are `last_hist_status`).  RandomElasticDeformation is a resampling pass of its own BEFORE the
     affine/flip pass wherever it is listed: torchio would apply the spatial transforms in listed order, here elastic always runs first
     (a sample that draws both is interpolated twice, as in torchio).  A OneOf of RandomAffine / RandomElasticDeformation members may stand
     in place of the single affine and/or elastic: each sample then gets at most one of them.  Per sample the random draws are: elastic,
@@ -900,12 +1012,13 @@ class DeviceCompose:
         self.flips = [t for t in transforms if isinstance(t, RandomFlip)]
         self.rescale = [t for t in transforms if isinstance(t, RescaleIntensity)]
         self.znorm = [t for t in transforms if isinstance(t, ZNormalization)]
+        self.hist = [t for t in transforms if isinstance(t, HistogramStandardization)]
         self.intensity = [t for t in transforms if isinstance(t, INTENSITY_TRANSFORMS) or (isinstance(t, OneOf) and not t.spatial)]
         elastic = self.elastic + [t for one in self.spatial for t in one.transforms if isinstance(t, RandomElasticDeformation)]
         if len(self.affine) > 1 or len(self.rescale) + len(self.znorm) > 1 or len(elastic) > 1 or len(self.spatial) > 1 or \
-                (self.spatial and (self.affine or self.elastic)) or \
+                (self.spatial and (self.affine or self.elastic)) or len(self.hist) > 1 or \
                 len(self.affine) + len(self.elastic) + len(self.spatial) + len(self.flips) + len(self.rescale) + len(self.znorm) + \
-                len(self.intensity) != len(transforms):
+                len(self.hist) + len(self.intensity) != len(transforms):
             raise NotImplementedError(f"DeviceCompose: {_BUILT}; anything else is not built")
         self._elastic = elastic[0] if elastic else None                   # the one elastic transform, listed singly or inside the spatial OneOf
         self.rng = np.random.default_rng(seed)
@@ -917,6 +1030,8 @@ class DeviceCompose:
         # int32 [B] on the device after a call that ran a percentile / masked rescale or a z-normalisation: 0 normalised, 1 empty mask,
         # 2 zero range or zero std (such samples come back unchanged).  Never synchronised on here; None after any other call.
         self.last_norm_status = None
+        # int32 [B] on the device after a call that ran a HistogramStandardization: 0 standardised, 1 empty mask (the sample went on unchanged)
+        self.last_hist_status = None
 
     def sample(self, B: int, shape):
         mats = np.tile(np.eye(3, 4, dtype=np.float32), (B, 1, 1))
@@ -967,8 +1082,10 @@ class DeviceCompose:
                 x = out
             for s in range(len(self.intensity)):
                 x = apply_intensity(x, [d if len(self.intensity) == 1 else (d[s] if d else None) for d in self.last_intensity])
-        self.last_norm_status = None
-        for t in self.rescale + self.znorm:                               # the one normaliser, if any
+        self.last_norm_status = self.last_hist_status = None
+        for t in self.hist:                                               # histogram standardisation, then ...
+            x, self.last_hist_status = t.apply(x, part)
+        for t in self.rescale + self.znorm:                               # ... the one normaliser, if any
             x, self.last_norm_status = t.apply(x, part)
         return x
 
@@ -1287,20 +1404,40 @@ class BatchMix:
         return out, target
 
 
-def normalizer(normalization: str = "minmax"):
+def normalizer(normalization="minmax"):
     """The batch's last step: 'minmax' = RescaleIntensity((0, 1)) as in train.py:50,58; 'percentile' = torchio's MRI recipe
-    RescaleIntensity((0, 1), percentiles=(0.5, 99.5)); 'znorm' = ZNormalization(masking_method=ZNormalization.mean)."""
+    RescaleIntensity((0, 1), percentiles=(0.5, 99.5)); 'znorm' = ZNormalization(masking_method=ZNormalization.mean).  A
+    `HistogramStandardization` instance stands for itself, and a list [HistogramStandardization(...), one of the three strings] gives the list
+    of the two transforms (torchio's recipe is the instance followed by 'znorm').  A dict {"histogram": {landmarks, masking_method, cutoff,
+    epsilon}, "then": string} is the configuration-file form of that list; `then` is optional."""
+    if isinstance(normalization, HistogramStandardization):
+        return normalization
+    if isinstance(normalization, dict):
+        if "histogram" not in normalization or set(normalization) - {"histogram", "then"}:
+            raise ValueError(f"normalization as a dict is {{'histogram': {{...}}, 'then': 'znorm' | 'percentile' | 'minmax'}}, not {normalization!r}")
+        first = HistogramStandardization(**normalization["histogram"])
+        return [first] + ([normalizer(str(normalization["then"]))] if normalization.get("then") is not None else [])
+    if isinstance(normalization, (list, tuple)):
+        if len(normalization) != 2 or not isinstance(normalization[0], HistogramStandardization) or not isinstance(normalization[1], str):
+            raise ValueError(f"normalization as a list is [HistogramStandardization(...), 'znorm' | 'percentile' | 'minmax'], not {normalization!r}")
+        return [normalization[0], normalizer(normalization[1])]
     if normalization == "minmax":
         return RescaleIntensity((0, 1))
     if normalization == "percentile":
         return RescaleIntensity((0, 1), percentiles=(0.5, 99.5))
     if normalization == "znorm":
         return ZNormalization(masking_method=ZNormalization.mean)
-    raise ValueError(f"normalization is 'minmax', 'percentile' or 'znorm', not {normalization!r}")
+    raise ValueError(f"normalization is 'minmax', 'percentile' or 'znorm' (or a HistogramStandardization, alone or in a list before one of "
+                     f"them), not {normalization!r}")
+
+
+def _normalizers(normalization) -> list:
+    n = normalizer(normalization)
+    return list(n) if isinstance(n, list) else [n]
 
 
 def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion: bool = False, elastic: bool = False,
-                     normalization: str = "minmax", artifacts: bool = False) -> DeviceCompose:
+                     normalization="minmax", artifacts: bool = False) -> DeviceCompose:
     """train.py:38-52.  The shipped script declares an intensity_augment dict (43-48) and leaves its `tio.OneOf(intensity_augment, p=0.75)`
     line (51) commented out, so the default here has no intensity transform.  intensity=True switches that line on, on the device, with
     the three members this package had first (RandomMotion's 0.25 spread over them); motion=True as well makes it the reference's dict
@@ -1322,12 +1459,12 @@ def train_transforms(seed: Optional[int] = None, intensity: bool = False, motion
     if artifacts:
         group = {t: 1 for t in list(group) + [RandomGhosting(), RandomSpike(), RandomGamma(), RandomAnisotropy()]}
     one_of = [OneOf(group, p=0.75)] if intensity else []
-    return DeviceCompose(spatial + one_of + [normalizer(normalization)], seed)
+    return DeviceCompose(spatial + one_of + _normalizers(normalization), seed)
 
 
-def eval_transforms(normalization: str = "minmax") -> DeviceCompose:
+def eval_transforms(normalization="minmax") -> DeviceCompose:
     """train.py:54-60: val and test."""
-    return DeviceCompose([normalizer(normalization)])
+    return DeviceCompose(_normalizers(normalization))
 
 
 class DataPreprocessor:
@@ -1336,7 +1473,8 @@ class DataPreprocessor:
     (default False) adds the intensity OneOf of `train_transforms(intensity=True)`, config['data']['motion_augment'] (default False)
     RandomMotion to it (`motion=True`), config['data']['elastic_augment'] (default False) puts the affine / elastic OneOf of
     `train_transforms(elastic=True)` in place of the affine, config['data']['normalization'] (default 'minmax'; 'percentile', 'znorm') picks
-    the last step of all three splits (`normalizer`), config['data']['artifact_augment'] (default False) adds RandomGhosting, RandomSpike,
+    the last step of all three splits (`normalizer`; a dict {"histogram": {"landmarks": path, "masking_method": ..., "cutoff": ...}, "then":
+    "znorm"} puts a `HistogramStandardization` before it, `then` is optional and without it nothing follows), config['data']['artifact_augment'] (default False) adds RandomGhosting, RandomSpike,
     RandomGamma and RandomAnisotropy to the intensity OneOf (`artifacts=True`; it needs intensity_augment).  config['data']['batch_mix'] (absent by
     default: `batch_mix` is None) is a dict of `BatchMix` arguments and builds the `batch_mix` attribute, to call on the training batch and its
     labels after `train_transforms`.  config['data']['conform'] (absent by default: `conform` is None and nothing changes) is a dict with

@@ -201,6 +201,8 @@ SIGNATURES = {
     "gvk_volume_stats": [_P, _P, _P, _P, _I, _F, _I, _I, _L, _P],
     "gvk_volume_order_stats": [_P, _P, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _I, _L, _P],
     "gvk_normalize_intensity": [_P, _P, _P, _P, _I, _P, _P, _I, _F, _F, _I, _L, _P],
+    "gvk_volume_landmarks": [_P, _P, _P, _P, _P, _I, _P, _I, _L, _P],
+    "gvk_histogram_standardize": [_P, _P, _P, _P, _P, C.c_double, _P, _P, _I, _L, _P],
     "gvk_axis_circular_conv": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_gamma_spike": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gvk_axis_gather2": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -1302,6 +1302,56 @@ def normalize_intensity(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, m
     return status
 
 
+LANDMARKS_MAX, LANDMARKS_WS_WORDS = 16, 128 + 4 * 32 * 256                # GVK_LANDMARKS_MAX, GVK_LANDMARKS_WS_WORDS
+HISTSTD_KNOTS, HISTSTD_PARAMS = 11, 32                                    # GVK_HISTSTD_KNOTS, GVK_HISTSTD_PARAMS
+
+
+def volume_landmarks(x: torch.Tensor, stats: torch.Tensor, percentiles, pairs: torch.Tensor = None, cutoffs: torch.Tensor = None,
+                     workspace: torch.Tensor = None):
+    """`volume_order_stats` for up to 16 percentiles in one call and a fixed four sweeps over the volume: (pairs float32 [B][Q][2], cutoffs
+    float32 [B][Q]), equal to its results bit for bit for the same percentile.  The percentiles go to the kernels by value.  No sort, no host
+    read.  The outputs and the scratch `workspace` (int32, B * LANDMARKS_WS_WORDS) are allocated here unless given."""
+    B, V = _volumes(x, "volume_landmarks x")
+    _chk(stats, torch.float64, "volume_landmarks stats", B * NORMALIZE_STATS)
+    q = [float(p) for p in percentiles]
+    if not 1 <= len(q) <= LANDMARKS_MAX or any(not 0.0 <= p <= 100.0 for p in q):
+        raise L.GavikoHipError(f"volume_landmarks: 1..{LANDMARKS_MAX} percentiles in [0, 100], got {percentiles!r}")
+    qf = (C.c_double * len(q))(*[p / 100.0 for p in q])
+    ws = torch.empty(B * LANDMARKS_WS_WORDS, dtype=torch.int32, device=x.device) if workspace is None else workspace
+    pairs = torch.empty((B, len(q), 2), dtype=torch.float32, device=x.device) if pairs is None else pairs
+    cutoffs = torch.empty((B, len(q)), dtype=torch.float32, device=x.device) if cutoffs is None else cutoffs
+    _chk(ws, torch.int32, "volume_landmarks workspace", B * LANDMARKS_WS_WORDS)
+    _chk(pairs, torch.float32, "volume_landmarks pairs", 2 * B * len(q))
+    _chk(cutoffs, torch.float32, "volume_landmarks cutoffs", B * len(q))
+    L.launch.gvk_volume_landmarks(x, stats, ws, pairs, cutoffs, len(q), qf, B, V)
+    return pairs, cutoffs
+
+
+def histogram_standardize(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, cutoffs: torch.Tensor, targets, epsilon: float = 1e-5,
+                          status: torch.Tensor = None, params: torch.Tensor = None) -> torch.Tensor:
+    """torchio's HistogramStandardization apply step: the piecewise-linear map that takes each volume's own 11 landmarks, cutoffs float32
+    [B][11] (`volume_landmarks`), onto the 11 trained `targets` (host floats), y = float32(slope_j x + icpt_j) in float64 with j the number
+    of interior landmarks <= x.  Every voxel is mapped.  Returns status int32 [B] (0 standardised, 1 empty mask: such a sample is copied bit
+    for bit), a device tensor nobody waits on."""
+    B, V = _volumes(x, "histogram_standardize x")
+    _chk(y, torch.float32, "histogram_standardize y", x.numel())
+    _chk(stats, torch.float64, "histogram_standardize stats", B * NORMALIZE_STATS)
+    if not isinstance(cutoffs, torch.Tensor) or cutoffs.dim() != 2 or tuple(cutoffs.shape) != (B, HISTSTD_KNOTS):
+        raise L.GavikoHipError(f"histogram_standardize: cutoffs are [B = {B}][{HISTSTD_KNOTS}] (the volume's landmarks)")
+    _chk(cutoffs, torch.float32, "histogram_standardize cutoffs")
+    m = [float(t) for t in targets]
+    if len(m) != HISTSTD_KNOTS or not all(np.isfinite(m)) or not float(epsilon) >= 0.0:
+        raise L.GavikoHipError(f"histogram_standardize: {HISTSTD_KNOTS} finite targets and epsilon >= 0, got {targets!r}, {epsilon!r}")
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=x.device)
+    if params is None:
+        params = torch.empty((B, HISTSTD_PARAMS), dtype=torch.float64, device=x.device)
+    _chk(status, torch.int32, "histogram_standardize status", B)
+    _chk(params, torch.float64, "histogram_standardize params", HISTSTD_PARAMS * B)
+    L.launch.gvk_histogram_standardize(x, y, stats, cutoffs, (C.c_double * HISTSTD_KNOTS)(*m), float(epsilon), params, status, B, V)
+    return status
+
+
 AXIS_CONV_MAX_N, SPIKE_MAX = 256, 4                                       # GVK_AXIS_CONV_MAX_N, GVK_SPIKE_MAX
 KSPACE_COPY, KSPACE_GAMMA, KSPACE_SPIKE = 0, 1, 2                         # kind[b] of gamma_spike
 

@@ -772,6 +772,29 @@ int gvk_volume_order_stats(const float* x, const double* stats, void* workspace,
 int gvk_normalize_intensity(const float* x, float* y, const double* stats, const float* cutoffs, int Q, double* params, int32_t* status, int mode,
                             float out_min, float out_max, int B, int64_t V, void* stream);
 
+/* ---- histogram standardisation (csrc/normalize.hip): tio.HistogramStandardization (Nyul & Udupa) --------------------------------------
+ * Same volumes, tables and preconditions as above; stats comes from gvk_volume_stats of the same x.  fractions_host and targets_host are
+ * HOST arrays: they are copied into the kernels' arguments, never into device memory.  No host read, no floating-point atomics: the same
+ * bits on every run.
+ * gvk_volume_landmarks: gvk_volume_order_stats for 1 <= Q <= GVK_LANDMARKS_MAX percentile fractions fractions_host[Q] in one call: pairs
+ *   [B][Q][2] and cutoffs [B][Q] equal its results bit for bit for the same fraction (same ranks, same keys, same cutoff arithmetic).  The
+ *   radix select runs GVK_LANDMARKS_PASSES passes of 8-bit digits, every one of the 2 Q wanted ranks with a histogram slot of its own
+ *   (32 slots x 256 bins = 32 KB of LDS), so a pass is exactly one sweep over the volume whatever Q, the data and the number of distinct
+ *   prefixes are: 4 sweeps per call.  An empty mask gives zeros.  workspace: B * GVK_LANDMARKS_WS_WORDS uint32.
+ * gvk_histogram_standardize: cutoffs [B][GVK_HISTSTD_KNOTS] are the volume's own landmarks k_j (float32, ascending), targets_host
+ *   [GVK_HISTSTD_KNOTS] the trained ones m_j.  A one-thread-per-sample step writes params [B][GVK_HISTSTD_PARAMS] doubles = (k_0..k_10,
+ *   slope_0..slope_9, icpt_0..icpt_9, one unused word) in float64, every operation rounded once: d_j = k_{j+1} - k_j, taken as +inf where
+ *   d_j < epsilon; slope_j = (m_{j+1} - m_j) / d_j; icpt_j = m_j - slope_j k_j.  Then ONE streaming pass writes
+ *   y = float32(slope_j (double)x + icpt_j), product and sum rounded once each (no FMA), j = the number of interior knots k_1..k_9 that
+ *   are <= x (np.digitize, right = False; nine float32 compares): the first and last segment extrapolate.  The mask only chose the voxels
+ *   the landmarks came from; every voxel is mapped.  status: 0 standardised; 1 empty mask -- such a sample is copied bit for bit. */
+enum { GVK_LANDMARKS_MAX = 16, GVK_LANDMARKS_PASSES = 4, GVK_LANDMARKS_WS_WORDS = 128 + 4 * 32 * 256 };
+enum { GVK_HISTSTD_KNOTS = 11, GVK_HISTSTD_PARAMS = 32 };
+int gvk_volume_landmarks(const float* x, const double* stats, void* workspace, float* pairs, float* cutoffs, int Q, const double* fractions_host, int B,
+                         int64_t V, void* stream);
+int gvk_histogram_standardize(const float* x, float* y, const double* stats, const float* cutoffs, const double* targets_host, double epsilon,
+                              double* params, int32_t* status, int B, int64_t V, void* stream);
+
 /* ---- tio.RandomGhosting / RandomSpike / RandomGamma / RandomAnisotropy (csrc/kspace.hip): the rest of torchio's MRI augmentation family ----
  * Volumes are float32 [B][D][H][W], one channel, resident in HBM; every table is a DEVICE array with one row per sample and is never read by
  * the host, so one launch serves a batch in which each sample drew a different axis, a different transform or none.  A sample that drew
