@@ -53,7 +53,7 @@ def make_dataset(root, n, num_classes, seed=0, ragged=False):
 
 
 def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gaviko_run", batch_size=4, lr=1e-3, seed=0, log=print, intensity_augment=False,
-        motion_augment=False, batch_mix=False, ragged=False, histogram=False):
+        motion_augment=False, batch_mix=False, ragged=False, histogram=False, ood_scores=False):
     dev = torch.device("cuda:0")
     K = 5
     csv = make_dataset(os.path.join(out, "data"), samples, K, seed, ragged)
@@ -113,7 +113,22 @@ def run(method="gaviko", backbone="vit-t16", epochs=3, samples=8, out="/tmp/gavi
             best_path = load_pretrained.save_trainable(model, out, method, backbone, epoch, best_acc, tuning_params)
     paths = [os.path.join(config["data"]["image_folder"], p) for p in val_ds.df["mri_path"]]
     csv_out = metrics.write_eval_outputs(os.path.join(out, "results"), method, backbone, paths, r["y_pred"], r["accuracy"], r["quadratic_kappa"], r["auc"])
-    return dict(history=history, checkpoint=best_path, results_csv=csv_out, model=model, config=config, pre=pre, val_loader=val_loader)
+    ood_eval = None
+    if ood_scores:      # is a scan the kind of scan the model was trained on?  Gaussians on the training features, then validation volumes
+        from gaviko_amd import features, ood                              # against the same volumes behind a strong bias field and ghosting
+        embed = lambda x: features.embed(model, pre.val_transforms(x)).pooled      # noqa: E731
+        feats, labs = zip(*[(embed(to_grid(inputs)), labels.to(dev)) for inputs, labels in train_loader])
+        fit = ood.fit_gaussian(torch.cat(feats), torch.cat(labs), K)
+        shift = data.DeviceCompose([data.RandomBiasField(coefficients=1.0), data.RandomGhosting(num_ghosts=(6, 10), intensity=(1.0, 2.0))], seed=seed)
+        s_in, s_out = [], []
+        for inputs, _ in val_loader:
+            x = to_grid(inputs)
+            s_in.append(fit.relative(embed(x.clone()))[0])
+            s_out.append(fit.relative(embed(shift(x.clone())))[0])
+        ood_eval = ood.evaluate(torch.cat(s_in), torch.cat(s_out), replicates=200, seed=seed)
+        log(f"ood (relative Mahalanobis, shrinkage {fit.shrinkage:.3f} / {fit.shrinkage0:.3f}): val vs bias field + ghosting: auroc {ood_eval.auroc:.3f} "
+            f"{tuple(round(v, 3) for v in ood_eval.auroc_ci)} fpr95 {ood_eval.fpr95:.3f} aupr {ood_eval.aupr:.3f}")
+    return dict(history=history, checkpoint=best_path, results_csv=csv_out, model=model, config=config, pre=pre, val_loader=val_loader, ood=ood_eval)
 
 
 if __name__ == "__main__":
@@ -129,8 +144,10 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true", help="synthetic volumes of unequal shape and spacing, brought onto the grid by data.Conform")
     ap.add_argument("--histogram", action="store_true", help="train histogram landmarks on the synthetic training volumes (on the device) and "
                     "normalise with data.HistogramStandardization followed by ZNormalization instead of the min-max rescale")
+    ap.add_argument("--ood", action="store_true", help="after training: fit ood.fit_gaussian on the training features and score the validation volumes "
+                    "against the same volumes behind a strong RandomBiasField + RandomGhosting (ood.evaluate)")
     a = ap.parse_args()
     res = run(a.method, a.backbone, a.epochs, a.samples, a.out, intensity_augment=a.intensity_augment, motion_augment=a.motion_augment,
-              batch_mix=a.batch_mix, ragged=a.ragged, histogram=a.histogram)
+              batch_mix=a.batch_mix, ragged=a.ragged, histogram=a.histogram, ood_scores=a.ood)
     print("checkpoint:", res["checkpoint"])
     print("results   :", res["results_csv"])

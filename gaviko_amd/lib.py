@@ -235,6 +235,9 @@ SIGNATURES = {
     "gvk_class_means": [_P, _P, _P, _P, _I, _I, _I, _P],
     "gvk_ragged_minmax": [_P, _P, _P, _P, _I, _P],
     "gvk_conform_volumes": [C.POINTER(ConformDesc), _P],
+    "gvk_scatter_matrix": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
+    "gvk_mahalanobis": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "gvk_logit_scores": [_P, _P, _I, _I, _F, _P],
 }
 NO_STREAM = {"gvk_last_error": (C.c_char_p, []), "gvk_device_check": (C.c_int, []), "gvk_abi_version": (C.c_int, []),
              "gvk_attention_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -2190,3 +2190,90 @@ def class_means(x: torch.Tensor, labels: torch.Tensor, num_classes: int):
     count = torch.empty(K, dtype=torch.int32, device=x.device)
     L.launch.gvk_class_means(x, labels, mean, count, N, C_, K)
     return mean, count
+
+
+# ---- out-of-distribution statistics (csrc/ood.hip) ----
+SCATTER_TILE = 64               # gvk_scatter_matrix: S in 64 x 64 tiles, upper triangle only
+SCATTER_CHUNK = 64              # rows per fp32 accumulation chunk (absolute row indices); chunk sums are added in double
+SCATTER_TARGET = 512            # workgroups wanted (tile pairs x row slabs)
+MAHALANOBIS_MAX_K = 32          # gvk_mahalanobis: centres per call
+LOGIT_MAX_CLASSES = 256         # gvk_logit_scores: 4 classes per lane of one wave
+
+
+def scatter_split(N: int, C: int):
+    """-> (npairs, nchunks, chunks per slab, nslabs, scratch bytes) of gvk_scatter_matrix: the rule of include/gaviko_hip.h, a function of
+    (N, C) alone."""
+    nt = (C + SCATTER_TILE - 1) // SCATTER_TILE
+    npairs = nt * (nt + 1) // 2
+    nchunks = (N + SCATTER_CHUNK - 1) // SCATTER_CHUNK
+    want = min(nchunks, (SCATTER_TARGET + npairs - 1) // npairs)
+    cps = (nchunks + want - 1) // want
+    nslabs = (nchunks + cps - 1) // cps
+    return npairs, nchunks, cps, nslabs, (nslabs * npairs * SCATTER_TILE * SCATTER_TILE + nchunks) * 8
+
+
+def scatter_matrix(x: torch.Tensor, labels: torch.Tensor, mean: torch.Tensor):
+    """x f32 [N, C], labels i32 [N] (None: every row is centred on row 0 of mean), mean f32 [K, C] -> (S f64 [C, C], r4 f64 [1],
+    count i32 [K]) with d_i = fl32(x_i - mean[labels_i]):  S = sum_i d_i d_i^T (not divided, S == S.T bit for bit), r4 = sum_i (||d_i||^2)^2,
+    count = rows per label.  fp32 products and sums inside chunks of 64 rows, double across chunks, a fixed order: bit-reproducible.  The
+    labels' range is the caller's contract (a row with a label outside [0, K) contributes nothing)."""
+    N, C_ = _feat_rows(x, "scatter_matrix x")
+    K, _ = _feat_rows(mean, "scatter_matrix mean", C_)
+    if K > 65535:
+        raise L.GavikoHipError(f"scatter_matrix: K = {K} classes outside [1, 65535]")
+    if mean.device != x.device:
+        raise L.GavikoHipError(f"scatter_matrix: x on {x.device}, mean on {mean.device}")
+    if labels is not None:
+        _tab(labels, "scatter_matrix labels", N)
+    if x.data_ptr() % 16 or mean.data_ptr() % 16:
+        raise L.GavikoHipError("scatter_matrix: x and mean must be 16-byte aligned")
+    S = torch.empty((C_, C_), dtype=torch.float64, device=x.device)
+    r4 = torch.empty(1, dtype=torch.float64, device=x.device)
+    count = torch.empty(K, dtype=torch.int32, device=x.device)
+    nbytes = scatter_split(N, C_)[4]
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    L.launch.gvk_scatter_matrix(x, labels, mean, S, r4, count, scratch, nbytes, N, C_, K)
+    return S, r4, count
+
+
+def mahalanobis(q: torch.Tensor, whiten: torch.Tensor, centres: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """q f32 [Nq, C], whiten f32 [C, C] (dense W, z = W v), centres f32 [K, C], K <= 32 -> d2 f32 [Nq, K] = ||W q_n - W m_k||^2: both sides
+    whitened by the same fp32 MFMA chain, the differences of the whitened coordinates squared and added in fp32 (d2 >= 0, exactly 0 for
+    q_n == m_k); a row's result does not depend on Nq."""
+    Nq, C_ = _feat_rows(q, "mahalanobis q")
+    _feat_rows(whiten, "mahalanobis whiten", C_)
+    if whiten.shape[0] != C_:
+        raise L.GavikoHipError(f"mahalanobis whiten: expected [{C_}, {C_}], got {tuple(whiten.shape)}")
+    K, _ = _feat_rows(centres, "mahalanobis centres", C_)
+    if K > MAHALANOBIS_MAX_K:
+        raise L.GavikoHipError(f"mahalanobis: K = {K} centres outside [1, {MAHALANOBIS_MAX_K}]")
+    if whiten.device != q.device or centres.device != q.device:
+        raise L.GavikoHipError(f"mahalanobis: q on {q.device}, whiten on {whiten.device}, centres on {centres.device}")
+    if q.data_ptr() % 16 or whiten.data_ptr() % 16 or centres.data_ptr() % 16:
+        raise L.GavikoHipError("mahalanobis: q, whiten and centres must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((Nq, K), dtype=torch.float32, device=q.device)
+    _chk(out, torch.float32, "mahalanobis out")
+    if tuple(out.shape) != (Nq, K):
+        raise L.GavikoHipError(f"mahalanobis out: expected [{Nq}, {K}], got {tuple(out.shape)}")
+    L.launch.gvk_mahalanobis(q, whiten, centres, out, Nq, C_, K)
+    return out
+
+
+def logit_scores(logits: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+    """logits f32 [N, K], 2 <= K <= 256 -> f32 [N, 4]: the largest softmax probability, the largest logit, T logsumexp(z / T) and the
+    entropy of softmax(z) in nats; computed in double, shifted by the row maximum, one rounding at the store."""
+    if not isinstance(logits, torch.Tensor):
+        raise L.GavikoHipError(f"logit_scores logits: expected a tensor, got {type(logits).__name__}")
+    _chk(logits, torch.float32, "logit_scores logits")
+    if logits.dim() != 2 or logits.shape[0] < 1:
+        raise L.GavikoHipError(f"logit_scores logits: expected [N, K], got {tuple(logits.shape)}")
+    N, K = logits.shape
+    if not 2 <= K <= LOGIT_MAX_CLASSES:
+        raise L.GavikoHipError(f"logit_scores: K = {K} classes outside [2, {LOGIT_MAX_CLASSES}]")
+    T = float(temperature)
+    if not 0.0 < T < float("inf"):
+        raise L.GavikoHipError(f"logit_scores: temperature = {temperature!r} (a finite positive number)")
+    out = torch.empty((N, 4), dtype=torch.float32, device=logits.device)
+    L.launch.gvk_logit_scores(logits, out, N, K, T)
+    return out

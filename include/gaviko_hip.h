@@ -1113,6 +1113,39 @@ typedef struct gvk_conform_desc {
 int gvk_ragged_minmax(const float* data, const int64_t* offsets, const int64_t* counts, float* partials, int B, void* stream);
 int gvk_conform_volumes(const gvk_conform_desc* d, void* stream);
 
+/* ---- out-of-distribution statistics (csrc/ood.hip; gaviko_amd/ood.py) ----
+ * fp32 in, no atomics, every sum in a fixed order: two runs are bit-identical.  C % 4 == 0, C <= 1024 as in the feature kernels; x, mean,
+ * q, W and m 16-byte aligned.
+ * gvk_scatter_matrix: x f32 [N][C], labels int32 [N] or NULL, mean f32 [K][C].  With d_i = fl32(x_i - mean[labels_i]) (row 0 of mean for every
+ *   row when labels is NULL) it writes
+ *     S f64 [C][C] = sum_i d_i d_i^T (NOT divided),   r4 f64 [1] = sum_i (||d_i||^2)^2,   count int32 [K] = rows per label.
+ *   A label outside [0, K) contributes nothing and is not counted (the caller rejects such labels).  1 <= K <= 65535, N >= 1.
+ *   Products on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).  The rows are cut into chunks of 64 rows at absolute row
+ *   indices (chunk c = rows [64 c, 64 c + 64)): inside a chunk an entry is one chain of fp32 fmas in row order, the chunk sums are then added in
+ *   double, in chunk order inside a slab of consecutive chunks and in slab order over the slabs.  ||d_i||^2 is summed in fp32 (per lane the
+ *   columns 4 l .. 4 l + 3, 4 l + 256 .., then the xor butterfly), squared and accumulated in double: per chunk in row order, then thread t
+ *   of one workgroup adds the chunks t, t + 256, .. and the 256 sums are folded in halves -- an order that depends on N alone.  Only the 64 x 64 tiles on and above
+ *   the diagonal are computed and each is written twice from the same double: S == S^T bit for bit.  Grid = tile pairs x slabs; with
+ *   nt = ceil(C / 64), npairs = nt (nt + 1) / 2, nchunks = ceil(N / 64):  want = min(nchunks, ceil(512 / npairs)),  cps = ceil(nchunks / want),
+ *   nslabs = ceil(nchunks / cps) -- a function of (N, C) alone.  scratch: (nslabs * npairs * 4096 + nchunks) * 8 bytes, 8-byte aligned.
+ *   Rows past N are never read.
+ * gvk_mahalanobis: q f32 [Nq][C], W f32 [C][C] (dense whitening matrix, z = W v), m f32 [K][C] -> d2 f32 [Nq][K],
+ *     d2[n][k] = sum_j ( (W q_n)_j - (W m_k)_j )^2 ,   (W v)_j = sum_c W[j][c] v[c] on v_mfma_f32_16x16x4_f32 in column order,
+ *   the queries and the centres whitened by the same chain of fmas (q_n == m_k bit for bit gives exactly 0), the differences of the whitened
+ *   coordinates formed, squared and added in fp32: never the ||z||^2 + ||m||^2 - 2 z.m form, d2 >= 0 always.  The whitened rows stay on the
+ *   chip: a workgroup of eight waves holds 16 queries, wave w walks the coordinate chunks [16 t, 16 t + 16), t = w, w + 8, .., and keeps K
+ *   running sums per query; a lane adds its coordinates in chunk order, the 16 lanes of a query meet in the xor butterfly (1, 2, 4, 8), the
+ *   eight waves are added in wave order.  The order depends on C alone: a row's result does not depend on Nq, its tile or the grid.
+ *   1 <= K <= 32, Nq >= 1.  Rows past Nq are never read.  Cost: ceil(Nq / 16) workgroups, each reading all of W (from L2) and whitening the
+ *   K centres again: bound by the W traffic, and CUs stay idle below Nq of about 4096.
+ * gvk_logit_scores: logits f32 [N][K], temperature T > 0 -> out f32 [N][4] = { max softmax probability, max logit, T logsumexp(z / T),
+ *   entropy of softmax(z) in nats with 0 log 0 = 0 }.  One wave per row, computed in double shifted by the row maximum, one rounding at the
+ *   store; nothing overflows for finite logits, the entropy is >= 0.  2 <= K <= 256, N >= 1. */
+int gvk_scatter_matrix(const float* x, const int32_t* labels, const float* mean, double* S, double* r4, int32_t* count, void* scratch,
+                       int64_t scratch_bytes, int N, int C, int K, void* stream);
+int gvk_mahalanobis(const float* q, const float* W, const float* m, float* d2, int Nq, int C, int K, void* stream);
+int gvk_logit_scores(const float* logits, float* out, int N, int K, float temperature, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
