@@ -15,12 +15,6 @@ namespace gvk {
 constexpr int kBootMaxN = GVK_BOOTSTRAP_MAX_ROWS;               // multiplicities stay below 2^24 (the label shares their LDS word), two N-entry LDS arrays
 constexpr int kBootMaxK = GVK_BOOTSTRAP_MAX_CLASSES;            // the label takes the 8 bits above them; K x K counters in LDS
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One 256-thread workgroup per replicate.  LDS (dynamic): wl[Npad] | P[Npad] | conf[K * K], Npad = N rounded up to the scan tile.
 //   wl[row] = label << 24 | multiplicity: the label is laid down first, the N draws of the replicate add 1 each (32-bit LDS atomics; a
 //   multiplicity is at most N <= 8192, so it never reaches the label), and every later pass gets both from one LDS read.
@@ -83,8 +77,8 @@ __global__ __launch_bounds__(256) void bootstrap_counts_kernel(const long long* 
         npos += w;
       }
     }
-    acc = wave_sum_u64(acc);
-    npos = wave_sum_u64(npos);
+    acc = wave_sum(acc);
+    npos = wave_sum(npos);
     if (lane == 0) { s_red[wave] = acc; s_red[4 + wave] = npos; }
     __syncthreads();
     if (t == 0) {

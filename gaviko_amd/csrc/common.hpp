@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <functional>
 #include <stdint.h>
+#include <type_traits>
 
 namespace gvk {
 
@@ -25,7 +26,12 @@ constexpr int kWave = 64;
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// Full-wave xor butterflies: every lane ends with the same bits.  A butterfly that carries a pair (an argmax, a packed key) stays with its kernel.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double> || std::is_same_v<T, int> || std::is_same_v<T, long long> ||
+                    std::is_same_v<T, unsigned long long>,
+                "wave_sum: a 32- or 64-bit type __shfl_xor moves whole");
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -34,6 +40,40 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// v_mfma_f32_16x16x4_f32: fp32 operands, one rounding per product, fp32 accumulation in k order.  Lane l supplies A[row l & 15][k = l >> 4]
+// and B[k = l >> 4][column l & 15] and holds C/D[row 4 (l >> 4) + register][column l & 15].
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// sum / max over the four k-quarters of a 16x16 tile: the lanes that share lane & 15
+__device__ __forceinline__ float kq_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+__device__ __forceinline__ float kq_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+// LDS traffic between the lanes of ONE wave: the DS unit serves a wave's requests in order, the fence keeps the compiler from moving them
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // Attention-style grids: `nblk` row blocks of each of `ngrp` independent (batch, head) groups all stream the SAME operand of their group.
@@ -166,6 +206,17 @@ inline int ensure_lds(K kernel, size_t bytes, size_t& granted, const char* who) 
   if (e != hipSuccess) return set_error(-3, "hipFuncSetAttribute(%s): %s", who, hipGetErrorString(e));
   granted = bytes;
   return 0;
+}
+
+// grid of a grid-stride kernel with 256 threads per workgroup: one workgroup per 256 items, at least 1 and at most `cap`
+inline unsigned grid_blocks(int64_t n, int64_t cap) {
+  const int64_t b = (n + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+// do [a, a + bytes) and [b, b + bytes) share a byte: the "in and out must not overlap" test of the kernels that read neighbours of what they write
+inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return !(p + bytes <= q || q + bytes <= p);
 }
 }  // namespace gvk
 

@@ -108,11 +108,6 @@ __global__ __launch_bounds__(256) void rows_gather_kernel(const float* __restric
   }
 }
 
-static unsigned blocks_for(long n, long cap = 4096) {
-  long b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace gvk
 
 extern "C" int gvk_evp_highpass(const float* img, const float* hp, const int32_t* depth_mask, float* out, int B, int D, int H, int W, void* stream) {
@@ -125,37 +120,37 @@ extern "C" int gvk_pad2d_f32(const float* src, int ld_src, int rows, int cols, i
   using namespace gvk;
   GVK_REQUIRE(src && dst && rows > 0 && cols > 0 && drows > 0 && dcols > 0 && ld_src >= cols && ld_dst >= dcols, "gvk_pad2d_f32: bad arguments");
   GVK_REQUIRE(transpose ? (drows >= cols && dcols >= rows) : (drows >= rows && dcols >= cols), "gvk_pad2d_f32: destination smaller than the source");
-  GVK_LAUNCH(pad2d_kernel, dim3(blocks_for((long)drows * dcols, 1L << 30)), dim3(256), 0, (hipStream_t)stream, src, ld_src, rows, cols, transpose, dst, ld_dst, drows,
+  GVK_LAUNCH(pad2d_kernel, dim3(grid_blocks((int64_t)drows * dcols, (int64_t)1 << 30)), dim3(256), 0, (hipStream_t)stream, src, ld_src, rows, cols, transpose, dst, ld_dst, drows,
              dcols);
   return check_launch("pad2d_f32");
 }
 extern "C" int gvk_add2d_f32(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int rows, int cols, void* stream) {
   using namespace gvk;
   GVK_REQUIRE(a && b && out && rows > 0 && cols > 0 && lda >= cols && ldb >= cols && ldo >= cols, "gvk_add2d_f32: bad arguments");
-  GVK_LAUNCH(add2d_kernel, dim3(blocks_for((long)rows * cols, 1L << 30)), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, out, ldo, rows, cols);
+  GVK_LAUNCH(add2d_kernel, dim3(grid_blocks((int64_t)rows * cols, (int64_t)1 << 30)), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, out, ldo, rows, cols);
   return check_launch("add2d_f32");
 }
 extern "C" int gvk_gelu_fwd_f32(const float* x, float* y, int64_t n, void* stream) {
   using namespace gvk;
   GVK_REQUIRE(x && y && n > 0, "gvk_gelu_fwd_f32: bad arguments");
-  GVK_LAUNCH(gelu_fwd_kernel, dim3(blocks_for(n, 1L << 30)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
+  GVK_LAUNCH(gelu_fwd_kernel, dim3(grid_blocks(n, (int64_t)1 << 30)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
   return check_launch("gelu_fwd_f32");
 }
 extern "C" int gvk_gelu_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   using namespace gvk;
   GVK_REQUIRE(dy && x && dx && n > 0, "gvk_gelu_bwd_f32: bad arguments");
-  GVK_LAUNCH(gelu_bwd_kernel, dim3(blocks_for(n, 1L << 30)), dim3(256), 0, (hipStream_t)stream, dy, x, dx, (long)n);
+  GVK_LAUNCH(gelu_bwd_kernel, dim3(grid_blocks(n, (int64_t)1 << 30)), dim3(256), 0, (hipStream_t)stream, dy, x, dx, (long)n);
   return check_launch("gelu_bwd_f32");
 }
 extern "C" int gvk_rows_patch(float* tok, const float* src, const float* pos, int B, int T, int N, int C, int row_off, int accumulate, void* stream) {
   using namespace gvk;
   GVK_REQUIRE(tok && src && B > 0 && N > 0 && C % 4 == 0 && row_off >= 0 && row_off + N <= T, "gvk_rows_patch: bad arguments");
-  GVK_LAUNCH(rows_patch_kernel, dim3(blocks_for((long)B * N * (C / 4))), dim3(256), 0, (hipStream_t)stream, tok, src, pos, B, T, N, C, row_off, accumulate);
+  GVK_LAUNCH(rows_patch_kernel, dim3(grid_blocks((int64_t)B * N * (C / 4), 4096)), dim3(256), 0, (hipStream_t)stream, tok, src, pos, B, T, N, C, row_off, accumulate);
   return check_launch("rows_patch");
 }
 extern "C" int gvk_rows_gather(const float* tok, float* dst, int B, int T, int N, int C, int row_off, void* stream) {
   using namespace gvk;
   GVK_REQUIRE(tok && dst && B > 0 && N > 0 && C % 4 == 0 && row_off >= 0 && row_off + N <= T, "gvk_rows_gather: bad arguments");
-  GVK_LAUNCH(rows_gather_kernel, dim3(blocks_for((long)B * N * (C / 4))), dim3(256), 0, (hipStream_t)stream, tok, dst, B, T, N, C, row_off);
+  GVK_LAUNCH(rows_gather_kernel, dim3(grid_blocks((int64_t)B * N * (C / 4), 4096)), dim3(256), 0, (hipStream_t)stream, tok, dst, B, T, N, C, row_off);
   return check_launch("rows_gather");
 }

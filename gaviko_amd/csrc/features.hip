@@ -85,17 +85,6 @@ __device__ __forceinline__ bool better(float k1, int i1, float k2, int i2) { ret
 __device__ __forceinline__ bool better3(float k1, int i1, int w1, float k2, int i2, int w2) {
   return k1 > k2 || (k1 == k2 && (i1 < i2 || (i1 == i2 && w1 < w2)));
 }
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float kq_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-// LDS traffic between the lanes of ONE wave: the DS unit serves a wave's requests in order, the fence keeps the compiler from moving them
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // One wave merges P sorted lists (best first, k entries each, list p at lk / li + p * pstride) into the k best, written by lane 0 to
 // ok / oi.  Lane l owns the lists l, l + 64, ... (PL of them) and a head position in each; every step is one butterfly for the best head

@@ -11,11 +11,6 @@
 
 namespace gvk {
 
-static unsigned ig_blocks(int64_t n, int64_t cap = 4096) {
-  int64_t b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // out[b] = beta * out[b] + sum_{j < nsum} alpha * G[b * nsum + j] (* (x[b] - x0[b])), G = the volume of dcols rows (b * nsum + j) * N ...
 // One thread per 4 consecutive voxels along W (pw % 4 == 0: they are 4 consecutive columns of one dcols row).  The sum runs over j in order
 // as one FMA per step, so splitting the j range over several calls (beta = 1 after the first) gives the same bits.  beta == 0 never reads out.
@@ -139,7 +134,7 @@ extern "C" int gvk_unpatchify_f32(const float* dcols, float* out, const float* x
               "gvk_unpatchify_f32: volume %dx%dx%d not divisible by patch %dx%dx%d (pw must be a multiple of 4)", D, H, W, pd, ph, pw);
   GVK_REQUIRE((((uintptr_t)dcols | (uintptr_t)out | (uintptr_t)x | (uintptr_t)x0) & 15) == 0, "gvk_unpatchify_f32: pointers must be 16-byte aligned");
   const int64_t total = (int64_t)B * D * H * (W / 4);
-  GVK_LAUNCH(unpatchify_kernel, dim3(ig_blocks(total)), dim3(256), 0, (hipStream_t)stream, dcols, out, x, x0, B, D, H, W, pd, ph, pw, nsum, alpha, beta);
+  GVK_LAUNCH(unpatchify_kernel, dim3(grid_blocks(total, 4096)), dim3(256), 0, (hipStream_t)stream, dcols, out, x, x0, B, D, H, W, pd, ph, pw, nsum, alpha, beta);
   return check_launch("unpatchify_f32");
 }
 

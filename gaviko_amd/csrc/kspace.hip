@@ -6,7 +6,7 @@
 // mask does not depend on the other two frequency axes, so their transforms cancel against the inverses, exactly as in motion.hip; what is
 // left is a real circular convolution along that axis,  y[..i..] = sum_i' c[(i - i') mod N] x[..i'..],  with the row c built on the host in
 // float64 (data.ghosting_tables).  Unlike RandomMotion the axis is drawn per sample and can be any of the three:
-//   axis 2  Y = X . C,  X = 32 (d, h) lines of W voxels: motion.hip's product with one image and no resampling;
+//   axis 2  Y = X . C,  X = 32 (d, h) lines of W voxels (circulant.hpp);
 //   axis 0  Y = C . X,  X = [D x 32 columns of the flattened H*W axis], rows H*W apart;
 //   axis 1  Y = C . X,  X = [H x 32 columns of W] of one d, rows W apart.
 // In the two left-multiply forms the contraction axis is the strided one and the columns are contiguous, so every global access still runs
@@ -21,7 +21,7 @@
 //
 // gvk_axis_gather2 (anisotropy): nearest-neighbour downsampling along one axis followed by linear upsampling collapses to two taps per output
 // index; the host does all coordinate arithmetic in float64 (data.anisotropy_tables) and the device only gathers and blends.
-#include "common.hpp"
+#include "circulant.hpp"
 #include "../../include/gaviko_hip.h"
 
 namespace gvk {
@@ -32,19 +32,15 @@ constexpr int kAcCols = 32;                                    // axes 0, 1: col
 constexpr int kAcTiles = kAcMaxN / 32;                         // 16-wide tiles of the convolved axis one wave owns at most
 static_assert(kAcMaxN == 256 && kAcMaxN % 32 == 0, "the tile lists and strides below assume a cap of 256");
 
-// LDS strides.  Both operands of v_mfma_f32_16x16x4_f32 are read one dword per lane (ds_read_b32: 32 banks, the two 32-lane halves are
-// served separately, so the 16 lanes x 2 k of one half must fall on 32 different banks).
-// Axis 2, A operand = x[line l & 15][k = l >> 4]: bank = stride * line + k, so the stride is 2 above a multiple of 32 (motion.hip's motion_stride).
+// LDS strides, by the bank rule stated at circulant_stride, which is the stride of axis 2.
 // Axes 0 and 1, B operand = x[k = l >> 4][column l & 15]: bank = stride * k + column, so the stride is 16 above a multiple of 32.
-__host__ __device__ constexpr int line_stride(int Wk) { return ((Wk + 31) & ~31) + 2; }
 constexpr int kAcColStride = kAcCols + 16;
-constexpr int kAcLdsX = kAcMaxN * kAcColStride > kAcLines * line_stride(kAcMaxN) ? kAcMaxN * kAcColStride : kAcLines * line_stride(kAcMaxN);
+constexpr int kAcLdsX = kAcMaxN * kAcColStride > kAcLines * circulant_stride(kAcMaxN) ? kAcMaxN * kAcColStride : kAcLines * circulant_stride(kAcMaxN);
 
 // 256 threads = 4 waves.  One grid serves the three forms: blockIdx.y = sample, blockIdx.x = work item of that sample's form (the grid is
-// sized for the form with the most items; the others' surplus workgroups leave at once).  Wave v owns tile v & 1 of the 32 lines / columns
-// and the tiles (v >> 1), (v >> 1) + 2, ... of the convolved axis: nt = ceil(tiles / 2) <= 8 accumulators, kept in registers by a fully
-// unrolled loop whose wave-uniform test skips the unused ones.  With an odd number of tiles the waves with v >> 1 = 1 run one tile past the
-// axis (s_c is filled that far, the result is dropped).
+// sized for the form with the most items; the others' surplus workgroups leave at once).  The waves split the tiles as circulant.hpp says,
+// in the left-multiply forms with v & 1 choosing 16 of the 32 columns; nt = ceil(tiles / 2) <= 8 accumulators are live, and the fully
+// unrolled loops skip the others with a wave-uniform test.
 __global__ __launch_bounds__(256) void axis_circular_conv_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ ctab,
                                                                  const int* __restrict__ axis, const int* __restrict__ live, int D, int H, int W) {
   __shared__ float s_x[kAcLdsX];                               // the operand slab, then the output tile
@@ -66,12 +62,7 @@ __global__ __launch_bounds__(256) void axis_circular_conv_kernel(const float* __
   if ((int)blockIdx.x >= nwork) return;
   const int Nk = (N + 15) & ~15, N4 = (N + 3) & ~3;            // rows / columns of the output tiles; k extent of the product (k = N.. are zero)
   const int ntile = Nk >> 4, nt = (ntile + 1) >> 1;
-  const float* c = ctab + (size_t)b * kAcMaxN;
-  for (int i = tid; i < 2 * Nk + 16; i += 256) {
-    int m = (i - Nk) % N;
-    if (m < 0) m += N;
-    s_c[i] = c[m];
-  }
+  circulant_fill_row(s_c, ctab + (size_t)b * kAcMaxN, N, Nk, tid);
   f32x4 acc[kAcTiles];
 #pragma unroll
   for (int i = 0; i < kAcTiles; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -80,32 +71,13 @@ __global__ __launch_bounds__(256) void axis_circular_conv_kernel(const float* __
   if (ax == 2) {                                               // Y = X . C: 32 lines, contraction along the contiguous axis
     const int line0 = blockIdx.x * kAcLines;
     const int nlines = min(kAcLines, DH - line0);
-    const int S = line_stride(Nk);
+    const int S = circulant_stride(Nk);
     for (int r = wave; r < kAcLines; r += 4)                   // a wave per line, lanes along W: coalesced; lines past the volume and columns
       for (int w = lane; w < S; w += 64)                       // past W are zero and contribute nothing
         s_x[r * S + w] = (r < nlines && w < W) ? src[(size_t)(line0 + r) * W + w] : 0.f;
     __syncthreads();
-    // lane l holds A[line l & 15][k = k0 + (l >> 4)] and B[k = k0 + (l >> 4)][column l & 15] = c[(column - k) mod W]
-    const float* xa = s_x + (half * 16 + (lane & 15)) * S + (lane >> 4);
-    const float* cb = s_c + t0 * 16 + (lane & 15) - (lane >> 4) + Nk;
-    for (int k0 = 0; k0 < N4; k0 += 4) {
-      const float a = xa[k0];
-#pragma unroll
-      for (int i = 0; i < kAcTiles; ++i)
-        if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, cb[i * 32 - k0], acc[i], 0, 0, 0);
-    }
-    __syncthreads();
-    // C/D map of the 16x16 forms: column = lane & 15, row = 4 (lane >> 4) + register.  Through LDS, so that lines leave as whole rows.
-#pragma unroll
-    for (int i = 0; i < kAcTiles; ++i) {
-      const int ct = t0 + 2 * i;
-      if (i < nt && ct < ntile)                                // wave-uniform
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s_x[(half * 16 + (lane >> 4) * 4 + e) * S + ct * 16 + (lane & 15)] = acc[i][e];
-    }
-    __syncthreads();
-    for (int r = wave; r < nlines; r += 4)
-      for (int w = lane; w < W; w += 64) dst[(size_t)(line0 + r) * W + w] = s_x[r * S + w];
+    circulant_product<kAcTiles>(acc, nt, s_x, S, s_c, Nk, N4, half, t0, lane);
+    circulant_store_lines<kAcTiles>(acc, nt, s_x, S, dst, line0, nlines, W, Nk, half, t0, wave, lane);
     return;
   }
 
@@ -129,7 +101,7 @@ __global__ __launch_bounds__(256) void axis_circular_conv_kernel(const float* __
     const float bv = xb[k0 * kAcColStride];
 #pragma unroll
     for (int i = 0; i < kAcTiles; ++i)
-      if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(ca[i * 32 - k0], bv, acc[i], 0, 0, 0);
+      if (i < nt) acc[i] = mfma4(ca[i * 32 - k0], bv, acc[i]);
   }
   __syncthreads();
 #pragma unroll
@@ -220,11 +192,6 @@ __global__ __launch_bounds__(256) void axis_gather2_kernel(const float* __restri
   }
 }
 
-static bool overlap(const void* in, const void* out, size_t bytes) {
-  const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out;
-  return !(a + bytes <= o || o + bytes <= a);
-}
-
 }  // namespace gvk
 
 extern "C" int gvk_axis_circular_conv(const float* in, float* out, const float* ctab, const int32_t* axis, const int32_t* live, int B, int D, int H,
@@ -235,7 +202,7 @@ extern "C" int gvk_axis_circular_conv(const float* in, float* out, const float* 
   // axis is a device table this call does not read, so every extent a sample may convolve along has to be in range
   GVK_REQUIRE(D >= 2 && D <= kAcMaxN && H >= 2 && H <= kAcMaxN && W >= 2 && W <= kAcMaxN,
               "gvk_axis_circular_conv: volume (%d, %d, %d): 2..%d voxels on the convolved axis are built, and any axis may be drawn", D, H, W, kAcMaxN);
-  GVK_REQUIRE(!overlap(in, out, (size_t)B * D * H * W * sizeof(float)), "gvk_axis_circular_conv: in and out must not overlap");
+  GVK_REQUIRE(!ranges_overlap(in, out, (size_t)B * D * H * W * sizeof(float)), "gvk_axis_circular_conv: in and out must not overlap");
   const int n2 = (D * H + kAcLines - 1) / kAcLines, n1 = D * ((W + kAcCols - 1) / kAcCols), n0 = (H * W + kAcCols - 1) / kAcCols;
   const unsigned gx = (unsigned)max(n2, max(n1, n0));
   GVK_LAUNCH(axis_circular_conv_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, in, out, ctab, (const int*)axis, (const int*)live, D, H, W);
@@ -248,7 +215,7 @@ extern "C" int gvk_gamma_spike(const float* in, float* out, const int32_t* kind,
   GVK_REQUIRE(in && out && kind && gamma && amp && nspikes && tab && stats, "gvk_gamma_spike: null pointer");
   GVK_REQUIRE(B > 0 && B <= 65535 && D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < ((int64_t)1 << 31), "gvk_gamma_spike: bad shape");
   const size_t V = (size_t)D * H * W;
-  GVK_REQUIRE(!overlap(in, out, (size_t)B * V * sizeof(float)), "gvk_gamma_spike: in and out must not overlap");
+  GVK_REQUIRE(!ranges_overlap(in, out, (size_t)B * V * sizeof(float)), "gvk_gamma_spike: in and out must not overlap");
   const unsigned gx = (unsigned)((V + kGsChunk - 1) / kGsChunk);
   GVK_LAUNCH(gamma_spike_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, in, out, (const int*)kind, gamma, amp, (const int*)nspikes, tab, stats,
              D, H, W);
@@ -263,7 +230,7 @@ extern "C" int gvk_axis_gather2(const float* in, float* out, const int32_t* src,
   GVK_REQUIRE(n_max >= D && n_max >= H && n_max >= W, "gvk_axis_gather2: table rows of %d entries, the volume is (%d, %d, %d) and any axis may be drawn",
               n_max, D, H, W);
   const size_t V = (size_t)D * H * W;
-  GVK_REQUIRE(!overlap(in, out, (size_t)B * V * sizeof(float)), "gvk_axis_gather2: in and out must not overlap (the kernel reads neighbouring voxels)");
+  GVK_REQUIRE(!ranges_overlap(in, out, (size_t)B * V * sizeof(float)), "gvk_axis_gather2: in and out must not overlap (the kernel reads neighbouring voxels)");
   const unsigned gx = (unsigned)((V + kGsChunk - 1) / kGsChunk);
   GVK_LAUNCH(axis_gather2_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, in, out, (const int*)src, w, (const int*)axis, (const int*)live, n_max,
              D, H, W);

@@ -16,7 +16,7 @@
 // one rounding per product, fp32 accumulation in k order = an fmaf chain; bf16 operands would not do, the rows cancel to an impulse on raw
 // intensities of ~1e3), image after image into the same accumulators, so the moved images never exist in HBM and every output line is
 // written once.  2 (K+1) W flops per voxel: 11.8 GFLOP at B = 4, (120,160,160), K = 2 against ~100 MB of traffic -- bound by the matrix pipe.
-#include "common.hpp"
+#include "circulant.hpp"
 #include "resample.hpp"
 #include "../../include/gaviko_hip.h"
 
@@ -26,17 +26,10 @@ constexpr int kMoLines = 32;                                   // lines per work
 constexpr int kMoMaxW = GVK_MOTION_MAX_W;
 constexpr int kMoMaxStride = kMoMaxW + 2;
 static_assert(kMoMaxW == 256, "gvk_motion_artifact lists 1..8 column tiles per wave");
-static_assert(kMoMaxW % 32 == 0, "the line stride below assumes a cap that is a multiple of 32");
+static_assert(circulant_stride(kMoMaxW) == kMoMaxStride, "s_x holds 32 lines at the widest stride");
 
-// LDS line stride for a width rounded up to 16 columns: 2 above a multiple of 32 words, so that the 16 lines x 4 k of an A-operand read
-// fall on different banks (bank = 2 line + k), and at least Wk + 2
-__host__ __device__ constexpr int motion_stride(int Wk) { return ((Wk + 31) & ~31) + 2; }
-
-// Global accesses of whole lines (plain line, dead-sample copy, output) are one dword per lane, 256 contiguous bytes per wave instruction:
-// lines start on a 16-byte boundary only when W is a multiple of 4, and the live path is bound by the matrix pipe, not by these streams.
-// 256 threads = 4 waves; wave v owns line tile v & 1 and the NT column tiles (v >> 1), (v >> 1) + 2, ...  NT = ceil(column tiles / 2) is a
-// template argument so that the accumulators are registers and the product loop has no branch; with an odd number of column tiles the
-// waves with v >> 1 = 1 run one tile past the line (s_c is filled that far, the result is dropped).
+// Global accesses of whole lines (plain line, dead-sample copy, output) are one dword per lane: the live path is bound by the matrix pipe,
+// not by these streams.  The product is circulant.hpp's; NT = ceil(column tiles / 2) is a template argument so that its loop has no branch.
 template <int NT>
 __global__ __launch_bounds__(256) void motion_artifact_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ mats,
                                                               const float* __restrict__ ctab, const int* __restrict__ live,
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(256) void motion_artifact_kernel(const float* __res
   float pad, hi_unused;
   reduce_partials(part, b, pad, hi_unused);
   const int Wk = (W + 15) & ~15, W4 = (W + 3) & ~3;            // columns of the output tiles; k extent of the product (columns W.. stay zero)
-  const int S = motion_stride(Wk), nct = Wk >> 4;
+  const int S = circulant_stride(Wk);
   for (int i = tid; i < kMoLines * S; i += 256) s_x[i] = 0.f;  // lines past the volume and columns past W contribute nothing
   const int rt = wave & 1, ct0 = wave >> 1;
   f32x4 acc[NT];
@@ -67,11 +60,7 @@ __global__ __launch_bounds__(256) void motion_artifact_kernel(const float* __res
   for (int s = 0; s <= K; ++s) {
     __syncthreads();                                           // the zero fill, or the previous image's product, is done with s_x and s_c
     const float* c = ctab + ((size_t)b * (K + 1) + s) * W;
-    for (int i = tid; i < 2 * Wk + 16; i += 256) {
-      int m = (i - Wk) % W;
-      if (m < 0) m += W;
-      s_c[i] = c[m];
-    }
+    circulant_fill_row(s_c, c, W, Wk, tid);
     const float* m = mats + ((size_t)b * K + max(s - 1, 0)) * 12;
     for (int r = wave; r < nlines; r += 4) {                   // a wave per line, lanes along W: coalesced
       const int line = line0 + r;
@@ -80,27 +69,9 @@ __global__ __launch_bounds__(256) void motion_artifact_kernel(const float* __res
         s_x[r * S + w] = s == 0 ? src[(size_t)line * W + w] : trilinear_sample(src, m, (float)d, (float)h, (float)w, D, H, W, pad);
     }
     __syncthreads();
-    // lane l holds A[line l & 15][k = k0 + (l >> 4)] and B[k = k0 + (l >> 4)][column l & 15] = c_s[(column - k) mod W]
-    const float* xa = s_x + (rt * 16 + (lane & 15)) * S + (lane >> 4);
-    const float* cb = s_c + ct0 * 16 + (lane & 15) - (lane >> 4) + Wk;
-    for (int k0 = 0; k0 < W4; k0 += 4) {
-      const float a = xa[k0];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, cb[i * 32 - k0], acc[i], 0, 0, 0);
-    }
+    circulant_product<NT>(acc, NT, s_x, S, s_c, Wk, W4, rt, ct0, lane);
   }
-  __syncthreads();
-  // C/D map of the 16x16 forms: column = lane & 15, row = 4 (lane >> 4) + register.  Through LDS, so that lines leave as whole rows.
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
-    const int ct = ct0 + 2 * i;
-    if (ct < nct)                                              // wave-uniform
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s_x[(rt * 16 + (lane >> 4) * 4 + e) * S + ct * 16 + (lane & 15)] = acc[i][e];
-  }
-  __syncthreads();
-  for (int r = wave; r < nlines; r += 4)
-    for (int w = lane; w < W; w += 64) dst[(size_t)(line0 + r) * W + w] = s_x[r * S + w];
+  circulant_store_lines<NT>(acc, NT, s_x, S, dst, line0, nlines, W, Wk, rt, ct0, wave, lane);
 }
 
 }  // namespace gvk
@@ -112,8 +83,8 @@ extern "C" int gvk_motion_artifact(const float* in, float* out, const float* mat
   GVK_REQUIRE(K >= 1 && K <= GVK_MOTION_MAX_TRANSFORMS, "gvk_motion_artifact: %d movements (1..%d are built)", K, GVK_MOTION_MAX_TRANSFORMS);
   GVK_REQUIRE(W >= 2 && W <= GVK_MOTION_MAX_W, "gvk_motion_artifact: last axis of %d voxels (2..%d are built)", W, GVK_MOTION_MAX_W);
   GVK_REQUIRE(B > 0 && D > 0 && H > 0 && B <= 65535 && (int64_t)D * H < (1ll << 30), "gvk_motion_artifact: bad shape");
-  const uintptr_t a = (uintptr_t)in, o = (uintptr_t)out, bytes = (uintptr_t)B * D * H * W * sizeof(float);
-  GVK_REQUIRE(a + bytes <= o || o + bytes <= a, "gvk_motion_artifact: in and out must not overlap (the kernel reads neighbouring lines)");
+  GVK_REQUIRE(!ranges_overlap(in, out, (size_t)B * D * H * W * sizeof(float)),
+              "gvk_motion_artifact: in and out must not overlap (the kernel reads neighbouring lines)");
   const unsigned gx = (unsigned)(((int64_t)D * H + kMoLines - 1) / kMoLines);
   switch ((W + 31) / 32) {                                     // column tiles per wave
 #define GVK_MOTION_CASE(NT)                                                                                                                       \

@@ -11,13 +11,6 @@
 
 namespace gvk {
 
-__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// LDS traffic between the lanes of ONE wave: the DS unit serves a wave's requests in order, the fence keeps the compiler from moving them
-__device__ __forceinline__ void ood_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // ---------------------------------------------------------------------------------------------------------------- scatter_matrix
 // S is cut into 64 x 64 tiles; only the pairs (ta <= tb) are computed, pair p counting (0,0), (0,1), .., (0,nt-1), (1,1), ...  The rows are
 // cut into chunks of kScatChunk = 64 rows at ABSOLUTE row indices (chunk c = rows [64 c, 64 c + 64)), and the chunks into `nslabs` slabs of
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void scatter_tile_kernel(const float* __restri
       const int i = 4 * ks + kq;                                // MFMA: lane (r, kq) supplies row i of the chunk, column r of its 16
       const float a = sA[i * kScatPitch + 16 * w + r];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = mfma_f32(a, sBB[i * kScatPitch + 16 * j + r], acc[j]);
+      for (int j = 0; j < 4; ++j) acc[j] = mfma4(a, sBB[i * kScatPitch + 16 * j + r], acc[j]);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -174,8 +167,7 @@ __global__ __launch_bounds__(256) void scatter_finish_kernel(const double* __res
     if (cls >= K) return;                                       // uniform over the wave
     int cnt = 0;
     for (int n = lane; n < N; n += 64) cnt += (labels ? labels[n] : 0) == cls ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    cnt = wave_sum(cnt);
     if (lane == 0) count[cls] = cnt;
   }
 }
@@ -238,35 +230,35 @@ __global__ __launch_bounds__(64 * kMahaWaves) void mahalanobis_kernel(const floa
     for (int ss = 0; ss < nfull; ++ss) {
       const f32x4 b4 = *(const f32x4*)(wrow + 16 * ss);
       const f32x4 a4 = *(const f32x4*)(arow + 16 * ss);
-      zq = mfma_f32(a4.x, b4.x, zq);
-      zq = mfma_f32(a4.y, b4.y, zq);
-      zq = mfma_f32(a4.z, b4.z, zq);
-      zq = mfma_f32(a4.w, b4.w, zq);
+      zq = mfma4(a4.x, b4.x, zq);
+      zq = mfma4(a4.y, b4.y, zq);
+      zq = mfma4(a4.z, b4.z, zq);
+      zq = mfma4(a4.w, b4.w, zq);
 #pragma unroll
       for (int u = 0; u < KT; ++u) {
         const f32x4 c4 = *(const f32x4*)(mrow[u] + 16 * ss);
-        zm[u] = mfma_f32(c4.x, b4.x, zm[u]);
-        zm[u] = mfma_f32(c4.y, b4.y, zm[u]);
-        zm[u] = mfma_f32(c4.z, b4.z, zm[u]);
-        zm[u] = mfma_f32(c4.w, b4.w, zm[u]);
+        zm[u] = mfma4(c4.x, b4.x, zm[u]);
+        zm[u] = mfma4(c4.y, b4.y, zm[u]);
+        zm[u] = mfma4(c4.z, b4.z, zm[u]);
+        zm[u] = mfma4(c4.w, b4.w, zm[u]);
       }
     }
     if (nfull < nss) {                                          // C % 16 != 0: the columns past C are zero on every side
       f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
       if (tail_live) b4 = *(const f32x4*)(wrow + 16 * nfull);
       const f32x4 a4 = *(const f32x4*)(arow + 16 * nfull);
-      zq = mfma_f32(a4.x, b4.x, zq);
-      zq = mfma_f32(a4.y, b4.y, zq);
-      zq = mfma_f32(a4.z, b4.z, zq);
-      zq = mfma_f32(a4.w, b4.w, zq);
+      zq = mfma4(a4.x, b4.x, zq);
+      zq = mfma4(a4.y, b4.y, zq);
+      zq = mfma4(a4.z, b4.z, zq);
+      zq = mfma4(a4.w, b4.w, zq);
 #pragma unroll
       for (int u = 0; u < KT; ++u) {
         f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
         if (tail_live) c4 = *(const f32x4*)(mrow[u] + 16 * nfull);
-        zm[u] = mfma_f32(c4.x, b4.x, zm[u]);
-        zm[u] = mfma_f32(c4.y, b4.y, zm[u]);
-        zm[u] = mfma_f32(c4.z, b4.z, zm[u]);
-        zm[u] = mfma_f32(c4.w, b4.w, zm[u]);
+        zm[u] = mfma4(c4.x, b4.x, zm[u]);
+        zm[u] = mfma4(c4.y, b4.y, zm[u]);
+        zm[u] = mfma4(c4.z, b4.z, zm[u]);
+        zm[u] = mfma4(c4.w, b4.w, zm[u]);
       }
     }
     // accumulators: lane holds Zq[query 4 kq + e][j0 + r] and Zm[centre 16 u + 4 kq + e][j0 + r]
@@ -274,7 +266,7 @@ __global__ __launch_bounds__(64 * kMahaWaves) void mahalanobis_kernel(const floa
     for (int u = 0; u < KT; ++u)
 #pragma unroll
       for (int e = 0; e < 4; ++e) zt[(16 * u + 4 * kq + e) * 17 + r] = zm[u][e];
-    ood_wave_lds_sync();
+    wave_lds_sync();
     const bool livej = j0 + r < C;                              // a coordinate past C (the last chunk of C % 16 != 0) adds nothing
 #pragma unroll
     for (int k = 0; k < KK; ++k) {
@@ -285,7 +277,7 @@ __global__ __launch_bounds__(64 * kMahaWaves) void mahalanobis_kernel(const floa
         acc[e][k] += livej ? df * df : 0.f;
       }
     }
-    ood_wave_lds_sync();
+    wave_lds_sync();
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e)
@@ -316,12 +308,6 @@ __global__ __launch_bounds__(64 * kMahaWaves) void mahalanobis_kernel(const floa
 //   out[3] = log1p(R) - (sum e_c s_c) / S (the entropy; a class whose e_c underflows to 0 adds 0: 0 log 0 = 0).  Both terms are >= 0.
 constexpr int kLogitKPL = 4;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void logit_scores_kernel(const float* __restrict__ z, float* __restrict__ out, int N, int K, double T) {
   const int n = (int)blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;                                           // uniform over the wave
@@ -333,14 +319,12 @@ __global__ __launch_bounds__(256) void logit_scores_kernel(const float* __restri
     v[i] = c < K ? (double)zr[c] : -INFINITY;
     mx = fmax(mx, v[i]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   int am = INT_MAX;                                             // the first class at the maximum: its term exp(0) = 1 is kept apart
 #pragma unroll
   for (int i = kLogitKPL - 1; i >= 0; --i)
     if (lane + 64 * i < K && v[i] == mx) am = lane + 64 * i;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+  am = wave_min(am);
   double r1 = 0.0, rt = 0.0, se = 0.0;
 #pragma unroll
   for (int i = 0; i < kLogitKPL; ++i) {
@@ -352,9 +336,9 @@ __global__ __launch_bounds__(256) void logit_scores_kernel(const float* __restri
       rt += exp(d / T);
     }
   }
-  r1 = wave_sum_f64(r1);
-  se = wave_sum_f64(se);
-  rt = wave_sum_f64(rt);
+  r1 = wave_sum(r1);
+  se = wave_sum(se);
+  rt = wave_sum(rt);
   if (lane == 0) {
     const double s1 = 1.0 + r1;
     float* o = out + (int64_t)n * 4;

@@ -161,11 +161,6 @@ __global__ __launch_bounds__(64) void curve_auc_kernel(const float* __restrict__
   auc[s] = (float)(a / (double)N);
 }
 
-static unsigned pt_blocks(int64_t n, int64_t cap = 8192) {
-  int64_t b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace gvk
 
 extern "C" int gvk_patch_rank(const float* rel, int32_t* rank, int S, int N, void* stream) {
@@ -180,7 +175,7 @@ extern "C" int gvk_patch_mask_rank(const int32_t* rank, const int32_t* src, cons
                                    void* stream) {
   using namespace gvk;
   GVK_REQUIRE(rank && src && lo && hi && mask && Bout > 0 && S > 0 && N > 0, "gvk_patch_mask_rank: bad arguments");
-  GVK_LAUNCH(patch_mask_rank_kernel, dim3(pt_blocks((int64_t)Bout * N)), dim3(256), 0, (hipStream_t)stream, (const int*)rank, (const int*)src,
+  GVK_LAUNCH(patch_mask_rank_kernel, dim3(grid_blocks((int64_t)Bout * N, 8192)), dim3(256), 0, (hipStream_t)stream, (const int*)rank, (const int*)src,
              (const int*)lo, (const int*)hi, mask, Bout, S, N);
   return check_launch("patch_mask_rank");
 }
@@ -189,7 +184,7 @@ extern "C" int gvk_patch_mask_box(const int32_t* boxes, uint8_t* mask, int Bout,
   using namespace gvk;
   GVK_REQUIRE(boxes && mask && Bout > 0 && nd > 0 && nh > 0 && nw > 0, "gvk_patch_mask_box: bad arguments");
   GVK_REQUIRE((int64_t)nd * nh * nw < (1LL << 24), "gvk_patch_mask_box: patch grid %dx%dx%d too large", nd, nh, nw);
-  GVK_LAUNCH(patch_mask_box_kernel, dim3(pt_blocks((int64_t)Bout * nd * nh * nw)), dim3(256), 0, (hipStream_t)stream, (const int*)boxes, mask, Bout,
+  GVK_LAUNCH(patch_mask_box_kernel, dim3(grid_blocks((int64_t)Bout * nd * nh * nw, 8192)), dim3(256), 0, (hipStream_t)stream, (const int*)boxes, mask, Bout,
              nd, nh, nw);
   return check_launch("patch_mask_box");
 }
@@ -209,10 +204,10 @@ extern "C" int gvk_perturb_volume(const float* x, const uint8_t* mask, const int
   const bool vec = pw % 4 == 0 && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)base) & 15) == 0;
   const uint32_t *xb = (const uint32_t*)x, *fb = (const uint32_t*)fill_scalar, *bb = (const uint32_t*)base;
   if (vec)
-    GVK_LAUNCH(perturb_volume_kernel<4>, dim3(pt_blocks((int64_t)Bout * V / 4)), dim3(256), 0, (hipStream_t)stream, xb, mask, (const int*)src, fb, bb,
+    GVK_LAUNCH(perturb_volume_kernel<4>, dim3(grid_blocks((int64_t)Bout * V / 4, 8192)), dim3(256), 0, (hipStream_t)stream, xb, mask, (const int*)src, fb, bb,
                nbase, (uint32_t*)out, Bout, S, D, H, W, pd, ph, pw);
   else
-    GVK_LAUNCH(perturb_volume_kernel<1>, dim3(pt_blocks((int64_t)Bout * V)), dim3(256), 0, (hipStream_t)stream, xb, mask, (const int*)src, fb, bb, nbase,
+    GVK_LAUNCH(perturb_volume_kernel<1>, dim3(grid_blocks((int64_t)Bout * V, 8192)), dim3(256), 0, (hipStream_t)stream, xb, mask, (const int*)src, fb, bb, nbase,
                (uint32_t*)out, Bout, S, D, H, W, pd, ph, pw);
   return check_launch("perturb_volume");
 }

@@ -119,10 +119,10 @@ __global__ __launch_bounds__(256) void roc_replicates_kernel(const long long* __
       else if (here && !before) { o[0] = TPg; o[1] = FPg; }                 // the first point that reaches the sensitivity
     }
   }
+  acc = wave_sum(acc);
+  pairs = wave_sum(pairs);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    acc += __shfl_xor(acc, o, 64);
-    pairs += __shfl_xor(pairs, o, 64);
     const unsigned long long other = __shfl_xor(best, o, 64);
     best = other > best ? other : best;
   }

@@ -87,8 +87,7 @@ __global__ __launch_bounds__(256) void risk_coverage_kernel(const long long* __r
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum(acc);
   if (lane == 0) s_red[wave] = acc;
   __syncthreads();
   if (t == 0) {
@@ -105,12 +104,7 @@ constexpr int kFitMaxIter = 64;
 // the block's sum of three per-thread doubles, the same bits in every thread: the xor butterfly of a wave, then the 16 wave partials in order
 __device__ __forceinline__ void fit_block_sum(double& a, double& b, double& c, double (*s_part)[3]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-    c += __shfl_xor(c, o, 64);
-  }
+  a = wave_sum(a), b = wave_sum(b), c = wave_sum(c);
   __syncthreads();                                                          // the partials of the evaluation before have been read
   if (lane == 0) { s_part[wave][0] = a; s_part[wave][1] = b; s_part[wave][2] = c; }
   __syncthreads();

@@ -36,15 +36,7 @@ constexpr int kSW = 8;                 // waves per workgroup
 constexpr int kSL = 20;                // latent width these kernels are built for (configs/gaviko.yaml prompt_latent_dim / local_dim)
 constexpr int kK4 = kSL / 4;           // MFMA k-steps of the up projection
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-// sum over the four kq lanes that share lane & 15
-__device__ __forceinline__ float kq_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
 
 // W fragment of a down projection: W[n][c .. c+3], zero for n >= kSL (the load itself is clamped, never skipped).  WL 0: w [L][C]; 1: w [C][L]
 template <int WL>

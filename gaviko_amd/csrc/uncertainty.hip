@@ -53,17 +53,6 @@ __global__ __launch_bounds__(256) void tta_volumes_kernel(const uint32_t* __rest
 constexpr int kStatsKPL = 4;                                    // classes per lane of predictive_stats_kernel
 constexpr int kStatsMaxK = 64 * kStatsKPL;
 
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // softmax of one member row over the wave: lane l holds the classes l, l + 64, ... (p[j] = class l + 64 j; classes >= K hold 0).  Returns
 // the lowest index of the largest logit.  Called twice per member with the same inputs: the same bits both times.
 __device__ __forceinline__ int member_softmax(const float* __restrict__ z, int K, int lane, float (&p)[kStatsKPL]) {
@@ -88,7 +77,7 @@ __device__ __forceinline__ int member_softmax(const float* __restrict__ z, int K
   sum = wave_sum(sum);
 #pragma unroll
   for (int j = 0; j < kStatsKPL; ++j) p[j] = p[j] / sum;
-  return wave_min_i(am);
+  return wave_min(am);
 }
 
 // H[p] = -sum_k p_k log p_k with 0 log 0 = 0; the xor butterfly leaves the same bits in every lane
@@ -134,12 +123,12 @@ __global__ __launch_bounds__(256) void predictive_stats_kernel(const float* __re
     vmax = max(vmax, vote[j]);
   }
   top = wave_max(top);
-  vmax = wave_max_i(vmax);
+  vmax = wave_max(vmax);
   int am = INT_MAX;
 #pragma unroll
   for (int j = 0; j < kStatsKPL; ++j)
     if (lane + 64 * j < K && mean[j] == top) am = min(am, lane + 64 * j);
-  am = wave_min_i(am);
+  am = wave_min(am);
   const float h = wave_entropy(mean), he = hsum / fS;
   float var[kStatsKPL];
 #pragma unroll
@@ -233,11 +222,6 @@ __global__ __launch_bounds__(256) void calibration_bins_kernel(const float* __re
   }
 }
 
-static unsigned un_blocks(int64_t n, int64_t cap = 8192) {
-  int64_t b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace gvk
 
 extern "C" int gvk_tta_volumes(const float* x, const int32_t* src, const int32_t* flip, float* out, int Bout, int S, int D, int H, int W, void* stream) {
@@ -248,10 +232,10 @@ extern "C" int gvk_tta_volumes(const float* x, const int32_t* src, const int32_t
   GVK_REQUIRE(out + (int64_t)Bout * V <= x || x + (int64_t)S * V <= out, "gvk_tta_volumes: out must not overlap x");
   const bool vec = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
   if (vec)
-    GVK_LAUNCH(tta_volumes_kernel<4>, dim3(un_blocks((int64_t)Bout * V / 4)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)x, (const int*)src,
+    GVK_LAUNCH(tta_volumes_kernel<4>, dim3(grid_blocks((int64_t)Bout * V / 4, 8192)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)x, (const int*)src,
                (const int*)flip, (uint32_t*)out, Bout, S, D, H, W);
   else
-    GVK_LAUNCH(tta_volumes_kernel<1>, dim3(un_blocks((int64_t)Bout * V)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)x, (const int*)src,
+    GVK_LAUNCH(tta_volumes_kernel<1>, dim3(grid_blocks((int64_t)Bout * V, 8192)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)x, (const int*)src,
                (const int*)flip, (uint32_t*)out, Bout, S, D, H, W);
   return check_launch("tta_volumes");
 }

@@ -28,11 +28,6 @@ constexpr int kL = 20;            // latent width this file is built for
 constexpr int kRow = 3 * kL;      // floats per token row of q | k | v
 constexpr int kSplit = 4;         // waves per 16-token block (in the step: 4 -> 714, 8 -> 710, 16 -> 702, 2 -> 668 volumes/s; isolated 8 is the fastest)
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// reductions over the four 16-lane groups of a wave (same lane % 16)
-__device__ __forceinline__ float xsum(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
-__device__ __forceinline__ float xmax(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
-
 struct Tok { int d, h, w; };
 __device__ __forceinline__ Tok decode(int idx, int H, int W) {
   Tok t;
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(64 * kSplit) void win_mfma_fwd_kernel(WinArgs p) {
       sv[i] = ok ? s[i] : -INFINITY;
       mb = fmaxf(mb, sv[i]);
     }
-    const float mn = fmaxf(m, xmax(mb));
+    const float mn = fmaxf(m, kq_max(mb));
     const float ms = mn == -INFINITY ? 0.f : mn;         // a tile wholly outside this query's window leaves everything at zero
     const float corr = __expf(m - ms);
     l *= corr; o0 *= corr; o1 *= corr;
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(64 * kSplit) void win_mfma_fwd_kernel(WinArgs p) {
       ring[r] = fetch(kb + (kRing + r) * kSplit);
     }
   }
-  l = xsum(l);
+  l = kq_sum(l);
   if (g == 0) { sm_m[wave][l16] = m; sm_l[wave][l16] = l; }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -247,7 +242,7 @@ __device__ __forceinline__ void win_bwd_q_body(const WinArgs& p, const int* tokc
   RowOp Q = load_rowop(base + (size_t)q * kRow, g);
   Q.v *= p.scale; Q.x *= p.scale;
   const RowOp Dc = load_rowop(p.dctx + row * kL, g), Cx = load_rowop(p.ctx + row * kL, g);
-  const float delta = xsum(Dc.v[0] * Cx.v[0] + Dc.v[1] * Cx.v[1] + Dc.v[2] * Cx.v[2] + Dc.v[3] * Cx.v[3] + Dc.x * Cx.x);
+  const float delta = kq_sum(Dc.v[0] * Cx.v[0] + Dc.v[1] * Cx.v[1] + Dc.v[2] * Cx.v[2] + Dc.v[3] * Cx.v[3] + Dc.x * Cx.x);
   const float lse = p.lse[row];
   int kb0, kb1;
   block_range((qb * 16) / HW, min(qb * 16 + 15, N - 1) / HW, p.kd / 2, p.kd - 1 - p.kd / 2, p.D, HW, N, kb0, kb1);
@@ -347,7 +342,7 @@ __device__ __forceinline__ void win_bwd_kv_body(const WinArgs& p, const int* tok
     const int q0 = qb * 16;
     RowOp Q = in.Q;
     Q.v *= p.scale; Q.x *= p.scale;
-    const float del_row = xsum(in.Dc.v[0] * in.Cx.v[0] + in.Dc.v[1] * in.Cx.v[1] + in.Dc.v[2] * in.Cx.v[2] + in.Dc.v[3] * in.Cx.v[3] +
+    const float del_row = kq_sum(in.Dc.v[0] * in.Cx.v[0] + in.Dc.v[1] * in.Cx.v[1] + in.Dc.v[2] * in.Cx.v[2] + in.Dc.v[3] * in.Cx.v[3] +
                                in.Dc.x * in.Cx.x);          // delta of query q0 + l16, in all four lane groups
     const f32x4 s = dot_tile(Q, K), dp = dot_tile(in.Dc, V);   // [query q0 + 4g + i][key]
     const int4 tq4 = *(const int4*)(tokc + q0 + 4 * g);

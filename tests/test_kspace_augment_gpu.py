@@ -75,9 +75,7 @@ def _report(tag, got, ref, bound):
 
 
 # ------------------------------------------------------------------------------------------------ ghosting
-@pytest.mark.parametrize("axis", [0, 1, 2])
-@pytest.mark.parametrize("shape", SHAPES)
-def test_ghosting_vs_fft(dev, shape, axis):
+def _check_ghosting_vs_fft(dev, shape, axis):
     vols = np.stack([_vol(shape, 10 + axis), _ramp(shape), _line(shape, axis), _vol(shape, 20 + axis)])
     n, g = [2, 3, 1, 7], [0.7, 1.0, 0.9, 0.55]                           # n dividing and not dividing the extent, n = 1, g = 1
     got, ctab = _ghost(dev, vols, n, g, [axis] * 4)
@@ -85,6 +83,18 @@ def test_ghosting_vs_fft(dev, shape, axis):
         ref = kspace_ref.ghosting_fft(vols[b], n[b], axis, g[b])
         _report(f"ghosting {shape} axis {axis} sample {b} n {n[b]} g {g[b]}", got[b], ref, _ghost_bound(ctab[b], vols[b], axis))
     assert np.abs(got[0] - vols[0]).max() > 10.0                         # an artifact, not a copy
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_ghosting_vs_fft(dev, shape, axis):
+    _check_ghosting_vs_fft(dev, shape, axis)
+
+
+# 240 voxels on the convolved axis: 15 tiles, all 8 accumulators of a wave live, the second wave pair one tile past the axis
+@pytest.mark.parametrize("shape,axis", [((2, 3, 240), 2), ((240, 2, 4), 0), ((2, 240, 4), 1)])
+def test_ghosting_vs_fft_with_eight_accumulators(dev, shape, axis):
+    _check_ghosting_vs_fft(dev, shape, axis)
 
 
 @pytest.mark.parametrize("axis", [0, 1, 2])

@@ -93,7 +93,8 @@ EXACT = [
      [[(1, 0, 0), (0, -4, 9), (-17, 2, -3)], [(3, 3, -3), (0, 0, 80), (-1, 1, 1)]]),
     ((3, 7, 33), [[0.3], [0.7]], [[(1, -1, 5)], [(-4, 2, -6)]]),                                      # K = 1 on both sides of 0.5; odd W; 21 lines; V % 4 != 0
     ((2, 3, 20), [[0.31, 0.34], [0.3, 0.7]], [[(0, 1, -2), (1, 0, 3)], [(-1, -1, 1), (0, 4, -1)]]),   # W below one tile pair; an empty slab
-]
+    ((2, 3, 240), [[0.3], [0.7]], [[(1, -1, 5)], [(0, 2, -250)]]),                                    # 15 column tiles: 8 accumulators per wave, the
+]                                                                                                     # second wave pair one tile past the line
 
 
 def _check_exact(dev, shape, times, trans, tag):
